@@ -16,7 +16,17 @@ puts the operand inside fp16's range) on the fp16 MFMA -- its error against floa
 in all three fp32-result modes at one tolerance); --math bf16x3 (six bf16 products, round 2's default) and
 --math fp32 (v_mfma_f32_32x32x2_f32) are reported beside the headline under other_configs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0: metric, value (images/s over the --steps timed steps), unit, higher_is_better, dtype,
+ms_per_step (one timed step), the configuration, and nothing a plain run has to measure separately.  A plain run sets up,
+warms up, times the steps, writes the last timed step's outputs if --dump-outputs DIR is given, and prints the line.
+
+--dump-outputs DIR: what a caller of the timed step receives after the LAST timed step, as DIR/<name>.npy (float32; float64
+for integer outputs): the training graph's outputs (cls_prob, loc_loss, cls_target, det_out, seg_out) and the weights after
+the SGD update; --mode infer: det_out and seg_out of the test graph.  64 MB in all: an array larger than its even share of
+that is written as DIR/<name>_sample.npy, a fixed sample (one entry per equal stride of the flattened array, at an offset
+drawn from a PCG64 generator seeded with 0), so that two builds run with the same arguments can be compared file by file.
+
+--full adds, all of it outside the timed region except the two instrumented steps of `roofline`:
   roofline     - the implicit-GEMM convolution family: algorithmic conv FLOPs executed per step / conv
                  kernel time per step, the latter measured live with HIP events on the launch stream
                  over the timed region; peak = the instruction that bounds the mode (f16x2: 16-bit MFMA
@@ -27,7 +37,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                  apply, SGD): algorithmic bytes / event-timed kernel time / 8 TB/s, measured after the timed region;
   cpu_baseline - the CPU restatement of the same step (oracle/dspnet_torch.py, fp32, all host cores) on a bounded sample
                  at B = 4 (`value`) and B = 1 (`conv_path`), and the multibox operators alone through the C restatement,
-                 one thread and over the batch (`multibox_ops`); rank 0, N = 1 only.
+                 one thread and over the batch (`multibox_ops`); rank 0, N = 1 only;
+  sustained    - 200 further steps with the engine clock and board power sampled;
+  other_configs - short side measurements of the other BASELINE.json configurations and math modes (N = 1).
 """
 import argparse
 import ctypes
@@ -80,25 +92,68 @@ def parse():
                          "0 at N = 1; at N > 1 switched to 16 after warm-up iff the exposed all-reduce time exceeds 1 ms")
     ap.add_argument("--wide-tiles", type=int, default=0,
                     help="dspn_conv_set_wide_tiles: 0 automatic (default), 1 never (the round-4 128x128 kernels), 2 / 3 / 4 force a shape")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, roofline_ops, cpu_baseline, "
+                         "math_accuracy_check, sustained, other_configs (the --no-* switches below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (64 MB at most; see the module docstring)")
     ap.add_argument("--sustained-steps", type=int, default=-1,
-                    help="further steps run AFTER the timed region for the `sustained` block of the line (0: skip; default: 200, "
-                         "or 0 for the short experiment runs that pass --no-other-configs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="--full: further steps run AFTER the timed region for the `sustained` block of the line (0: skip; "
+                         "default: 200, or 0 for the short experiment runs that pass --no-other-configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline and math_accuracy_check")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without roofline and roofline_ops")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short side measurements of BASELINE.json configs[1] (vgg16_reduced, bs 16), configs[3] "
+                    help="--full without the short side measurements of BASELINE.json configs[1] (vgg16_reduced, bs 16), configs[3] "
                          "(inceptionv3 1024x512, bs 8, bf16) and configs[4] (inference p50, bs 64) at N=1")
     ap.add_argument("--cpu-images", type=int, default=2)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher plumbing only (gloo, no GPU): every rank joins, rank 0 prints {dry_run, n_gpus}")
     ap.add_argument("--mode", choices=["train", "infer"], default="train",
-                    help="infer = BASELINE.json configs[4]: forward-only test graph + MultiBoxDetection/NMS, p50 latency")
-    return ap.parse_args()
+                    help="infer = BASELINE.json configs[4]: forward-only test graph + MultiBoxDetection/NMS, p50 latency "
+                         "over --steps iterations after --warmup ones")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_roofline = args.no_other_configs = True
+        args.sustained_steps = 0
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: arrays = [(name, device or host tensor)] -> path/<name>.npy, or path/<name>_sample.npy for an array
+    larger than its even share of DUMP_BUDGET_BYTES (module docstring)"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    total = 0
+    for name, t in arrays:
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        n, k = t.numel(), share // (8 if dtype == torch.float64 else 4)
+        if n > k:                       # (flattened)
+            t = t.reshape(-1)[torch.from_numpy(sample_offsets(n, k)).to(t.device)]
+            name += "_sample"
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+
+
+def sample_offsets(n, k):
+    """k sorted flat indices into n entries: one per equal stride, at an offset drawn from PCG64(0) -- the same for every run"""
+    import numpy as np
+    stride = n // k
+    off = np.random.Generator(np.random.PCG64(0)).integers(0, stride, size=k)
+    return np.arange(k, dtype=np.int64) * n // k + off
 
 
 def run_infer(args):
     """configs[4]: Inference-only path, bs=64 512x512, HIP multibox_detection + NMS, p50 latency over
-    >= 100 iterations after 10 warm-ups."""
+    --steps iterations after --warmup ones (>= 100 after 10)."""
     import numpy as np
     import torch
     from dspnet_amd import synthetic
@@ -109,8 +164,8 @@ def run_infer(args):
     det = Detector("resnet-50", args.size, num_classes=8, batch_size=B, device=dev)
     data = torch.from_numpy(synthetic.images(B, args.size, args.size, synthetic.rng(233))).to(dev)
     det.net.data.data.copy_(data)
-    iters = max(args.steps, 100)
-    for _ in range(10):
+    iters = args.steps
+    for _ in range(args.warmup):
         det.forward()
     torch.cuda.synchronize()
     lat = []
@@ -119,10 +174,12 @@ def run_infer(args):
         det.forward()
         torch.cuda.synchronize()
         lat.append((time.perf_counter() - t0) * 1e3)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, list(zip(("det_out", "seg_out"), det.net.outputs())))
     lat = np.sort(np.asarray(lat))
     p50 = float(np.percentile(lat, 50))
     print(json.dumps({"metric": "inference p50 latency, multitask detector forward + MultiBoxDetection/NMS", "value": round(p50, 3),
-                      "unit": "ms/batch", "n_gpus": 1, "steps": iters, "warmup": 10, "ms_per_step": round(p50, 3),
+                      "unit": "ms/batch", "n_gpus": 1, "steps": iters, "warmup": args.warmup, "ms_per_step": round(p50, 3),
                       "higher_is_better": False, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
                       "data": "synthetic", "p90_ms": round(float(np.percentile(lat, 90)), 3),
                       "images_per_s": round(B / p50 * 1e3, 1),
@@ -750,6 +807,9 @@ def main():
     exposed_ms = solver.reducer.exposed_ms() if solver.reducer is not None else None
     bucket_ms = solver.reducer.bucket_latency_ms() if solver.reducer is not None else None
     n_buckets = len(solver.buckets)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, list(zip(("cls_prob", "loc_loss", "cls_target", "det_out", "seg_out"), net.outputs()))
+                     + [("weights", net.g.arena)])
     # OUTSIDE the timed region (never part of `value`): the same step for SUSTAINED_STEPS further steps -- the headline's K
     # steps last under a second and say nothing about the clock the chip settles to -- with the engine clock and board power
     # sampled from sysfs while they run, where the box lets this process read them

@@ -8,6 +8,6 @@ DSPN_LIB=dspnet_amd/libdspn_hip_base.so python scratch/layer_bench.py 32 > $OUT/
 python scratch/layer_bench.py 32 > $OUT/lb_new.txt 2>&1
 tail -1 $OUT/lb_base.txt; tail -1 $OUT/lb_new.txt
 for i in 1 2; do
-DSPN_LIB=dspnet_amd/libdspn_hip_base.so python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('base', d['value'], d['roofline']['achieved'])"
-python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('new ', d['value'], d['roofline']['achieved'])"
+DSPN_LIB=dspnet_amd/libdspn_hip_base.so python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('base', d['value'], d['roofline']['achieved'])"
+python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('new ', d['value'], d['roofline']['achieved'])"
 done

@@ -16,7 +16,7 @@ bash scratch/r05/ops_prof.sh > gpurun_out/final_r06/ops_prof.txt 2>&1; python sc
 cp gpurun_out/final_r06/ops_prof.txt gpurun_out/profiles_r06/r06_multibox_ops_alone.txt
 ( echo "# same box, alternating: the tile-spanning loop off (DSPN_XT=0) / on (default)"; echo "# columns: images/s, ms per step, conv family TFLOP/s, conv family ms per step"
 for R in 1 2 3; do for X in 0 1; do
-DSPN_XT=$X python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | python -c "
+DSPN_XT=$X python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); r=l['roofline']
 print('xt$X', l['value'], l['ms_per_step'], r['achieved'], r['conv_ms_per_step'])"

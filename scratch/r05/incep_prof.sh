@@ -1,6 +1,6 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-ARGS="--network inceptionv3 --size 512 --width 1024 --batch 8 --store bf16 --no-cpu-baseline --no-other-configs"
+ARGS="--full --network inceptionv3 --size 512 --width 1024 --batch 8 --store bf16 --no-cpu-baseline --no-other-configs"
 python3 bench.py $ARGS --steps 20 --warmup 5 | tail -1 > gpurun_out/incep_line.json
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/incep_prof -o kt -- python3 bench.py $ARGS --steps 6 --warmup 2 > gpurun_out/incep_prof.log 2>&1
 T=$(ls gpurun_out/incep_prof/*kernel_trace.csv | head -1)

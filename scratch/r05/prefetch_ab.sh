@@ -8,6 +8,6 @@ python scratch/layer_bench.py 32 > $OUT/layer_table_new.txt 2>&1; tail -1 $OUT/l
 DSPN_LIB=$PWD/dspnet_amd/libdspn_hip_var.so python scratch/layer_bench.py 32 > $OUT/layer_table_old.txt 2>&1; tail -1 $OUT/layer_table_old.txt
 line() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline'].get('conv_ms_per_step'))"; }
 for i in 1 2 3; do
-DSPN_LIB=$PWD/dspnet_amd/libdspn_hip_var.so timeout 600 python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line old
-timeout 600 python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line new
+DSPN_LIB=$PWD/dspnet_amd/libdspn_hip_var.so timeout 600 python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line old
+timeout 600 python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line new
 done

@@ -6,9 +6,9 @@ timeout 900 python -m pytest tests/test_nn_gpu.py -x -q -m gpu -k "piece_planes 
 python scratch/layer_bench.py 32 > $OUT/layer_table.txt 2>&1; tail -2 $OUT/layer_table.txt
 line() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline'].get('conv_ms_per_step'))"; }
 for i in 1 2; do
-timeout 600 python bench.py --no-cpu-baseline --no-other-configs --wide-tiles 1 2>/dev/null | tail -1 | line narrow
-timeout 600 python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line auto
+timeout 600 python bench.py --full --no-cpu-baseline --no-other-configs --wide-tiles 1 2>/dev/null | tail -1 | line narrow
+timeout 600 python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line auto
 done
 for thr in 4 2 1; do
-DSPN_X_PLANES_MIN_READS=$thr timeout 600 python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line "auto_minreads$thr"
+DSPN_X_PLANES_MIN_READS=$thr timeout 600 python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 | line "auto_minreads$thr"
 done

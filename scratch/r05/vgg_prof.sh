@@ -1,6 +1,6 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-ARGS="--network vgg16_reduced --batch 16 --no-cpu-baseline --no-other-configs"
+ARGS="--full --network vgg16_reduced --batch 16 --no-cpu-baseline --no-other-configs"
 python3 bench.py $ARGS --steps 10 --warmup 3 | tail -1 > gpurun_out/vgg_line.json
 python3 bench.py $ARGS --steps 10 --warmup 3 --wide-tiles 1 | tail -1 > gpurun_out/vgg_line_narrow.json
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/vgg_prof -o kt -- python3 bench.py $ARGS --steps 4 --warmup 2 > gpurun_out/vgg_prof.log 2>&1

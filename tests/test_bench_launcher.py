@@ -79,3 +79,50 @@ def test_ranks_report_their_device_before_the_first_step():
     r = _run("--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0")
     assert r.returncode == 0, r.stderr[-2000:]
     assert "[bench rank 0/2] device 0" in r.stderr and "[bench rank 1/2] device 1" in r.stderr
+
+
+def _bench_module():
+    import importlib
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    return importlib.import_module("bench")
+
+
+def test_a_plain_run_leaves_the_extra_measurements_to_full(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.no_cpu_baseline and a.no_roofline and a.no_other_configs and a.sustained_steps == 0
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and not (a.no_cpu_baseline or a.no_roofline or a.no_other_configs) and a.sustained_steps == -1
+    assert a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_small_arrays_whole_and_a_fixed_sample_of_large_ones(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 4096)
+    small = torch.randn(3, 5)
+    labels = torch.arange(7, dtype=torch.int64)
+    big = torch.randn(10000)
+    arrays = [("small", small), ("labels", labels), ("big", big)]
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["big_sample.npy", "labels.npy", "small.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 3 * 4096
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
+    lab = np.load(tmp_path / "a" / "labels.npy")
+    assert lab.dtype == np.float64 and np.array_equal(lab, np.arange(7))
+    sample = np.load(tmp_path / "a" / "big_sample.npy")
+    idx = bench.sample_offsets(10000, 1024)
+    assert sample.shape == (1024,) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 10000
+    np.testing.assert_array_equal(sample, big.numpy()[idx])
