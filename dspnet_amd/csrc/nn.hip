@@ -89,12 +89,28 @@ __global__ __launch_bounds__(kT) void bn_stats_partial_kernel(const CA4Ptr x,
   }
 }
 
-// 64 channels x 16 slab-lanes per block; also folds gamma/beta into scale/shift for the apply pass
+// moving statistics of the two finalize kernels below (include/dspn_nn.h dspn_bn_moving, passed by value; mode 0: none).
+// keep = momentum, take = 1 - momentum, unbias = n / (n - 1) (1 at n == 1) are formed in double on the host
+struct BnMovingK {
+  float *mean, *var;
+  double keep, take, unbias;
+  int mode, channels;
+};
+// DSPN_BN_TRACK, one thread per channel: the batch's (mean, biased var) into the moving statistics, in double (cuDNN's
+// running-average convention: the unbiased variance); pad lanes untouched
+__device__ __forceinline__ void bn_moving_track(const BnMovingK &mv, const int c, const double m, const double var) {
+  if (c >= mv.channels) return;
+  mv.mean[c] = (float)(mv.keep * (double)mv.mean[c] + mv.take * m);
+  mv.var[c] = (float)(mv.keep * (double)mv.var[c] + mv.take * (var * mv.unbias));
+}
+
+// 64 channels x 16 slab-lanes per block; also folds gamma/beta into scale/shift for the apply pass.
+// DSPN_BN_GLOBAL: launched with nslabs = 0 (no statistics pass ran); mean / rstd come from the moving statistics
 __global__ __launch_bounds__(1024) void bn_stats_final_kernel(
     const CA1Ptr x, const float *__restrict__ partial, int nslabs, long long rows, int C,
     float eps, const float *__restrict__ gamma, const float *__restrict__ beta,
     float *__restrict__ mean, float *__restrict__ rstd, float *__restrict__ scale,
-    float *__restrict__ shift) {
+    float *__restrict__ shift, const BnMovingK mv) {
   __shared__ double s_S[16][64];
   __shared__ double s_SS[16][64];
   const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
@@ -110,12 +126,20 @@ __global__ __launch_bounds__(1024) void bn_stats_final_kernel(
   s_S[sl][cl] = S; s_SS[sl][cl] = SS;
   __syncthreads();
   if (sl == 0 && c < C) {
-    for (int k = 1; k < 16; ++k) { S += s_S[k][cl]; SS += s_SS[k][cl]; }
-    const double n = (double)rows;
-    const double m = S / n;
-    double var = SS / n - m * m;
-    if (var < 0) var = 0;
-    const float mu = (float)((double)x[c] + m);
+    double xm, var;
+    if (mv.mode == DSPN_BN_GLOBAL) {
+      xm = mv.mean[c];
+      var = mv.var[c];
+    } else {
+      for (int k = 1; k < 16; ++k) { S += s_S[k][cl]; SS += s_SS[k][cl]; }
+      const double n = (double)rows;
+      const double m = S / n;
+      var = SS / n - m * m;
+      if (var < 0) var = 0;
+      xm = (double)x[c] + m;
+      if (mv.mode == DSPN_BN_TRACK) bn_moving_track(mv, c, xm, var);
+    }
+    const float mu = (float)xm;
     const float rs = (float)(1.0 / sqrt(var + (double)eps));
     mean[c] = mu; rstd[c] = rs;
     const float sc = (gamma ? gamma[c] : 1.f) * rs;
@@ -129,19 +153,21 @@ __global__ __launch_bounds__(1024) void bn_stats_final_kernel(
 // (the cancellation in B/rows - mean^2 is harmless in double: the per-tile quantities carry 24 bits)
 // The loop is unrolled so that 8 loads per accumulator are in flight: the kernel sits alone between two
 // convolutions and is pure load latency.
-__global__ __launch_bounds__(1024) void bn_stats_tiles_final_kernel(
+// (amdgpu_waves_per_eu(8): with the moving-statistics tail the scheduler let the unrolled sweep grow from 64 to 72 VGPRs,
+// one workgroup per CU instead of two; held at 8 waves it allocates 52, no spills)
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void bn_stats_tiles_final_kernel(
     const float *__restrict__ ts, int tiles, int tile_rows, long long rows, int C, float eps,
     const float *__restrict__ gamma, const float *__restrict__ beta, float *__restrict__ mean,
     float *__restrict__ rstd, float *__restrict__ scale, float *__restrict__ shift,
     const float *__restrict__ mm, int mm_tiles, int relu, unsigned *__restrict__ absmax, unsigned *__restrict__ absmin,
-    float *__restrict__ chan_minmax) {
+    float *__restrict__ chan_minmax, const BnMovingK mv) {
   __shared__ double sA[64][17], sB[64][17];
   __shared__ float sLo[64][17], sHi[64][17];
   const int cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
   const long long last_n = rows - (long long)(tiles - 1) * tile_rows;
   double A = 0, B = 0;
-  if (c < C) {
+  if (c < C) {         // (DSPN_BN_GLOBAL: launched with tiles = 0, the statistics table is not read)
 #pragma unroll 8
     for (int t = sl; t < tiles; t += 64) {
       const double n = (double)(t == tiles - 1 ? last_n : (long long)tile_rows);
@@ -170,10 +196,17 @@ __global__ __launch_bounds__(1024) void bn_stats_tiles_final_kernel(
   }
   __syncthreads();
   if (sl == 0 && c < C) {
-    for (int k = 4; k < 64; k += 4) { A += sA[k][cl]; B += sB[k][cl]; }      // (entries k .. k + 3 hold the same wave sum)
-    const double m = A / (double)rows;
-    double var = B / (double)rows - m * m;
-    if (var < 0) var = 0;
+    double m, var;
+    if (mv.mode == DSPN_BN_GLOBAL) {
+      m = mv.mean[c];
+      var = mv.var[c];
+    } else {
+      for (int k = 4; k < 64; k += 4) { A += sA[k][cl]; B += sB[k][cl]; }      // (entries k .. k + 3 hold the same wave sum)
+      m = A / (double)rows;
+      var = B / (double)rows - m * m;
+      if (var < 0) var = 0;
+      if (mv.mode == DSPN_BN_TRACK) bn_moving_track(mv, c, m, var);
+    }
     const float mu = (float)m;
     const float rs = (float)(1.0 / sqrt(var + (double)eps));
     mean[c] = mu; rstd[c] = rs;
@@ -1670,31 +1703,65 @@ static size_t bn_tiles_workspace_bytes(int tiles, int C) {
 size_t dspn_bn_workspace_bytes(long long rows, int C) { return bn_workspace_bytes(rows, C); }
 #endif
 
-int DSPN_FN(dspn_bn_stats)(const st_t *x, long long rows, int C, float eps, const float *gamma,
-                      const float *beta, float *mean, float *rstd, float *scale, float *shift,
-                      void *workspace, size_t workspace_bytes, void *stream) {
+// the dspn_bn_moving block of an `_ex` call -> the kernels' by-value form (mode 0 for NULL), checked before any HIP call
+static int bn_moving_arg(const dspn_bn_moving *mv, long long rows, int C, const char *what, BnMovingK *out) {
+  *out = BnMovingK{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0};
+  if (!mv) return 0;
+  DSPN_REQUIRE(mv->moving_mean && mv->moving_var, "%s: moving_mean and moving_var must not be NULL", what);
+  DSPN_REQUIRE(mv->momentum >= 0.f && mv->momentum <= 1.f, "%s: momentum must be in [0, 1]", what);
+  DSPN_REQUIRE(mv->mode == DSPN_BN_TRACK || mv->mode == DSPN_BN_GLOBAL, "%s: mode must be DSPN_BN_TRACK or DSPN_BN_GLOBAL", what);
+  DSPN_REQUIRE(mv->channels >= 0 && mv->channels <= C, "%s: channels must be in [0, C]", what);
+  const double n = (double)rows;
+  *out = BnMovingK{mv->moving_mean, mv->moving_var, (double)mv->momentum, 1.0 - (double)mv->momentum,
+                   rows > 1 ? n / (n - 1.0) : 1.0, mv->mode, mv->channels ? mv->channels : C};
+  return 0;
+}
+
+static int bn_stats_run(const st_t *x, long long rows, int C, float eps, const float *gamma, const float *beta, float *mean,
+                        float *rstd, float *scale, float *shift, void *workspace, size_t workspace_bytes, const BnMovingK &mv,
+                        void *stream) {
   DSPN_REQUIRE(x && beta && mean && rstd && scale && shift && workspace, "bn_stats: null pointer");
   DSPN_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, "bn_stats: C must be a positive multiple of 4");
   if (workspace_bytes < bn_workspace_bytes(rows, C))
     return dspn::fail(DSPN_ERR_WORKSPACE_, "bn_stats: workspace too small");
-  const int C4 = C / 4, CL = std::min(C4, 64), ns = bn_slabs(rows);
+  const int C4 = C / 4, CL = std::min(C4, 64);
+  int ns = 0;
   float *partial = static_cast<float *>(workspace);
-  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(ns, (C4 + CL - 1) / CL), dim3(kT),
-                     sizeof(float4) * 2 * kT, S_(stream), CA4Ptr(x), rows,
-                     C4, CL, partial, slab_rows_for(rows));
+  if (mv.mode != DSPN_BN_GLOBAL) {      // (DSPN_BN_GLOBAL: the coefficient kernel alone, no pass over x)
+    ns = bn_slabs(rows);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(ns, (C4 + CL - 1) / CL), dim3(kT),
+                       sizeof(float4) * 2 * kT, S_(stream), CA4Ptr(x), rows,
+                       C4, CL, partial, slab_rows_for(rows));
+  }
   hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + 63) / 64), dim3(1024), 0, S_(stream), CA1Ptr(x), partial,
-                     ns, rows, C, eps, gamma, beta, mean, rstd, scale, shift);
+                     ns, rows, C, eps, gamma, beta, mean, rstd, scale, shift, mv);
   return dspn::check_launch("bn_stats");
+}
+
+int DSPN_FN(dspn_bn_stats)(const st_t *x, long long rows, int C, float eps, const float *gamma,
+                      const float *beta, float *mean, float *rstd, float *scale, float *shift,
+                      void *workspace, size_t workspace_bytes, void *stream) {
+  return bn_stats_run(x, rows, C, eps, gamma, beta, mean, rstd, scale, shift, workspace, workspace_bytes,
+                      BnMovingK{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0}, stream);
+}
+
+int DSPN_FN(dspn_bn_stats_ex)(const st_t *x, long long rows, int C, float eps, const float *gamma,
+                         const float *beta, float *mean, float *rstd, float *scale, float *shift,
+                         void *workspace, size_t workspace_bytes, const dspn_bn_moving *moving, void *stream) {
+  BnMovingK mv;
+  if (const int st = bn_moving_arg(moving, rows, C, "bn_stats_ex", &mv)) return st;
+  return bn_stats_run(x, rows, C, eps, gamma, beta, mean, rstd, scale, shift, workspace, workspace_bytes, mv, stream);
 }
 
 #ifndef DSPN_HALF
 size_t dspn_bn_tiles_workspace_bytes(int tiles, int C) { return bn_tiles_workspace_bytes(tiles, C); }
 #endif
 #ifndef DSPN_HALF
-int dspn_bn_stats_from_tiles_f32(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
-                                 const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
-                                 float *shift, const float *tile_minmax, int relu, float *out_absmax, float *out_absmin,
-                                 float *out_chan_minmax, void *workspace, size_t workspace_bytes, void *stream) {
+static int bn_stats_from_tiles_run(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
+                                   const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
+                                   float *shift, const float *tile_minmax, int relu, float *out_absmax, float *out_absmin,
+                                   float *out_chan_minmax, void *workspace, size_t workspace_bytes, const BnMovingK &mv,
+                                   void *stream) {
   DSPN_REQUIRE(tile_stats && beta && mean && rstd && scale && shift && tiles > 0 && tile_rows > 0 && C > 0 &&
                    rows > (long long)(tiles - 1) * tile_rows && rows <= (long long)tiles * tile_rows,
                "bn_stats_from_tiles: bad argument");
@@ -1709,11 +1776,29 @@ int dspn_bn_stats_from_tiles_f32(const float *tile_stats, int tiles, int tile_ro
     tile_stats = grouped; tiles = groups; tile_rows *= kTileGroup;
     if (tile_minmax) { tile_minmax = grouped_mm; mm_tiles = groups; }
   }
-  hipLaunchKernelGGL(bn_stats_tiles_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, S_(stream), tile_stats, tiles,
-                     tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, tile_minmax, mm_tiles, relu,
+  hipLaunchKernelGGL(bn_stats_tiles_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, S_(stream), tile_stats,
+                     mv.mode == DSPN_BN_GLOBAL ? 0 : tiles, tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, tile_minmax, mm_tiles, relu,
                      reinterpret_cast<unsigned *>(out_absmax), reinterpret_cast<unsigned *>(tile_minmax ? out_absmin : nullptr),
-                     tile_minmax ? out_chan_minmax : nullptr);
+                     tile_minmax ? out_chan_minmax : nullptr, mv);
   return dspn::check_launch("bn_stats_from_tiles");
+}
+int dspn_bn_stats_from_tiles_f32(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
+                                 const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
+                                 float *shift, const float *tile_minmax, int relu, float *out_absmax, float *out_absmin,
+                                 float *out_chan_minmax, void *workspace, size_t workspace_bytes, void *stream) {
+  return bn_stats_from_tiles_run(tile_stats, tiles, tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, tile_minmax,
+                                 relu, out_absmax, out_absmin, out_chan_minmax, workspace, workspace_bytes,
+                                 BnMovingK{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0}, stream);
+}
+int dspn_bn_stats_from_tiles_ex_f32(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
+                                    const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
+                                    float *shift, const float *tile_minmax, int relu, float *out_absmax, float *out_absmin,
+                                    float *out_chan_minmax, void *workspace, size_t workspace_bytes,
+                                    const dspn_bn_moving *moving, void *stream) {
+  BnMovingK mv;
+  if (const int st = bn_moving_arg(moving, rows, C, "bn_stats_from_tiles_ex", &mv)) return st;
+  return bn_stats_from_tiles_run(tile_stats, tiles, tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, tile_minmax,
+                                 relu, out_absmax, out_absmin, out_chan_minmax, workspace, workspace_bytes, mv, stream);
 }
 #endif
 int DSPN_FN(dspn_bn_apply)(const st_t *x, const float *scale, const float *shift, st_t *y, long long rows,

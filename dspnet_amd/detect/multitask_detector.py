@@ -17,17 +17,25 @@ MEAN_RGB = (123.0, 117.0, 104.0)
 class Detector:
     def __init__(self, network="resnet-50", data_shape=512, num_classes=8, batch_size=1, mean_pixels=MEAN_RGB,
                  nms_thresh=0.5, force_suppress=False, nms_topk=400, device=None, params=None, seed=0,
-                 model_prefix=None, epoch=0):
+                 model_prefix=None, epoch=0, use_global_stats=False, aux_params=None):
+        """use_global_stats: every BatchNorm normalises with its moving statistics (the checkpoint's aux states, or
+        aux_params), so that a detection does not depend on the other images of the batch; default: batch statistics,
+        as the reference's forward(is_train=True).  aux_params ('<bn>_moving_mean' / '<bn>_moving_var') are loaded
+        after the checkpoint's."""
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.net = get_multi_symbol(network, data_shape, num_classes=num_classes, batch_size=batch_size,
                                     nms_thresh=nms_thresh, force_suppress=force_suppress, nms_topk=nms_topk,
-                                    device=self.device, seed=seed)
+                                    device=self.device, seed=seed, use_global_stats=use_global_stats)
         if params:
             self.net.g.load_params(params)
         if model_prefix is not None:   # mx.model.load_checkpoint(model_prefix, epoch) (detect/multitask_detector.py:105)
             from ..model import load_checkpoint
-            _, args, _ = load_checkpoint(model_prefix, epoch)
+            _, args, auxs = load_checkpoint(model_prefix, epoch)
             self.net.g.set_params(args)
+            # (a global-statistics net needs every BatchNorm's statistics; a batch-statistics one does not read them)
+            self.net.g.set_aux(auxs, allow_missing=not (use_global_stats and aux_params is None))
+        if aux_params is not None:
+            self.net.g.set_aux(aux_params, allow_missing=not use_global_stats)
         self.mean = torch.tensor(mean_pixels, dtype=torch.float32, device=self.device).view(1, 3, 1, 1)
 
     def forward(self, data=None):

@@ -152,6 +152,13 @@ class Graph:
         self.params = {}
         self.param_order = []
         self.bn_names = []         # (name, channels, fix_gamma) of every BatchNorm, for checkpoint files
+        self.bn_nodes = {}         # name -> BatchNorm (moving statistics: get_aux / set_aux)
+        # moving statistics of the BatchNorms built into this graph (set by the builders before the first BatchNorm):
+        # bn_momentum (the reference's 0.9) and bn_global (every BatchNorm normalises with its moving statistics: inference)
+        self.bn_momentum, self.bn_global = 0.9, False
+        # True only while the solver runs the forward of a step that updates the parameters: the moving statistics then
+        # advance once (MultiTaskSolver._train_forward); a bare forward() leaves them as they are
+        self.bn_track = False
         self.tensors = {}
         self.all_tensors = []
         self.pre_forward = []      # callables run at the top of forward() (joins of side-stream work)
@@ -918,6 +925,34 @@ class Graph:
                 dev[:v.shape[0]] = v
             p.data.copy_(torch.from_numpy(dev))
 
+    def get_aux(self):
+        """-> the moving statistics in the reference's aux-state names and shapes: '<bn>_moving_mean' / '<bn>_moving_var'
+        -> (channels,) float32 numpy arrays, pad channels dropped"""
+        out = {}
+        for name, channels, _ in self.bn_names:
+            n = self.bn_nodes[name]
+            out[name + "_moving_mean"] = n.moving_mean[:channels].detach().cpu().numpy().copy()
+            out[name + "_moving_var"] = n.moving_var[:channels].detach().cpu().numpy().copy()
+        return out
+
+    def set_aux(self, aux_params, allow_missing=False):
+        """copy aux states ('<bn>_moving_mean' / '<bn>_moving_var', shapes (channels,)) INTO the existing moving-statistics
+        buffers (a recorded step keeps valid pointers); pad lanes keep 0 / 1.  Names the graph has no BatchNorm for are
+        ignored; a BatchNorm without a value keeps its statistics if allow_missing else raises"""
+        wanted = [name + suffix for name, _, _ in self.bn_names for suffix in ("_moving_mean", "_moving_var")]
+        missing = [k for k in wanted if k not in aux_params]
+        if missing and not allow_missing:
+            raise KeyError("set_aux: no value for " + ", ".join(missing[:8]) + (" ..." if len(missing) > 8 else ""))
+        for name, channels, _ in self.bn_names:
+            n = self.bn_nodes[name]
+            for suffix, buf in (("_moving_mean", n.moving_mean), ("_moving_var", n.moving_var)):
+                if name + suffix not in aux_params:
+                    continue
+                v = np.asarray(aux_params[name + suffix], np.float32).reshape(-1)
+                if v.shape[0] != channels:
+                    raise ValueError("set_aux: %s%s has %d values, the graph expects %d" % (name, suffix, v.shape[0], channels))
+                buf[:channels].copy_(torch.from_numpy(v))
+
     def get_params(self):
         """-> name -> numpy array in the reference's shapes (inverse of set_params; pad channels dropped)"""
         out = {}
@@ -1011,7 +1046,12 @@ X_PLANES_MIN_READS = int(_os.environ.get("DSPN_X_PLANES_MIN_READS", "6"))
 
 class BatchNorm(Node):
     """mx.sym.BatchNorm with batch statistics (the solver always runs is_train=True,
-    multi_solver.py:284) optionally fused with the following ReLU."""
+    multi_solver.py:284) optionally fused with the following ReLU.
+
+    Moving statistics (MXNet's aux states): moving_mean / moving_var (C device floats, 0 / 1 at creation, pad lanes stay
+    so) advance with `momentum` in the statistics finalize of a forward that the solver runs for a parameter update
+    (Graph.bn_track); with Graph.bn_global the node normalises with them instead of the batch's (use_global_stats: the
+    finalize folds them into scale / shift, no statistics pass).  include/dspn_nn.h dspn_bn_moving."""
 
     def __init__(self, g, x, name, fix_gamma=False, eps=2e-5, relu=False, beta_grad_from_consumer=False,
                  defer_apply=False):
@@ -1028,6 +1068,11 @@ class BatchNorm(Node):
             if p is not None:
                 p.logical = (x.channels or C,)
         g.bn_names.append((name, x.channels or C, bool(fix_gamma)))   # gamma / moving_* entries of a checkpoint
+        g.bn_nodes[name] = self
+        self.channels = x.channels or C
+        self.momentum, self.use_global_stats = float(g.bn_momentum), bool(g.bn_global)
+        self.moving_mean = torch.zeros(C, dtype=torch.float32, device=g.device)
+        self.moving_var = torch.ones(C, dtype=torch.float32, device=g.device)
         self.mean = fn.zeros(C, device=g.device)
         self.rstd = fn.zeros(C, device=g.device)
         self.scale = fn.zeros(C, device=g.device)
@@ -1066,7 +1111,18 @@ class BatchNorm(Node):
         # whose data gradient gathered the sums: (args, kwargs) of the apply half, or None
         self._pending = None
 
+    def _moving(self):
+        """the dspn_bn_moving block of this forward's finalize, or None (batch statistics, nothing tracked)"""
+        if self.use_global_stats:
+            mode = fn.BN_GLOBAL
+        elif self._g.bn_track:
+            mode = fn.BN_TRACK
+        else:
+            return None
+        return fn.bn_moving(self.moving_mean, self.moving_var, self.momentum, mode, self.channels)
+
     def forward(self):
+        moving = self._moving()
         if self.tile_stats is not None:
             buf, tiles, tile_rows = self.tile_stats
             rows = int(np.prod(self.x.shape[:-1]))
@@ -1082,13 +1138,13 @@ class BatchNorm(Node):
                                    self.mean, self.rstd, self.scale, self.shift,
                                    tile_minmax=mm if am is not None else None, relu=self.relu, out_absmax=am,
                                    out_absmin=None if am is None else g.scalars_min[slot:slot + 1],
-                                   out_chan_minmax=self.x_ext if am is not None else None)
+                                   out_chan_minmax=self.x_ext if am is not None else None, moving=moving)
             self.planes_ready = self.planes is not None and am is not None
             if self.planes_ready:
                 fn.bn_apply_planes(self.x.data, self.scale, self.shift, am, relu=self.relu, out=self.planes)
         else:
             fn.bn_stats(self.x.data, self.eps, None if self.gamma is None else self.gamma.data, self.beta.data,
-                        self.mean, self.rstd, self.scale, self.shift)
+                        self.mean, self.rstd, self.scale, self.shift, moving=moving)
         if not self.defer_apply:
             am = self._g.scalar(self.am_out)
             fn.bn_apply(self.x.data, self.scale, self.shift, relu=self.relu, out=self.out.data, out_absmax=am)

@@ -132,6 +132,25 @@ _lib.register({
 })
 
 
+class BnMoving(_c.Structure):
+    """include/dspn_nn.h dspn_bn_moving: the moving-statistics block of the `_ex` BatchNorm finalize entry points"""
+    _fields_ = [("moving_mean", _vp), ("moving_var", _vp), ("momentum", _f), ("mode", _i), ("channels", _i)]
+
+
+BN_TRACK, BN_GLOBAL = 1, 2      # DSPN_BN_TRACK / DSPN_BN_GLOBAL
+_bnmp = _c.POINTER(BnMoving)
+_lib.register({
+    "dspn_bn_stats_ex_f32": (_i, _lib.SIGNATURES["dspn_bn_stats_f32"][1][:-1] + [_bnmp, _vp]),
+    "dspn_bn_stats_ex_bf16": (_i, _lib.SIGNATURES["dspn_bn_stats_f32"][1][:-1] + [_bnmp, _vp]),
+    "dspn_bn_stats_from_tiles_ex_f32": (_i, _lib.SIGNATURES["dspn_bn_stats_from_tiles_f32"][1][:-1] + [_bnmp, _vp]),
+})
+
+
+def bn_moving(moving_mean, moving_var, momentum, mode, channels=0):
+    """-> a dspn_bn_moving block (by reference) for the `_ex` calls; mode BN_TRACK or BN_GLOBAL"""
+    return _c.byref(BnMoving(ptr(moving_mean), ptr(moving_var), float(momentum), int(mode), int(channels)))
+
+
 def L():
     return _lib.lib()
 
@@ -269,16 +288,19 @@ def conv_stats_layout(out_pixels, cout):
 
 
 def bn_stats_from_tiles(tile_stats, tiles, tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift,
-                        tile_minmax=None, relu=False, out_absmax=None, out_absmin=None, out_chan_minmax=None):
+                        tile_minmax=None, relu=False, out_absmax=None, out_absmin=None, out_chan_minmax=None, moving=None):
     """tile_minmax + out_absmax ("f16x2" math): also max the magnitude of (relu)(x * scale + shift) into the 64-slot block
-    out_absmax, from the per-tile extremes the producing convolution wrote (conv2d_forward's out_minmax)"""
+    out_absmax, from the per-tile extremes the producing convolution wrote (conv2d_forward's out_minmax).
+    moving (bn_moving(...)): track or use the moving statistics (dspn_bn_stats_from_tiles_ex_f32)"""
     ws = workspace(L().dspn_bn_tiles_workspace_bytes(tiles, C), tile_stats.device, "bn")
     assert (tile_minmax is None) == (out_absmax is None)
     assert tile_minmax is None or (tile_minmax.numel() == tile_stats.numel() and out_absmax.numel() == ABSMAX_SLOTS)
-    check(L().dspn_bn_stats_from_tiles_f32(ptr(tile_stats), tiles, tile_rows, rows, C, eps, ptr(gamma), ptr(beta), ptr(mean),
-                                           ptr(rstd), ptr(scale), ptr(shift), ptr(tile_minmax), int(bool(relu)),
-                                           ptr(out_absmax), ptr(out_absmin), ptr(out_chan_minmax), ptr(ws), ws.numel(), stream()),
-          "bn_stats_from_tiles")
+    args = (ptr(tile_stats), tiles, tile_rows, rows, C, eps, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(scale), ptr(shift),
+            ptr(tile_minmax), int(bool(relu)), ptr(out_absmax), ptr(out_absmin), ptr(out_chan_minmax), ptr(ws), ws.numel())
+    if moving is None:
+        check(L().dspn_bn_stats_from_tiles_f32(*args, stream()), "bn_stats_from_tiles")
+    else:
+        check(L().dspn_bn_stats_from_tiles_ex_f32(*args, moving, stream()), "bn_stats_from_tiles_ex")
 
 
 ABSMAX_SLOTS = 64      # include/dspn_nn.h DSPN_ABSMAX_SLOTS: a magnitude is 64 partial maxima
@@ -666,8 +688,9 @@ def _rows(x):
     return x.numel() // x.shape[-1]
 
 
-def bn_stats(x, eps, gamma, beta, mean=None, rstd=None, scale=None, shift=None):
-    """batch statistics + folded affine; returns (mean, rstd, scale, shift)"""
+def bn_stats(x, eps, gamma, beta, mean=None, rstd=None, scale=None, shift=None, moving=None):
+    """batch statistics + folded affine; returns (mean, rstd, scale, shift).  moving (bn_moving(...)): track the moving
+    statistics, or fold them instead of the batch's (dspn_bn_stats_ex_*)"""
     C = x.shape[-1]
     rows = _rows(x)
     mean = empty(C, device=x.device) if mean is None else mean
@@ -675,8 +698,11 @@ def bn_stats(x, eps, gamma, beta, mean=None, rstd=None, scale=None, shift=None):
     scale = empty(C, device=x.device) if scale is None else scale
     shift = empty(C, device=x.device) if shift is None else shift
     ws = workspace(L().dspn_bn_workspace_bytes(rows, C), x.device, "bn")
-    check(_f("dspn_bn_stats", x)(ptr(x), rows, C, eps, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(scale),
-                                ptr(shift), ptr(ws), ws.numel(), stream()), "bn_stats")
+    args = (ptr(x), rows, C, eps, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(ws), ws.numel())
+    if moving is None:
+        check(_f("dspn_bn_stats", x)(*args, stream()), "bn_stats")
+    else:
+        check(_f("dspn_bn_stats_ex", x)(*args, moving, stream()), "bn_stats_ex")
     return mean, rstd, scale, shift
 
 

@@ -152,9 +152,9 @@ def load_checkpoint(prefix, epoch):
 def save_checkpoint(prefix, epoch, net, aux_params=None):
     """mx.model.save_checkpoint for this build's graph (`net`: a MultiTaskNet or its Graph): every parameter in the
     reference's shapes under 'arg:', plus what MXNet lists for the same layers and this graph does not own:
-    `gamma` = 1 for fix_gamma BatchNorms and the moving statistics under 'aux:'.  The solver of the reference zeroes
-    the aux states and always runs with batch statistics (multi_solver.py:212,284), so they never influence an
-    output; they are written from `aux_params` when given (a loaded checkpoint carried through) else as 0 / 1."""
+    `gamma` = 1 for fix_gamma BatchNorms and the moving statistics under 'aux:'.  The moving statistics are written
+    from `aux_params` when given (a loaded checkpoint carried through: missing entries as 0 / 1), else from the graph's
+    own buffers (Graph.get_aux: what MultiTaskSolver's steps tracked; 0 / 1 in a graph that has not been trained)."""
     g = getattr(net, "g", net)
     blob = {}
     args = g.get_params()
@@ -163,7 +163,8 @@ def save_checkpoint(prefix, epoch, net, aux_params=None):
             args.setdefault(name + "_gamma", np.ones(channels, np.float32))
     for k, v in args.items():
         blob["arg:" + k] = v
-    aux_params = aux_params or {}
+    if aux_params is None:
+        aux_params = g.get_aux() if hasattr(g, "get_aux") else {}
     for name, channels, _ in g.bn_names:
         blob["aux:%s_moving_mean" % name] = np.asarray(aux_params.get(name + "_moving_mean", np.zeros(channels)), np.float32)
         blob["aux:%s_moving_var" % name] = np.asarray(aux_params.get(name + "_moving_var", np.ones(channels)), np.float32)

@@ -268,68 +268,71 @@ class MultiTaskNet:
 def get_multi_symbol_train(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                            normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                            nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), num_labels=200, device=None,
-                           num_layers=50, seed=0, **kwargs):
+                           num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False, **kwargs):
     """symbol/multitask_symbol_builder.py:442-593"""
     return _build(True, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios, normalizations,
                   steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape, num_labels, device,
-                  num_layers, seed)
+                  num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats)
 
 
 def get_multi_symbol(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                      normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                      nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), device=None, num_layers=50, seed=0,
-                     **kwargs):
+                     bn_mom=0.9, use_global_stats=False, **kwargs):
     """Test graph, symbol/multitask_symbol_builder.py:595-726: outputs [det, seg_out].  No label inputs, no
-    MultiBoxTarget, no losses; class probabilities by SoftmaxActivation(mode='channel').  BatchNorm still
-    uses batch statistics, as every shipped caller runs with is_train=True (detect/multitask_detector.py:228).
+    MultiBoxTarget, no losses; class probabilities by SoftmaxActivation(mode='channel').  BatchNorm uses batch
+    statistics by default, as every shipped caller runs with is_train=True (detect/multitask_detector.py:228);
+    use_global_stats=True normalises every BatchNorm with its moving statistics instead (Graph.set_aux loads them),
+    so that an image's outputs do not depend on the rest of its batch.  bn_mom: the momentum of the moving statistics
+    (the training builders; MXNet's 0.9).
     The reference's `mx.symbol.softmax(..., multi_output=True)` on the seg logits is read as a softmax over
     the class axis."""
     return _build(False, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  200, device, num_layers, seed)
+                  200, device, num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats)
 
 
 def get_det_symbol_train(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                          normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                          nms_topk=400, batch_size=1, data_shape=(3, 300, 300), num_labels=200, device=None,
-                         num_layers=50, seed=0, **kwargs):
+                         num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False, **kwargs):
     """Detection + depth only, symbol/multitask_symbol_builder.py:20-121: outputs [cls_prob, loc_loss, cls_label,
     det_out]; the same graph without the segmentation decoder."""
     return _build(True, False, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  num_labels, device, num_layers, seed)
+                  num_labels, device, num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats)
 
 
 def get_det_symbol(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                    normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                    nms_topk=400, batch_size=1, data_shape=(3, 300, 300), device=None, num_layers=50, seed=0,
-                   **kwargs):
+                   bn_mom=0.9, use_global_stats=False, **kwargs):
     """Detection + depth test graph, symbol/multitask_symbol_builder.py:123-209: output [det]"""
     return _build(False, False, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  200, device, num_layers, seed)
+                  200, device, num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats)
 
 
 def get_seg_symbol_train(network, num_classes, from_layers, num_filters=None, strides=None, pads=None, sizes=None,
                          ratios=None, normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5,
                          force_suppress=False, nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), device=None,
-                         num_layers=50, seed=0, **kwargs):
+                         num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False, **kwargs):
     """Segmentation only, symbol/multitask_symbol_builder.py:211-323: backbone -> pyramid decoder ->
     SoftmaxOutput(grad_scale=4, ignore 255); output [seg_out].  The SSD arguments are accepted and unused, as
     in the reference.  Gradient reaches the backbone through conv_feat only (res3 / res4 are BlockGrad'ed)."""
     return _build(True, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  0, device, num_layers, seed, with_det=False)
+                  0, device, num_layers, seed, with_det=False, bn_mom=bn_mom, use_global_stats=use_global_stats)
 
 
 def get_seg_symbol(network, num_classes, from_layers, num_filters=None, strides=None, pads=None, sizes=None,
                    ratios=None, normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                    nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), device=None, num_layers=50, seed=0,
-                   **kwargs):
+                   bn_mom=0.9, use_global_stats=False, **kwargs):
     """Segmentation test graph, symbol/multitask_symbol_builder.py:325-440: output [seg_out] (softmax over classes)"""
     return _build(False, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  0, device, num_layers, seed, with_det=False)
+                  0, device, num_layers, seed, with_det=False, bn_mom=bn_mom, use_global_stats=use_global_stats)
 
 
 def _detection_branch(g, train, internals, label, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
@@ -366,10 +369,17 @@ def _detection_branch(g, train, internals, label, num_classes, from_layers, num_
 
 def _build(train, with_seg, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios, normalizations,
            steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape, num_labels, device,
-           num_layers, seed, with_det=True):
+           num_layers, seed, with_det=True, bn_mom=0.9, use_global_stats=False):
     assert network in ("resnet", "vgg16_reduced", "inceptionv3"), "backbones: resnet, vgg16_reduced, inceptionv3"
+    if train and use_global_stats:
+        raise ValueError("use_global_stats=True is for the test graphs (get_multi_symbol / get_det_symbol / get_seg_symbol): "
+                         "training with fixed BatchNorm statistics (its backward) is not implemented")
+    if not 0.0 <= float(bn_mom) <= 1.0:
+        raise ValueError("bn_mom must be in [0, 1], got %r" % (bn_mom,))
     device = device or torch.device("cuda", torch.cuda.current_device())
     g = E.Graph(device)
+    # every BatchNorm built below: moving statistics with momentum bn_mom; use_global_stats normalises with them (inference)
+    g.bn_momentum, g.bn_global = float(bn_mom), bool(use_global_stats)
     C, H, W = data_shape
     data = g.tensor((batch_size, C, H, W), "data", requires_grad=False, dtype=torch.float32)
     label = (g.tensor((batch_size, num_labels, 6), "label_det", requires_grad=False, dtype=torch.float32)

@@ -11,6 +11,12 @@ a full replica and its own batch shard; gradients are summed with RCCL all-reduc
 buckets of the flat gradient arena, launched as soon as backward has produced every gradient of a
 bucket so the reduction overlaps the remaining dgrad/wgrad kernels, then scaled by 1/world_size
 inside the SGD kernel (`rescale_grad = 1/len(ctx)` convention of train/train_multitask.py:248).
+
+BatchNorm moving statistics (MXNet's aux states): with track_bn_stats they advance exactly once per parameter update --
+in the forward of an eager step(), of a recorded step and of every warmup step that updates -- and never in the range
+guard's calibration pass, a bare forward(), or an evaluation pass.  Under data parallelism every rank keeps the
+statistics of its own shard (MXNet keeps one set per device); they are not averaged across ranks, and rank 0 writes
+its own to a checkpoint.
 """
 from .. import functional as fn
 
@@ -123,8 +129,17 @@ class GradBucketReducer:
 
 class MultiTaskSolver:
     def __init__(self, net, learning_rate=0.0005, momentum=0.9, wd=0.0005, process_group=None,
-                 world_size=1, bucket_mb=16.0, force_reducer=False, high_priority=True):
+                 world_size=1, bucket_mb=16.0, force_reducer=False, high_priority=True, track_bn_stats=True,
+                 aux_params=None):
+        """track_bn_stats: every step advances the BatchNorm moving statistics (False: the step of earlier builds, the
+        statistics stay as they are).  aux_params ('<bn>_moving_mean' / '<bn>_moving_var', e.g. load_checkpoint's third
+        item): loaded into the graph, so that resuming and init_from_resnet keep the pretrained statistics; BatchNorms
+        without a value keep 0 / 1.  (multi_solver.py:212 zeroes the aux states instead: the reference never reads them
+        in training, but a checkpoint written here then carries statistics that match its weights.)"""
         self.net, self.g = net, net.g
+        self.track_bn_stats = bool(track_bn_stats)
+        if aux_params:
+            net.g.set_aux(aux_params, allow_missing=True)
         # the step runs on a HIGH-priority stream of its own: MultiBoxDetection's side stream (normal priority) then never
         # gets its workgroups handed out ahead of a main-path kernel that is ready (HIP has two levels, and torch's
         # current stream already sits on the lower one).  step() orders that stream behind the caller's current stream
@@ -176,7 +191,17 @@ class MultiTaskSolver:
             self.net.label_seg.data.copy_(label_seg)
 
     def forward(self):
+        """a forward pass of the step's graph; the BatchNorm moving statistics do not move (only a step does that)"""
         self.g.forward()
+
+    def _train_forward(self):
+        """the forward of a step that updates the parameters: the moving statistics advance in it (track_bn_stats)"""
+        g = self.g
+        g.bn_track = self.track_bn_stats
+        try:
+            g.forward()
+        finally:
+            g.bn_track = False
 
     def backward(self):
         g = self.g
@@ -251,7 +276,7 @@ class MultiTaskSolver:
             if (self.lr, self.momentum, self.wd) != self._graph_hyper:
                 self._graph = None
                 if not self.capture(warmup=0):
-                    self.forward(); self.backward(); self.update()
+                    self._train_forward(); self.backward(); self.update()
                     return
             self._graph.replay()
             # the range guard cannot act from inside a recorded step: every GUARD_PERIOD-th replay its spans are looked at from
@@ -264,7 +289,7 @@ class MultiTaskSolver:
                 self.graph_rerecorded += 1
                 self._rerecord = True
             return
-        self.forward()
+        self._train_forward()
         self.backward()
         self.update()
         self._ran_eager = True
@@ -303,7 +328,7 @@ class MultiTaskSolver:
             # (captured on the solver's own high-priority stream when it has one: a replayed step then runs where an eager
             # step runs, not on torch's normal-priority capture stream)
             with torch.cuda.graph(graph, **({"stream": self.stream} if self.stream is not None else {})):
-                self.forward()
+                self._train_forward()
                 self.backward()
                 self.update()
                 if det is not None:

@@ -309,7 +309,8 @@ int dspn_conv2d_weight_prepare_bf16(const float *w, dspn_bf16 *wh, dspn_bf16 *wt
 int dspn_conv2d_weight_prepare_batch_bf16(const void *table, int n, long long total_tiles, void *stream);
 
 /* ---- BatchNorm with batch statistics (+ fused ReLU) (mx.sym.BatchNorm eps=2e-5:
- * symbol/resnet.py:30-41,91,96; multitask_symbol_builder.py:545-585) ------------------ */
+ * symbol/resnet.py:30-41,91,96; multitask_symbol_builder.py:545-585); moving statistics (aux states) and global-statistics
+ * inference through the `_ex` finalize entry points below ------------------ */
 
 size_t dspn_bn_workspace_bytes(long long rows, int C);
 
@@ -341,6 +342,44 @@ int dspn_bn_stats_from_tiles_f32(const float *tile_stats, int tiles, int tile_ro
 /* optional scratch for long tile tables (>= 1024 tiles are first merged in groups of 32 by many workgroups);
  * dspn_bn_backward_from_sums_f32 uses 3*C floats + this many bytes the same way */
 size_t dspn_bn_tiles_workspace_bytes(int tiles, int C);
+
+/* ---- BatchNorm moving statistics (MXNet's aux states moving_mean / moving_var; symbol/resnet.py:11,32 momentum 0.9) ----
+ * The `_ex` entry points take the arguments of the entry point of the same name plus `const dspn_bn_moving *moving` (a HOST
+ * pointer, read during the call; its values are passed to the kernel by value, so a captured graph keeps the momentum it was
+ * recorded with).  moving == NULL is exactly the entry point without `_ex`.  Otherwise moving_mean / moving_var point at C
+ * device floats each and `mode` is one of:
+ *   DSPN_BN_TRACK  (training)  mean / rstd / scale / shift and every magnitude output are those of the plain call, bit for bit;
+ *                  the finalize then updates, in double, per channel c < channels:
+ *                    moving_mean = momentum * moving_mean + (1 - momentum) * mean
+ *                    moving_var  = momentum * moving_var  + (1 - momentum) * var * n / (n - 1)
+ *                  with var the biased batch variance over n = rows = N*H*W rows (n == 1: the biased variance).  This is the
+ *                  convention of the reference's GPU training: MXNet runs BatchNorm through cuDNN, whose running average uses
+ *                  the factor (1 - momentum) and the UNBIASED variance (cuDNN's documented behaviour; not run against MXNet here).
+ *   DSPN_BN_GLOBAL (inference) the batch statistics are not formed: rstd = 1 / sqrt(moving_var + eps), scale = gamma * rstd
+ *                  (gamma = 1 when NULL), shift = beta - moving_mean * scale; mean = moving_mean and rstd are written too.
+ *                  dspn_bn_stats_ex_*: one small coefficient kernel, no pass over x.  dspn_bn_stats_from_tiles_ex_f32: the
+ *                  (mean, M2) table is not read; the per-tile (min, max) sweep runs as before, so out_absmax / out_absmin /
+ *                  out_chan_minmax are produced under the global affine.
+ * channels: lanes c >= channels (the zero-padded physical channels) are not updated in DSPN_BN_TRACK, so they keep the
+ * 0 / 1 a caller initialises them to; 0 = all C lanes.  momentum must lie in [0, 1]. */
+#define DSPN_BN_TRACK 1
+#define DSPN_BN_GLOBAL 2
+typedef struct dspn_bn_moving {
+  float *moving_mean;
+  float *moving_var;
+  float momentum;
+  int mode;
+  int channels;
+} dspn_bn_moving;
+int dspn_bn_stats_ex_f32(const float *x, long long rows, int C, float eps, const float *gamma,
+                         const float *beta, float *mean, float *rstd, float *scale, float *shift,
+                         void *workspace, size_t workspace_bytes, const dspn_bn_moving *moving, void *stream);
+int dspn_bn_stats_from_tiles_ex_f32(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
+                                    const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
+                                    float *shift, const float *tile_minmax, int relu, float *out_absmax, float *out_absmin,
+                                    float *out_chan_minmax, void *workspace, size_t workspace_bytes,
+                                    const dspn_bn_moving *moving, void *stream);
+
 /* out_absmax (optional, float tensors): DSPN_ABSMAX_SLOTS floats that receive the partial maxima of |y| as stored --
  * dspn_absmax_f32(y) without its pass over y (round 4: the magnitude of a MATERIALISED BatchNorm output for the
  * convolutions that multiply it in DSPN_MATH_F32_F16X2).  The caller zeroes it, as for dspn_absmax_f32. */
@@ -585,6 +624,9 @@ int dspn_sgd_momentum_f32(float *w, const float *grad, float *mom, long long n, 
 int dspn_bn_stats_bf16(const dspn_bf16 *x, long long rows, int C, float eps, const float *gamma,
                       const float *beta, float *mean, float *rstd, float *scale, float *shift,
                       void *workspace, size_t workspace_bytes, void *stream);
+int dspn_bn_stats_ex_bf16(const dspn_bf16 *x, long long rows, int C, float eps, const float *gamma,
+                          const float *beta, float *mean, float *rstd, float *scale, float *shift,
+                          void *workspace, size_t workspace_bytes, const dspn_bn_moving *moving, void *stream);
 int dspn_bn_apply_bf16(const dspn_bf16 *x, const float *scale, const float *shift, dspn_bf16 *y, long long rows,
                       int C, int relu, float *out_absmax /* ignored */, void *stream);
 int dspn_bn_backward_bf16(const dspn_bf16 *x, const float *scale, const float *shift, const dspn_bf16 *dy,
