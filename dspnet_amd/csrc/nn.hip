@@ -1681,6 +1681,57 @@ __global__ void sgd_kernel(float4 *__restrict__ w, const float4 *__restrict__ g,
   }
 }
 
+// Segmented SGD (dspn_sgd_momentum_segments_f32): the rows of `seg` cover disjoint, sorted float4 ranges of the arena; the
+// launch walks the CONCATENATION of those ranges (total4 float4 in all).  Every block first forms the inclusive prefix of the
+// row lengths in LDS (one scan of nseg values), then each thread finds the row of its first float4 by binary search and
+// follows the rows forward.  Elements outside every row are never touched.  Per element the arithmetic is sgd_kernel's with
+// lr * lr_mult and wd * wd_mult formed in float32 (multipliers 1.0 give sgd_kernel's bits).
+constexpr int kSgdPer = 8;                // float4 per thread: one block covers kT * kSgdPer consecutive float4 of the rows
+__global__ void __launch_bounds__(kT) sgd_segments_kernel(float4 *__restrict__ w, const float4 *__restrict__ g,
+                                                          float4 *__restrict__ m, const dspn_sgd_segment *__restrict__ seg,
+                                                          int nseg, long long total4, float lr, float mu, float wd,
+                                                          float rescale) {
+  extern __shared__ long long s_end[];    // s_end[r] = float4 in rows 0 .. r (inclusive prefix)
+  __shared__ long long s_part[kT];
+  const int t = threadIdx.x;
+  const int per = (nseg + kT - 1) / kT;   // rows per thread in the scan
+  long long acc = 0;
+  for (int r = t * per; r < nseg && r < (t + 1) * per; ++r) { acc += seg[r].length >> 2; s_end[r] = acc; }
+  s_part[t] = acc;
+  __syncthreads();
+  for (int d = 1; d < kT; d <<= 1) {     // inclusive scan of the per-thread sums (Hillis-Steele)
+    const long long v = t >= d ? s_part[t - d] : 0;
+    __syncthreads();
+    s_part[t] += v;
+    __syncthreads();
+  }
+  const long long before = t > 0 ? s_part[t - 1] : 0;
+  for (int r = t * per; r < nseg && r < (t + 1) * per; ++r) s_end[r] += before;
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * (kT * kSgdPer);
+  long long j = base + t;
+  if (j >= total4) return;
+  int lo = 0, hi = nseg - 1;              // the first row whose end lies beyond j
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s_end[mid] > j) hi = mid; else lo = mid + 1;
+  }
+  int r = lo;
+  for (int it = 0; it < kSgdPer && j < total4; ++it, j += kT) {
+    while (r < nseg && s_end[r] <= j) ++r;
+    if (r == nseg) return;                // (total4 larger than the rows hold: the rest is not ours to touch)
+    const dspn_sgd_segment sr = seg[r];
+    const float lre = lr * sr.lr_mult, wde = wd * sr.wd_mult;
+    const long long i = (sr.offset >> 2) + (j - (s_end[r] - (sr.length >> 2)));
+    float4 wv = w[i]; const float4 gv = g[i]; float4 mv = m[i];
+    mv.x = mu * mv.x - lre * (rescale * gv.x + wde * wv.x); wv.x += mv.x;
+    mv.y = mu * mv.y - lre * (rescale * gv.y + wde * wv.y); wv.y += mv.y;
+    mv.z = mu * mv.z - lre * (rescale * gv.z + wde * wv.z); wv.z += mv.z;
+    mv.w = mu * mv.w - lre * (rescale * gv.w + wde * wv.w); wv.w += mv.w;
+    w[i] = wv; m[i] = mv;
+  }
+}
+
 #endif   // !DSPN_HALF
 
 int bn_slabs(long long rows) { const int sr = slab_rows_for(rows); return (int)((rows + sr - 1) / sr); }
@@ -1835,7 +1886,7 @@ int DSPN_FN(dspn_bn_backward)(const st_t *x, const float *scale, const float *sh
                          const float *mean, const float *rstd, const float *gamma, st_t *dx,
                          float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
                          float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream) {
-  DSPN_REQUIRE(x && dy && mean && rstd && dx && workspace, "bn_backward: null pointer");
+  DSPN_REQUIRE(x && dy && mean && rstd && workspace, "bn_backward: null pointer");
   DSPN_REQUIRE(!relu || (scale && shift), "bn_backward: relu needs the forward scale/shift");
   DSPN_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, "bn_backward: C must be a positive multiple of 4");
   if (workspace_bytes < bn_workspace_bytes(rows, C))
@@ -1850,6 +1901,7 @@ int DSPN_FN(dspn_bn_backward)(const st_t *x, const float *scale, const float *sh
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(1024), 0, S_(stream), partial, ns, C,
                      1.0 / (double)rows, mean, rstd, gamma, coef, dgamma, dbeta, nullptr, nullptr, nullptr,
                      static_cast<unsigned *>(nullptr));
+  if (!dx) return dspn::check_launch("bn_backward (parameters only)");     // dx == NULL: the reductions and the finalize alone
   const long long n4 = rows * C4;
 #ifdef DSPN_HALF
   if (C % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
@@ -1878,7 +1930,7 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
                                  const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
                                  int Wo, const float *mean, const float *rstd, const float *gamma, float *dx, float *dgamma,
                                  float *dbeta, int relu, float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream) {
-  DSPN_REQUIRE(x && dy_pool && argmax && mean && rstd && dx && dbeta && workspace, "bn_backward_maxpool: null pointer");
+  DSPN_REQUIRE(x && dy_pool && argmax && mean && rstd && workspace, "bn_backward_maxpool: null pointer");
   DSPN_REQUIRE(!relu || (scale && shift), "bn_backward_maxpool: relu needs the forward scale/shift");
   DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && k > 0 && k * k <= 255 && stride > 0 && pad >= 0 && Ho > 0 && Wo > 0,
                "bn_backward_maxpool: bad geometry (C %% 4 == 0, k * k <= 255)");
@@ -1896,6 +1948,7 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(1024), 0, S_(stream), partial, ns, C,
                      1.0 / (double)rows, mean, rstd, gamma, coef, dgamma, dbeta, nullptr, nullptr, nullptr,
                      static_cast<unsigned *>(nullptr));
+  if (!dx) return dspn::check_launch("bn_backward_maxpool (parameters only)");
   const long long n4 = rows * C4;
   hipLaunchKernelGGL(bn_bwd_apply_pool_kernel, dim3(grid_for(n4)), dim3(256), 0, S_(stream), reinterpret_cast<const float4 *>(x),
                      reinterpret_cast<const float4 *>(scale), reinterpret_cast<const float4 *>(shift),
@@ -1936,7 +1989,9 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
   const int dx_planes = dx_planes_phase & 1, phase = (dx_planes_phase >> 1) & 3, defer = (dx_planes_phase >> 3) & 1;
   DSPN_REQUIRE(dx_planes_phase >= 0 && dx_planes_phase < 16 && phase <= 2 && (!defer || phase == 1),
                "bn_backward_from_sums: flag word = dx_planes | 2 (finalize only, | 8: parked for the next weight gradient) | 4 (apply only)");
-  DSPN_REQUIRE(x && dy && mean && rstd && dx && workspace && tile_sums && tiles > 0, "bn_backward_from_sums: null pointer");
+  DSPN_REQUIRE(x && dy && mean && rstd && workspace && tile_sums && tiles > 0, "bn_backward_from_sums: null pointer");
+  // dx == NULL (parameters only): the finalize alone, i.e. flag word 2 -- no apply half follows
+  DSPN_REQUIRE(dx || dx_planes_phase == 2, "bn_backward_from_sums: dx == NULL needs the finalize-only flag word 2");
   DSPN_REQUIRE(!dx_planes || (!dspn::kHalf && !accumulate && C % 32 == 0 && dx_absmax && dy_absmax && x_chan_minmax &&
                               static_cast<const void *>(dx) != static_cast<const void *>(dy) && static_cast<const void *>(dx) != static_cast<const void *>(x)),
                "bn_backward_from_sums: dx as piece planes needs float tensors, C %% 32 == 0, no accumulation, dx apart from x and dy, "
@@ -2415,6 +2470,20 @@ int dspn_sgd_momentum_f32(float *w, const float *grad, float *mom, long long n, 
                      reinterpret_cast<const float4 *>(grad), reinterpret_cast<float4 *>(mom), n / 4, lr,
                      momentum, wd, rescale);
   return dspn::check_launch("sgd_momentum");
+}
+#endif
+
+#ifndef DSPN_HALF
+int dspn_sgd_momentum_segments_f32(float *w, const float *grad, float *mom, const dspn_sgd_segment *segments, int nseg,
+                                   long long total4, float lr, float momentum, float wd, float rescale, void *stream) {
+  DSPN_REQUIRE(w && grad && mom && segments && nseg > 0 && nseg <= DSPN_SGD_MAX_SEGMENTS && total4 > 0,
+               "sgd_momentum_segments: need w, grad, mom, a segment table of 1 .. DSPN_SGD_MAX_SEGMENTS rows and total4 > 0");
+  const long long blocks = (total4 + (long long)kT * kSgdPer - 1) / ((long long)kT * kSgdPer);
+  DSPN_REQUIRE(blocks <= 0x7fffffffLL, "sgd_momentum_segments: total4 too large");
+  hipLaunchKernelGGL(sgd_segments_kernel, dim3((unsigned)blocks), dim3(kT), sizeof(long long) * (size_t)nseg, S_(stream),
+                     reinterpret_cast<float4 *>(w), reinterpret_cast<const float4 *>(grad), reinterpret_cast<float4 *>(mom),
+                     segments, nseg, total4, lr, momentum, wd, rescale);
+  return dspn::check_launch("sgd_momentum_segments");
 }
 #endif
 

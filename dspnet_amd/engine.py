@@ -18,6 +18,7 @@ arenas) so the optimizer is one kernel and data-parallel reduction works on a
 few large contiguous buckets.
 """
 import math
+import re
 
 import numpy as np
 import torch
@@ -157,6 +158,10 @@ class Tensor:
 class Param:
     def __init__(self, name, shape, init, wd_mult=1.0):
         self.name, self.shape, self.init, self.wd_mult = name, tuple(shape), init, wd_mult
+        # frozen (Graph.set_freeze: MXNet's fixed_param_names): no gradient is computed for it where that can be skipped,
+        # the optimizer never writes it or its momentum, the all-reduce never carries it.  lr_mult: the symbol's __lr_mult__
+        # (2.0 on the multibox head biases), honoured by MultiTaskSolver(optimizer_rules="module")
+        self.fixed, self.lr_mult = False, 1.0
         self.data = self.grad = None
         self.offset = 0
         # shape of the same parameter in the reference's checkpoint: (Cout, Cin, kh, kw) for a Convolution weight,
@@ -170,6 +175,25 @@ class Param:
 
 
 class Node:
+    """Every node's constructor takes the graph first.  The tensors it creates are its outputs (Graph._derive_requires_grad):
+    __init_subclass__ brackets the outermost constructor with the graph's tensor count."""
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        init = cls.__dict__.get("__init__")
+        if init is None:
+            return
+
+        def wrapped(self, g, *args, __init=init, **kwargs):
+            if "_made" in self.__dict__:           # (a subclass constructor calling its parent's)
+                return __init(self, g, *args, **kwargs)
+            start = len(g.all_tensors)
+            self._made = None
+            __init(self, g, *args, **kwargs)
+            self._made = (start, len(g.all_tensors))
+        wrapped.__wrapped__ = init
+        cls.__init__ = wrapped
+
     def forward(self):
         raise NotImplementedError
 
@@ -239,6 +263,32 @@ class Graph:
         self.guard = dict(enabled=_os.environ.get("DSPN_RANGE_GUARD", "1") != "0", have_stats=False, risk=frozenset(),
                           calls=0, calls_total=0, at_risk_slots=0)
         self.wmin_table = None     # descriptor table of the per-output-channel weight minima (one launch per step)
+        # frozen parameters (set_freeze, before the first node is built): names and / or a regex matched with re.match
+        self.fixed_names, self.freeze_re, self.freezing = frozenset(), None, False
+        # the derived operands of FROZEN weights (transposes, bf16 copies, piece planes, magnitudes, per-row minima) have tables
+        # of their own, run once and again only after set_params / load_params (frozen_stale); their magnitude slots sit at
+        # the end of the arena, behind _nscal_step, which forward() does not zero
+        self.wt_frozen = self.wp_frozen = self.am_frozen = self.wmin_frozen = None
+        self.frozen_stale = False
+        self._nscal_step = 0
+        self._add_mark = 0         # len(all_tensors) after the last add(): the tensors a node's constructor made follow it
+
+    def set_freeze(self, fixed_param_names=None, freeze_pattern=None):
+        """Freeze parameters of the nodes built from now on: every name in fixed_param_names and every name freeze_pattern
+        matches (re.match, as train_multitask.py applies --freeze).  Then a node's outputs need a gradient only if one of
+        its inputs does or it owns a parameter that is not frozen (MXNet's rule); without freezing nothing changes."""
+        assert not self.nodes, "set_freeze() before the graph is built"
+        self.fixed_names = frozenset(fixed_param_names or ())
+        self.freeze_re = re.compile(freeze_pattern) if freeze_pattern else None
+        self.freezing = bool(self.fixed_names) or self.freeze_re is not None
+
+    def is_fixed(self, name):
+        return name in self.fixed_names or (self.freeze_re is not None and self.freeze_re.match(name) is not None)
+
+    @property
+    def fixed_param_names(self):
+        """the frozen parameters this graph materialises, sorted"""
+        return sorted(p.name for p in self.param_order if p.fixed)
 
     # -- construction ---------------------------------------------------------
     def tensor(self, shape, name, requires_grad=True, data=None, virtual=False, dtype=None):
@@ -251,13 +301,34 @@ class Graph:
     def param(self, name, shape, init):
         assert name not in self.params, name
         p = Param(name, shape, init)
+        p.fixed = self.freezing and self.is_fixed(name)
         self.params[name] = p
         self.param_order.append(p)
         return p
 
     def add(self, node):
         self.nodes.append(node)
+        if self.freezing:
+            self._derive_requires_grad(node)
+        self._add_mark = len(self.all_tensors)
         return node
+
+    def _derive_requires_grad(self, node):
+        """MXNet's gradient rule for a node just built: its outputs (the tensors its constructor made) need a gradient only if
+        an input does or it owns a parameter that is not frozen.  Only ever switches a gradient off: a node nothing behind
+        asks a gradient of never runs its backward (Tensor._gw stays False), so a frozen prefix leaves backward altogether."""
+        lo, hi = getattr(node, "_made", None) or (self._add_mark, len(self.all_tensors))
+        made = {id(t) for t in self.all_tensors[lo:hi]}
+        ins, outs, trainable = [], [], False
+        for v in vars(node).values():
+            for t in (list(v.values()) if isinstance(v, dict) else v if isinstance(v, (list, tuple)) else [v]):
+                if isinstance(t, Tensor):
+                    (outs if id(t) in made else ins).append(t)
+                elif isinstance(t, Param) and not t.fixed:
+                    trainable = True
+        if not trainable and not any(t.requires_grad for t in ins):
+            for t in outs:
+                t.requires_grad = False
 
     def new_scalar(self, backward=False):
         """index of a fresh slot of the operand-magnitude arena ("f16x2" math).  backward=True: the magnitude of a gradient;
@@ -582,25 +653,42 @@ class Graph:
             # split math: a data gradient that contracts over whole 32-channel blocks reads piece planes, not the float
             # transpose (Conv.__init__ allocated them); only the other layers stay in the transpose table
             pairs = [n for n in self._wt_pairs_nodes if n.wtp is None or n.wh is not None]
-            if pairs:
-                self.wt_table = fn.weight_transpose_table([(n.w.data, n.wt, n.wh) for n in pairs], self.device)
-                self.half_operands = self.wt_table[3]
+            for frozen in (False, True):
+                rows = [(n.w.data, n.wt, n.wh) for n in pairs if n.w.fixed == frozen]
+                if rows:
+                    tab = fn.weight_transpose_table(rows, self.device)
+                    setattr(self, "wt_frozen" if frozen else "wt_table", tab)
+                    self.half_operands = tab[3]
         if self.device.type == "cuda":
+            wnodes = [n for n in self.nodes if getattr(n, "am_w", None) is not None and getattr(n, "w", None) is not None]
+            self._nscal_step = self._nscal
+            for n in wnodes:
+                if n.w.fixed:       # (a slot at the end: forward() zeroes the slots in front of _nscal_step only)
+                    n.am_w = self.new_scalar()
+                    if isinstance(n, Deconv4x4s2):
+                        n.am = (n.am[0], n.am_w, n.am[2])
             if self.math == "f16x2" and self._nscal:
                 self.scalars = torch.zeros(self._nscal * fn.ABSMAX_SLOTS, dtype=torch.float32, device=self.device)
                 self.scalars_min = torch.full((self._nscal,), float("inf"), dtype=torch.float32, device=self.device)
-                wnodes = [n for n in self.nodes if getattr(n, "am_w", None) is not None and getattr(n, "w", None) is not None]
-                pairs = [(n.w.data, self.scalar(n.am_w)) for n in wnodes]
                 self._am_table_slots = {n.am_w for n in wnodes}
-                if pairs:
-                    self.am_table = fn.absmax_table(pairs, self.device)
-                    if self.guard["enabled"]:
-                        self.wmin_table = fn.absmin_rows_table(
-                            [(n.w.data.view(n.w.shape[0], -1), self.scalars_min[n.am_w:n.am_w + 1]) for n in wnodes], self.device)
-            planes = [(n.w.data, n.wp, n.wtp) + ((self.scalar(n.am_w),) if self.math == "f16x2" else ())
-                      for n in self.nodes if isinstance(n, Conv) and (n.wp is not None or n.wtp is not None)]
-            if planes:
-                self.wp_table = fn.weight_planes_table(planes, self.device)
+                for frozen in (False, True):
+                    sel = [n for n in wnodes if n.w.fixed == frozen]
+                    if not sel:
+                        continue
+                    am = fn.absmax_table([(n.w.data, self.scalar(n.am_w)) for n in sel], self.device)
+                    wmin = (fn.absmin_rows_table([(n.w.data.view(n.w.shape[0], -1), self.scalars_min[n.am_w:n.am_w + 1])
+                                                  for n in sel], self.device) if self.guard["enabled"] else None)
+                    if frozen:
+                        self.am_frozen, self.wmin_frozen = am, wmin
+                    else:
+                        self.am_table, self.wmin_table = am, wmin
+            convs = [n for n in self.nodes if isinstance(n, Conv) and (n.wp is not None or n.wtp is not None)]
+            for frozen in (False, True):
+                planes = [(n.w.data, n.wp, n.wtp) + ((self.scalar(n.am_w),) if self.math == "f16x2" else ())
+                          for n in convs if n.w.fixed == frozen]
+                if planes:
+                    setattr(self, "wp_frozen" if frozen else "wp_table", fn.weight_planes_table(planes, self.device))
+            self.frozen_stale = any(t is not None for t in (self.wt_frozen, self.wp_frozen, self.am_frozen))
         if self.device.type == "cuda":
             # every Conv keeps the split-K partial sums of its weight gradient in a buffer of its own, so that the
             # slab sums of many layers run as one launch (flush_slabs) instead of one small kernel per layer
@@ -650,6 +738,7 @@ class Graph:
 
     def load_params(self, values):
         """values: name -> numpy array in the param's (device-layout) shape"""
+        self.frozen_stale = self.frozen_stale or any(self.params[k].fixed for k in values)
         for k, v in values.items():
             self.params[k].data.copy_(torch.from_numpy(np.ascontiguousarray(v, np.float32)).view(self.params[k].shape))
 
@@ -754,8 +843,8 @@ class Graph:
             self.wt_batched = True
         if self.scalars is not None:   # "f16x2" math: every operand magnitude of the step starts from zero; the weights' now
             self._update_guard(blocking=self.guard.pop("decide_now", False))
-            self.scalars.zero_()
-            self.scalars_min.fill_(float("inf"))
+            self.scalars[:self._nscal_step * fn.ABSMAX_SLOTS].zero_()     # (frozen weights' slots behind: refresh_frozen)
+            self.scalars_min[:self._nscal_step].fill_(float("inf"))
             if self.wmin_table is not None and self.guard.get("wmin_now", True):
                 fn.absmin_rows_batch(*self.wmin_table)
             self._am_done = set()
@@ -763,6 +852,7 @@ class Graph:
             if self.am_table is not None:
                 fn.absmax_batch(*self.am_table)
                 self._am_done |= self._am_table_slots
+        self.refresh_frozen()
         if self.wp_table is not None:  # split math: the piece planes of every weight (forward and data-gradient operands;
             fn.weight_planes_batch(*self.wp_table)     # "f16x2": cut relative to the magnitudes just taken)
         for f in self.pre_forward:
@@ -792,6 +882,24 @@ class Graph:
                     done.record(side)
                     self.side_pending = True
         self.guard["have_stats"] = True       # (forward-only use -- the Detector -- is guarded by the spans of inputs and weights)
+
+    def refresh_frozen(self):
+        """the derived operands of the frozen weights -- bf16 copies and transposes, magnitudes, per-row minima, piece planes
+        (cut by those magnitudes) -- formed when they are stale: after finalize() and after set_params / load_params"""
+        if not self.frozen_stale:
+            return
+        self.frozen_stale = False
+        if self.wt_frozen is not None:
+            fn.weight_transpose_batch(*self.wt_frozen)
+        if self.scalars is not None:
+            self.scalars[self._nscal_step * fn.ABSMAX_SLOTS:].zero_()
+            self.scalars_min[self._nscal_step:].fill_(float("inf"))
+            if self.wmin_frozen is not None:
+                fn.absmin_rows_batch(*self.wmin_frozen)
+            if self.am_frozen is not None:
+                fn.absmax_batch(*self.am_frozen)
+        if self.wp_frozen is not None:
+            fn.weight_planes_batch(*self.wp_frozen)
 
     def set_side_segment(self, first, last):
         """nodes [first, last] run their forward on the branch stream.  On a CPU graph only the plan is kept (side_plan):
@@ -971,6 +1079,7 @@ class Graph:
                     dev[:] = p.data.detach().cpu().numpy()
                 dev[:v.shape[0]] = v
             p.data.copy_(torch.from_numpy(dev))
+            self.frozen_stale = self.frozen_stale or p.fixed
 
     def get_aux(self):
         """-> the moving statistics in the reference's aux-state names and shapes: '<bn>_moving_mean' / '<bn>_moving_var'
@@ -1214,7 +1323,8 @@ class BatchNorm(Node):
         instead -- two events per node -- the step LOST 1.5 %: profiles/r06_finalize_beside_ab.txt.)  -> True if it did."""
         g = self._g
         if (not FINALIZE_BESIDE or g.device.type != "cuda" or not self.bwd_sums_ready or self.pool_grad is not None
-                or not self.out._gw or self._pending is not None):
+                or not self.out._gw or self._pending is not None or not self.x.requires_grad):
+            # (parameters only -- x needs no gradient -- is the finalize alone: no apply half to park it for)
             return False
         self.backward(beside=True)
         return self._pending is not None
@@ -1236,6 +1346,9 @@ class BatchNorm(Node):
         if not self.out._gw:
             return
         am = None
+        # frozen gamma / beta: not computed (NULL to the kernels); dgamma stays None where there is no gamma (fix_gamma)
+        dgam = None if self.gamma is None else (fn.NO_OUTPUT if self.gamma.fixed else self.gamma.grad)
+        dbet = fn.NO_OUTPUT if self.beta.fixed else self.beta.grad
         if self.x.requires_grad:
             dx, acc = self.x.grad_target()
             # "f16x2" math: dx is the output gradient of the convolution that produced x; when this call completes it (a
@@ -1246,15 +1359,15 @@ class BatchNorm(Node):
                     and self.completes_x_grad):
                 am = g.scalar(prod.am_dy)
                 g._am_done.add(prod.am_dy)
-        else:  # parameters still need their gradients; dx goes to scratch
-            dx, acc = (self.out.grad if self.pool_grad is None else self.out.own_grad()), False
+        else:  # the parameters alone: reductions and finalize, no dx (the kernels take dx == NULL)
+            dx, acc = fn.NO_OUTPUT, False
         if self.pool_grad is not None:
             argmax, dyp, k, s, p = self.pool_grad
             self.pool_grad = None
             if not acc:
                 fn.bn_backward_maxpool(self.x.data, self.scale, self.shift, dyp, argmax, k, s, p, self.mean, self.rstd,
                                        None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx,
-                                       dgamma=None if self.gamma is None else self.gamma.grad, dbeta=self.beta.grad, dx_absmax=am)
+                                       dgamma=dgam, dbeta=dbet, dx_absmax=am)
                 return
             # (a second writer of x's gradient: materialise the pooling backward after all)
             fn.maxpool_backward_argmax(argmax, dyp, self.out.shape, k, s, p, dx=self.out.own_grad())
@@ -1265,8 +1378,7 @@ class BatchNorm(Node):
             self.bwd_sums_ready = False
             self._from_sums(beside, (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
                                      None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
-                            dict(relu=self.relu, dx=dx, dgamma=None if self.gamma is None else self.gamma.grad,
-                                 dbeta=self.beta.grad, accumulate=False, dx_absmax=am,
+                            dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=False, dx_absmax=am,
                                  dy_absmax=self._g.scalar(self.am_dyin), x_chan_minmax=self.x_ext, dx_planes=True,
                                  dx_absmin=g.scalars_min[prod.am_dy:prod.am_dy + 1] if g.guard["enabled"] else None))
             self.x.grad_planes = True
@@ -1275,13 +1387,11 @@ class BatchNorm(Node):
             self.bwd_sums_ready = False
             self._from_sums(beside, (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
                                      None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
-                            dict(relu=self.relu, dx=dx, dgamma=None if self.gamma is None else self.gamma.grad,
-                                 dbeta=self.beta.grad, accumulate=acc, dx_absmax=am))
+                            dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=acc, dx_absmax=am))
             return
         assert not beside, "finalize_beside() without the data gradient's sums"
         fn.bn_backward(self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
-                       None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx,
-                       dgamma=None if self.gamma is None else self.gamma.grad, dbeta=self.beta.grad,
+                       None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet,
                        accumulate=acc, dx_absmax=am)
 
 
@@ -1398,6 +1508,8 @@ class Conv(Node):
         self.flops_bwd = self.flops_fwd * (2 if x.requires_grad else 1)
 
     def alloc_slabs(self):
+        if self.w.fixed:
+            return                 # (a frozen weight has no weight gradient)
         cout, kh, kw, cin = self.w.shape
         wshape = (cout * kh * kw, 1, 1, cin) if self.tap_expand else self.w.shape
         xs = self.x.shape
@@ -1533,7 +1645,7 @@ class Conv(Node):
             fn.relu_backward(self.out.data, dy, dx=dy)
         if self.residual is not None and self.residual.requires_grad:
             self.residual.give_grad(dy)
-        if self.b is not None and not self.relu:
+        if self.b is not None and not self.relu and not self.b.fixed:
             fn.colsum(dy, self.cout, out=self.b.grad)
         # "f16x2" math: the gradient's magnitude once (after the in-place ReLU mask above), for both of its readers
         xa, dya, wa = self._magnitudes("x"), self._magnitudes("dy"), self._magnitudes("w")
@@ -1543,14 +1655,22 @@ class Conv(Node):
         # round 6: when this data gradient gathers the backward sums of the BatchNorm in front (bn_bwd_node), it goes FIRST and
         # that node's finalize rides in front of the weight gradient's grid (BatchNorm.finalize_beside)
         bn = getattr(self, "bn_bwd_node", None) if self.x.requires_grad else None
+        isg = self.input_sum_grad if (self.input_sum_grad is not None and not self.input_sum_grad.fixed) else None
+        if self.w.fixed:
+            # frozen weight: no weight gradient, so nothing for a BatchNorm finalize to ride in (it runs on its own) and no
+            # second stream; the data gradient (and the bn_data beta's sum) still run
+            if isg is not None:
+                fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=isg.grad)
+            if self.x.requires_grad:
+                self._data_gradient(dy, planes, dya, wa)
+            return
         early = (bn is not None and FINALIZE_BESIDE and not self.guard_fb and self._g.device.type == "cuda"
                  and bn.pool_grad is None)
         if (WGRAD_SIDE and self._g.wgrad_side_allowed and self._g.device.type == "cuda" and (bn is not None or self._g.batchnorm_chain()) and self._wgrad_worth_a_stream()
                 and self._g.wgrad_beside(self, dy, planes, xa, dya)):
             early = False          # (the weight gradient went to its own stream: nothing to ride in, and the finalize's gap is filled)
-            if self.input_sum_grad is not None:
-                fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil,
-                                         out=self.input_sum_grad.grad)
+            if isg is not None:
+                fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=isg.grad)
             if self.x.requires_grad:
                 self._data_gradient(dy, planes, dya, wa)
             return
@@ -1558,9 +1678,8 @@ class Conv(Node):
             self._data_gradient(dy, planes, dya, wa)
             bn.finalize_beside()
         self._weight_gradient(dy, planes, xa, dya)
-        if self.input_sum_grad is not None:
-            fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil,
-                                     out=self.input_sum_grad.grad)
+        if isg is not None:
+            fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=isg.grad)
         if self.x.requires_grad and not early:
             self._data_gradient(dy, planes, dya, wa)
 
@@ -1614,10 +1733,11 @@ class Conv(Node):
         self.slabs_fresh = self.slabs is not None
 
     def _data_gradient(self, dy, planes, dya, wa):
-        if self.wtp is not None and self._g.wp_table is None:
+        g = self._g
+        if self.wtp is not None and (g.wp_frozen if self.w.fixed else g.wp_table) is None:
             fn.weight_planes(self.w.data, transposed=True, cols=self.wtp.shape[2] * 32, out=self.wtp, math=self.math,
                              w_absmax=wa)
-        elif self.wtp is None and not self._g.wt_batched:
+        elif self.wtp is None and not (g.wt_frozen is not None if self.w.fixed else g.wt_batched):
             fn.weight_transpose(self.w.data, out=self.wt, copy=self.wh)
         dx, acc = self.x.grad_target()
         bn = getattr(self, "bn_bwd_node", None)   # set by Graph.finalize on the LAST writer of a deferred BN's gradient
@@ -1749,16 +1869,18 @@ class BilinearConcatConv(Node):
                                                        dx_absmax=dza)
             xa, wa = self._g.magnitude(self.am[c][0], t.data, src=t), self._g.scalar(self.am_w)
             dza = self._g.magnitude(self.am[c][2], dz)
-            fn.conv2d_wgrad(t.data, dz, (self.T, 1, 1, t.shape[3]), 1, 0, 1, out=self.dwc[c], math=self.math, x_absmax=xa,
-                            dy_absmax=dza)
-            fn.copy_block(self.dwc[c], self.w.grad, 1, self.T, t.shape[3], 0, t.shape[3], 0, 0, Cin, self.offsets[c])
+            if not self.w.fixed:
+                fn.conv2d_wgrad(t.data, dz, (self.T, 1, 1, t.shape[3]), 1, 0, 1, out=self.dwc[c], math=self.math,
+                                x_absmax=xa, dy_absmax=dza)
+                fn.copy_block(self.dwc[c], self.w.grad, 1, self.T, t.shape[3], 0, t.shape[3], 0, 0, Cin, self.offsets[c])
             if t.requires_grad:
                 if self.wch[c] is None:
                     fn.weight_transpose(self.wc[c], out=self.wct[c])
                 dx, acc = t.grad_target()
                 fn.conv2d_dgrad(dz, self.wct[c], t.shape, 1, 0, 1, out=dx, accumulate=acc, math=self.math, dy_absmax=dza,
                                 w_absmax=wa)
-        fn.affine_sampler_theta_reduce(self.tpart, self.theta.grad)
+        if not self.theta.fixed:
+            fn.affine_sampler_theta_reduce(self.tpart, self.theta.grad)
 
 
 class Deconv4x4s2(Node):
@@ -1794,7 +1916,9 @@ class Deconv4x4s2(Node):
         dy = self.out.grad
         g = self._g
         xa, wa, dya = g.magnitude(self.am[0], self.x.data, src=self.x), g.magnitude(self.am[1], self.w.data), g.magnitude(self.am[2], dy)
-        fn.conv2d_wgrad(dy, self.x.data, self.w.shape, 2, 1, 1, out=self.w.grad, math=self.math, x_absmax=dya, dy_absmax=xa)
+        if not self.w.fixed:
+            fn.conv2d_wgrad(dy, self.x.data, self.w.shape, 2, 1, 1, out=self.w.grad, math=self.math, x_absmax=dya,
+                            dy_absmax=xa)
         if self.x.requires_grad:
             dx, acc = self.x.grad_target()
             fn.conv2d_forward(dy, self.w.data if self.wh is None else self.wh, None, 2, 1, 1, out=dx, accumulate=acc,
@@ -1981,7 +2105,8 @@ class BilinearConcat(Node):
     def backward(self):
         if not self.out._gw:
             return
-        fn.affine_sampler_backward_theta(self.sources, self.theta.data, self.out.grad, self.theta.grad)
+        if not self.theta.fixed:
+            fn.affine_sampler_backward_theta(self.sources, self.theta.data, self.out.grad, self.theta.grad)
         for t, off in zip(self.inputs, self.offsets):
             if not t.requires_grad:
                 continue

@@ -112,6 +112,7 @@ _lib.register({
     "dspn_cross_entropy_sum_f32": (_i, [_vp, _vp, _ll, _i, _i, _f, _f, _vp, _vp]),
     "dspn_sum_f32": (_i, [_vp, _ll, _vp, _vp]),
     "dspn_sgd_momentum_f32": (_i, [_vp, _vp, _vp, _ll, _f, _f, _f, _f, _vp]),
+    "dspn_sgd_momentum_segments_f32": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _f, _f, _f, _f, _vp]),
 })
 
 
@@ -739,17 +740,32 @@ def absmax_affine_bound(scale, shift, x_absmax, out):
     return out
 
 
+# dx / dgamma / dbeta = NO_OUTPUT: the BatchNorm backward passes NULL for it (dx: the parameter gradients alone, no apply pass;
+# dgamma / dbeta: a frozen parameter); None keeps meaning "allocate one"
+NO_OUTPUT = type("NoOutput", (), {"__repr__": lambda self: "NO_OUTPUT"})()
+
+
+def _bn_outputs(x, gamma, dx, dgamma, dbeta):
+    C = x.shape[-1]
+    dx = None if dx is NO_OUTPUT else (torch.empty_like(x) if dx is None else dx)
+    dbeta = None if dbeta is NO_OUTPUT else (empty(C, device=x.device) if dbeta is None else dbeta)
+    if dgamma is NO_OUTPUT:
+        dgamma = None
+    elif gamma is not None and dgamma is None:
+        dgamma = empty(C, device=x.device)
+    assert dx is None or dx.dtype == x.dtype
+    return dx, dgamma, dbeta
+
+
 def bn_backward(x, scale, shift, dy, mean, rstd, gamma, relu=False, dx=None, dgamma=None, dbeta=None,
                 accumulate=False, dx_absmax=None):
-    """dx_absmax: 64-float magnitude block that receives the partial maxima of |dx| as stored (see absmax)"""
+    """dx_absmax: 64-float magnitude block that receives the partial maxima of |dx| as stored (see absmax).
+    dx / dgamma / dbeta = NO_OUTPUT: not computed (dx: reductions and finalize only, dgamma / dbeta bit-identical)"""
     C = x.shape[-1]
     rows = _rows(x)
-    dx = torch.empty_like(x) if dx is None else dx
-    dbeta = empty(C, device=x.device) if dbeta is None else dbeta
-    if gamma is not None and dgamma is None:
-        dgamma = empty(C, device=x.device)
+    dx, dgamma, dbeta = _bn_outputs(x, gamma, dx, dgamma, dbeta)
     ws = workspace(L().dspn_bn_workspace_bytes(rows, C), x.device, "bn")
-    assert dy.dtype == x.dtype == dx.dtype
+    assert dy.dtype == x.dtype
     check(_f("dspn_bn_backward", x)(ptr(x), ptr(scale), ptr(shift), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
                                    ptr(dgamma), ptr(dbeta), rows, C, int(relu), int(accumulate), ptr(dx_absmax), ptr(ws),
                                    ws.numel(), stream()), "bn_backward")
@@ -762,10 +778,7 @@ def bn_backward_maxpool(x, scale, shift, dy_pool, argmax, k, stride, pad, mean, 
     BatchNorm(+ReLU) -> max pooling pair of the resnet stem without the dense gradient tensor in between (float32)"""
     N, H, W, C = x.shape
     assert x.dtype == dy_pool.dtype == torch.float32 and argmax.dtype == torch.uint8 and argmax.shape == dy_pool.shape
-    dx = torch.empty_like(x) if dx is None else dx
-    dbeta = empty(C, device=x.device) if dbeta is None else dbeta
-    if gamma is not None and dgamma is None:
-        dgamma = empty(C, device=x.device)
+    dx, dgamma, dbeta = _bn_outputs(x, gamma, dx, dgamma, dbeta)
     ws = workspace(L().dspn_bn_workspace_bytes(N * H * W, C), x.device, "bn")
     check(L().dspn_bn_backward_maxpool_f32(ptr(x), ptr(scale), ptr(shift), ptr(dy_pool), ptr(argmax), N, H, W, C, k, stride, pad,
                                            dy_pool.shape[1], dy_pool.shape[2], ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
@@ -782,7 +795,7 @@ def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, r
     BOUND of |dx| that is formed from dy_absmax (the magnitude block of dy, conv2d_dgrad's bn_dy_absmax) and x_chan_minmax
     (2 x C per-channel extremes of x, bn_stats_from_tiles' out_chan_minmax) and left in dx_absmax.
     phase (round 6): 1 = the finalize alone (coefficients into `workspace`), 2 = the apply pass alone from what a phase-1 call
-    with the same arguments and workspace left there; 0 = both.  park (with phase 1): the finalize is not launched but parked for
+    with the same arguments and workspace left there; 0 = both (dx=NO_OUTPUT: the finalize alone).  park (with phase 1): the finalize is not launched but parked for
     the NEXT weight-gradient launch on this stream, in front of whose grid it rides (csrc/bn_final_job.h); the phase-2 call runs
     it on its own if no weight gradient came by.
     workspace: a bn_from_sums_workspace(tiles, C) buffer of the caller's.  Phases 1 and 2 hand the coefficients over in it, so a
@@ -791,13 +804,13 @@ def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, r
     assert phase in (0, 1, 2) and (not park or phase == 1)
     C = x.shape[-1]
     rows = _rows(x)
-    dx = torch.empty_like(x) if dx is None else dx
-    dbeta = empty(C, device=x.device) if dbeta is None else dbeta
-    if gamma is not None and dgamma is None:
-        dgamma = empty(C, device=x.device)
+    dx, dgamma, dbeta = _bn_outputs(x, gamma, dx, dgamma, dbeta)
+    if dx is None:                # parameters only: the finalize alone (flag word 2), nothing parked, no apply half
+        assert phase == 0 and not park and not dx_planes, "dx=NO_OUTPUT is a whole call"
+        phase = 1
     if workspace is None:
         workspace = _scratch(12 * C + L().dspn_bn_tiles_workspace_bytes(tiles, C), x.device, "bn_from_sums")
-    assert dy.dtype == x.dtype == dx.dtype
+    assert dy.dtype == x.dtype
     check(_f("dspn_bn_backward_from_sums", x)(ptr(x), ptr(scale), ptr(shift), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma),
                                              ptr(sums), tiles, ptr(dx), ptr(dgamma), ptr(dbeta), rows, C, int(relu),
                                              int(accumulate), ptr(dx_absmax), ptr(dx_absmin), ptr(dy_absmax), ptr(x_chan_minmax),
@@ -1180,3 +1193,34 @@ def sum_all(a, out=None):
 def sgd_momentum(w, grad, mom, lr, momentum, wd, rescale):
     check(L().dspn_sgd_momentum_f32(ptr(w), ptr(grad), ptr(mom), w.numel(), lr, momentum, wd, rescale,
                                     stream()), "sgd_momentum")
+
+
+# include/dspn_nn.h dspn_sgd_segment (24 bytes) and DSPN_SGD_MAX_SEGMENTS
+SGD_SEGMENT_FIELDS = [("offset", "<i8"), ("length", "<i8"), ("lr_mult", "<f4"), ("wd_mult", "<f4")]
+SGD_MAX_SEGMENTS = 8192
+
+
+def sgd_segment_table(rows, numel, device):
+    """rows: [(offset, length, lr_mult, wd_mult)] in floats, sorted, disjoint, multiples of 4, inside an arena of `numel`
+    floats -> (device table, nseg, total4) for sgd_momentum_segments.  The rows are checked here: the kernel trusts them."""
+    import numpy as np
+    if not 0 < len(rows) <= SGD_MAX_SEGMENTS:
+        raise ValueError("sgd_segment_table: need 1 .. %d rows, got %d" % (SGD_MAX_SEGMENTS, len(rows)))
+    tab = np.zeros(len(rows), dtype=SGD_SEGMENT_FIELDS)
+    end = 0
+    for i, (off, length, lm, wm) in enumerate(rows):
+        off, length = int(off), int(length)
+        if off % 4 or length % 4 or length <= 0 or off < end or off + length > numel:
+            raise ValueError("sgd_segment_table: row %d (%d, %d) is not a sorted, disjoint, 4-aligned range of %d floats"
+                             % (i, off, length, numel))
+        tab[i] = (off, length, lm, wm)
+        end = off + length
+    dev = torch.from_numpy(tab.view(np.uint8).copy()).to(device)
+    return dev, len(rows), int(tab["length"].sum()) // 4
+
+
+def sgd_momentum_segments(w, grad, mom, table, lr, momentum, wd, rescale):
+    """SGD-momentum over the rows of a sgd_segment_table (table = its (device table, nseg, total4)); one launch"""
+    dev, nseg, total4 = table
+    check(L().dspn_sgd_momentum_segments_f32(ptr(w), ptr(grad), ptr(mom), ptr(dev), nseg, total4, lr, momentum, wd,
+                                             rescale, stream()), "sgd_momentum_segments")

@@ -105,6 +105,9 @@ def multitask_layer(g, from_layers, num_classes, sizes, ratios, normalization=-1
                            no_bias=False, init="maxdim", tap_expand=big)).out
         cls = g.add(E.Conv(g, from_layer, "{}_cls_pred_conv".format(from_name), num_anchors * num_classes, 3,
                            1, 1, no_bias=False, init="maxdim", tap_expand=big)).out
+        # the reference declares both biases with __lr_mult__ 2.0 (symbol/common.py:394-406)
+        for t in (loc, cls):
+            t.producer.b.lr_mult = 2.0
         loc_maps.append(loc); loc_w.append(num_anchors * 5)
         cls_maps.append(cls); cls_w.append(num_anchors * num_classes)
         step = (steps[k], steps[k]) if steps else (-1.0, -1.0)

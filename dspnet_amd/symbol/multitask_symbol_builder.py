@@ -252,6 +252,11 @@ class MultiTaskNet:
         self.g, self.data, self.label_det, self.label_seg = g, data, label_det, label_seg
         self.__dict__.update(nodes)
 
+    @property
+    def fixed_param_names(self):
+        """the frozen parameters the graph materialises, sorted (fixed_param_names / freeze_pattern of the builders)"""
+        return self.g.fixed_param_names
+
     def outputs(self):
         """training graph: [cls_prob, loc_loss, cls_label, det_out, seg_out] (multitask_symbol_builder.py:592);
         test graph: [det, seg_out] (:726); segmentation-only graphs: [seg_out] (:322, :439); detection-only
@@ -268,11 +273,19 @@ class MultiTaskNet:
 def get_multi_symbol_train(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                            normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                            nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), num_labels=200, device=None,
-                           num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False, **kwargs):
-    """symbol/multitask_symbol_builder.py:442-593"""
+                           num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False,
+                           fixed_param_names=None, freeze_pattern=None,
+                           **kwargs):
+    """symbol/multitask_symbol_builder.py:442-593.
+    fixed_param_names / freeze_pattern (every training builder): the parameters to freeze, as mx.mod.Module's
+    fixed_param_names -- the names given plus every argument name freeze_pattern matches (re.match, train_multitask.py:
+    196-200).  A frozen parameter keeps its value and momentum, and backward skips what only it needed (engine.Graph.set_freeze).
+    A name the graph does not know raises ValueError; the `_gamma` of a fix_gamma BatchNorm and the graph inputs are known
+    arguments without effect."""
     return _build(True, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios, normalizations,
                   steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape, num_labels, device,
-                  num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats)
+                  num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats,
+                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern)
 
 
 def get_multi_symbol(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
@@ -295,12 +308,15 @@ def get_multi_symbol(network, num_classes, from_layers, num_filters, strides, pa
 def get_det_symbol_train(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                          normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                          nms_topk=400, batch_size=1, data_shape=(3, 300, 300), num_labels=200, device=None,
-                         num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False, **kwargs):
+                         num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False,
+                         fixed_param_names=None, freeze_pattern=None,
+                         **kwargs):
     """Detection + depth only, symbol/multitask_symbol_builder.py:20-121: outputs [cls_prob, loc_loss, cls_label,
     det_out]; the same graph without the segmentation decoder."""
     return _build(True, False, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  num_labels, device, num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats)
+                  num_labels, device, num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats,
+                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern)
 
 
 def get_det_symbol(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
@@ -316,13 +332,16 @@ def get_det_symbol(network, num_classes, from_layers, num_filters, strides, pads
 def get_seg_symbol_train(network, num_classes, from_layers, num_filters=None, strides=None, pads=None, sizes=None,
                          ratios=None, normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5,
                          force_suppress=False, nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), device=None,
-                         num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False, **kwargs):
+                         num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False,
+                         fixed_param_names=None, freeze_pattern=None,
+                         **kwargs):
     """Segmentation only, symbol/multitask_symbol_builder.py:211-323: backbone -> pyramid decoder ->
     SoftmaxOutput(grad_scale=4, ignore 255); output [seg_out].  The SSD arguments are accepted and unused, as
     in the reference.  Gradient reaches the backbone through conv_feat only (res3 / res4 are BlockGrad'ed)."""
     return _build(True, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
-                  0, device, num_layers, seed, with_det=False, bn_mom=bn_mom, use_global_stats=use_global_stats)
+                  0, device, num_layers, seed, with_det=False, bn_mom=bn_mom, use_global_stats=use_global_stats,
+                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern)
 
 
 def get_seg_symbol(network, num_classes, from_layers, num_filters=None, strides=None, pads=None, sizes=None,
@@ -367,9 +386,24 @@ def _detection_branch(g, train, internals, label, num_classes, from_layers, num_
     return conv_feat, target, cls_out, loc_loss, det, anchor_boxes, loc_preds, cls_flat
 
 
+def known_argument_names(g):
+    """the reference symbol's list_arguments() for a graph built here: its parameters, the `_gamma` of every fix_gamma
+    BatchNorm (MXNet lists it, this build does not materialise it) and the graph inputs"""
+    names = set(g.params)
+    names.update(name + "_gamma" for name, _, fix_gamma in g.bn_names if fix_gamma)
+    names.update(k for k in ("data", "label_det", "seg_out_label") if k in g.tensors)
+    return names
+
+
+def _check_fixed_names(g, fixed_param_names):
+    unknown = sorted(set(fixed_param_names) - known_argument_names(g))
+    if unknown:
+        raise ValueError("fixed_param_names: the graph has no argument " + ", ".join(unknown))
+
+
 def _build(train, with_seg, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios, normalizations,
            steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape, num_labels, device,
-           num_layers, seed, with_det=True, bn_mom=0.9, use_global_stats=False):
+           num_layers, seed, with_det=True, bn_mom=0.9, use_global_stats=False, fixed_param_names=None, freeze_pattern=None):
     assert network in ("resnet", "vgg16_reduced", "inceptionv3"), "backbones: resnet, vgg16_reduced, inceptionv3"
     if train and use_global_stats:
         raise ValueError("use_global_stats=True is for the test graphs (get_multi_symbol / get_det_symbol / get_seg_symbol): "
@@ -380,6 +414,10 @@ def _build(train, with_seg, network, num_classes, from_layers, num_filters, stri
     g = E.Graph(device)
     # every BatchNorm built below: moving statistics with momentum bn_mom; use_global_stats normalises with them (inference)
     g.bn_momentum, g.bn_global = float(bn_mom), bool(use_global_stats)
+    if isinstance(fixed_param_names, str):
+        fixed_param_names = [fixed_param_names]
+    fixed_param_names = list(fixed_param_names or ())
+    g.set_freeze(fixed_param_names, freeze_pattern)
     C, H, W = data_shape
     data = g.tensor((batch_size, C, H, W), "data", requires_grad=False, dtype=torch.float32)
     label = (g.tensor((batch_size, num_labels, 6), "label_det", requires_grad=False, dtype=torch.float32)
@@ -409,6 +447,7 @@ def _build(train, with_seg, network, num_classes, from_layers, num_filters, stri
         target = cls_out = loc_loss = det = anchor_boxes = loc_preds = cls_flat = None
 
     if not with_seg:
+        _check_fixed_names(g, fixed_param_names)
         g.finalize(seed)
         return MultiTaskNet(g, data, label, None,
                             dict(target=target, cls_out=cls_out, loc_loss=loc_loss, det=det, seg_out=None,
@@ -477,6 +516,7 @@ def _build(train, with_seg, network, num_classes, from_layers, num_filters, stri
         # test graph: the detection branch up to and including MultiBoxDetection beside the segmentation decoder; its only
         # reader is the caller, through det.join()
         g.set_side_segment(det_first, g.nodes.index(det))
+    _check_fixed_names(g, fixed_param_names)
     g.finalize(seed)
     return MultiTaskNet(g, data, label, seg_label,
                         dict(target=target, cls_out=cls_out, loc_loss=loc_loss, det=det, seg_out=seg_out,

@@ -21,13 +21,16 @@ its own to a checkpoint.
 from .. import functional as fn
 
 
-def plan_buckets(params, owner_index, total, bucket_elems):
+def plan_buckets(params, owner_index, total, bucket_elems, frozen=None):
     """Cut the flat gradient arena into contiguous buckets.
 
     params: [(name, offset, padded_size)] in arena order; owner_index[name] = index of the graph node
     that produces the gradient.  Returns [(lo, hi, first_node)] sorted by the order in which backward
     (which runs nodes from last to first) completes them: a bucket is complete once the node with the
-    smallest index among its owners has run."""
+    smallest index among its owners has run.
+    frozen: names of frozen parameters -- no bucket covers them (a bucket ends where one starts)."""
+    if frozen:
+        return _plan_buckets_frozen(params, owner_index, bucket_elems, set(frozen))
     buckets, lo, first = [], 0, None
     for name, offset, size in params:
         idx = owner_index[name]
@@ -40,6 +43,55 @@ def plan_buckets(params, owner_index, total, bucket_elems):
         buckets.append((lo, total, first if first is not None else 0))
     buckets.sort(key=lambda b: -b[2])
     return buckets
+
+
+def _plan_buckets_frozen(params, owner_index, bucket_elems, frozen):
+    buckets, lo, first, end = [], None, None, None
+    for name, offset, size in params:
+        if name in frozen:
+            if lo is not None:
+                buckets.append((lo, offset, first))
+                lo, first = None, None
+            continue
+        if lo is None:
+            lo = offset
+        idx = owner_index[name]
+        first = idx if first is None else min(first, idx)
+        end = offset + size
+        if end - lo >= bucket_elems:
+            buckets.append((lo, end, first))
+            lo, first = None, None
+    if lo is not None:
+        buckets.append((lo, end, first))
+    buckets.sort(key=lambda b: -b[2])
+    return buckets
+
+
+OPTIMIZER_RULES = ("multi_solver", "module")
+
+
+def rule_multipliers(name, rules, lr_mult=1.0, wd_mult=1.0):
+    """(lr multiplier, wd multiplier) of one parameter.  "multi_solver" (multi_solver.py:221 builds the optimizer without
+    the symbol): (1, 1) for everything.  "module" (an optimizer mx.mod.Module builds with the symbol, MXNet 1.x
+    Optimizer.set_lr_mult / set_wd_mult): the symbol's lr_mult; weight decay only on names ending in _weight or _gamma."""
+    if rules == "multi_solver":
+        return 1.0, 1.0
+    if rules != "module":
+        raise ValueError("optimizer_rules must be one of %s, got %r" % (OPTIMIZER_RULES, rules))
+    return float(lr_mult), (float(wd_mult) if name.endswith(("_weight", "_gamma")) else 0.0)
+
+
+def sgd_segments(params):
+    """params: [(offset, padded_size, lr_mult, wd_mult)] of the TRAINABLE parameters in arena order -> the rows of the
+    segmented update: [(offset, length, lr_mult, wd_mult)], neighbours with equal multipliers merged into one row"""
+    rows = []
+    for offset, size, lm, wm in params:
+        assert offset % 4 == 0 and size % 4 == 0, "arena ranges are float4-aligned"
+        if rows and rows[-1][0] + rows[-1][1] == offset and rows[-1][2:] == (lm, wm):
+            rows[-1] = (rows[-1][0], rows[-1][1] + size, lm, wm)
+        else:
+            rows.append((offset, size, lm, wm))
+    return rows
 
 
 def side_buckets(buckets, params, owner_index, side_nodes):
@@ -130,12 +182,19 @@ class GradBucketReducer:
 class MultiTaskSolver:
     def __init__(self, net, learning_rate=0.0005, momentum=0.9, wd=0.0005, process_group=None,
                  world_size=1, bucket_mb=16.0, force_reducer=False, high_priority=True, track_bn_stats=True,
-                 aux_params=None):
+                 aux_params=None, optimizer_rules="multi_solver", rescale_grad=None):
         """track_bn_stats: every step advances the BatchNorm moving statistics (False: the step of earlier builds, the
         statistics stay as they are).  aux_params ('<bn>_moving_mean' / '<bn>_moving_var', e.g. load_checkpoint's third
         item): loaded into the graph, so that resuming and init_from_resnet keep the pretrained statistics; BatchNorms
         without a value keep 0 / 1.  (multi_solver.py:212 zeroes the aux states instead: the reference never reads them
-        in training, but a checkpoint written here then carries statistics that match its weights.)"""
+        in training, but a checkpoint written here then carries statistics that match its weights.)
+        optimizer_rules: "multi_solver" (default, multi_solver.py:221: wd on every parameter, no lr_mult, rescale_grad
+        1/(batch * world)) or "module" (train_multitask.py's mx.mod.Module: lr * lr_mult, weight decay only on *_weight /
+        *_gamma, rescale_grad 1/world, :248).  rescale_grad: overrides either rule's.  Under both, frozen parameters
+        (the net's fixed_param_names) and their momenta are never written and never all-reduced."""
+        if optimizer_rules not in OPTIMIZER_RULES:
+            raise ValueError("optimizer_rules must be one of %s, got %r" % (OPTIMIZER_RULES, optimizer_rules))
+        self.optimizer_rules, self.rescale_grad = optimizer_rules, rescale_grad
         self.net, self.g = net, net.g
         self.track_bn_stats = bool(track_bn_stats)
         if aux_params:
@@ -164,7 +223,17 @@ class MultiTaskSolver:
                     owner.setdefault(v.name, idx)
                     owner[v.name] = min(owner[v.name], idx)
         params = [(p.name, p.offset, (p.size + 3) // 4 * 4) for p in g.param_order]
-        self.buckets = plan_buckets(params, owner, g.arena.numel(), int(bucket_mb * (1 << 20) / 4))
+        fixed = {p.name for p in g.param_order if p.fixed}
+        self.buckets = plan_buckets(params, owner, g.arena.numel(), int(bucket_mb * (1 << 20) / 4), frozen=fixed or None)
+        # something frozen or the Module rule: one segmented launch over the trainable ranges with their multipliers; else
+        # the single launch over the whole arena of earlier builds
+        self.sgd_rows = self.sgd_table = None
+        if fixed or optimizer_rules == "module":
+            self.sgd_rows = sgd_segments([(p.offset, (p.size + 3) // 4 * 4)
+                                          + rule_multipliers(p.name, optimizer_rules, p.lr_mult, p.wd_mult)
+                                          for p in g.param_order if not p.fixed])
+            if self.sgd_rows and g.device.type == "cuda":
+                self.sgd_table = fn.sgd_segment_table(self.sgd_rows, g.arena.numel(), g.device)
         self.reducer = (GradBucketReducer(g.grad_arena, self.buckets, process_group)
                         if (world_size > 1 or force_reducer) else None)
         # round 6: with an all-reduce to feed, the weight gradients stay on the step's stream (engine.WGRAD_SIDE): a bucket's
@@ -234,10 +303,25 @@ class MultiTaskSolver:
         g.join_side_backward()
         self.reducer.finish()
 
+    def rescale(self):
+        if self.rescale_grad is not None:
+            return float(self.rescale_grad)
+        if self.optimizer_rules == "module":
+            return 1.0 / self.world_size
+        return 1.0 / (self.batch_size * self.world_size)
+
     def update(self):
         g = self.g
-        fn.sgd_momentum(g.arena, g.grad_arena, g.mom_arena, self.lr, self.momentum, self.wd,
-                        1.0 / (self.batch_size * self.world_size))
+        if self.sgd_rows is None:
+            fn.sgd_momentum(g.arena, g.grad_arena, g.mom_arena, self.lr, self.momentum, self.wd, self.rescale())
+        elif not self.sgd_rows:
+            return                     # every parameter is frozen: nothing to update
+        elif self.sgd_table is None:
+            raise RuntimeError("MultiTaskSolver.update: the segmented update runs on a GPU graph only (this one is on %s)"
+                               % g.device)
+        else:
+            fn.sgd_momentum_segments(g.arena, g.grad_arena, g.mom_arena, self.sgd_table, self.lr, self.momentum, self.wd,
+                                     self.rescale())
 
     def _on_step_stream(self, body):
         """run body() on the solver's stream with ordinary stream semantics for the caller (behind the caller's current
@@ -273,7 +357,8 @@ class MultiTaskSolver:
         if self._graph is not None:
             # the recorded SGD launch carries lr / momentum / wd BY VALUE: a schedule that moved them since the recording
             # (the reference's optimizer takes an lr_scheduler, multi_solver.py:221) drops the graph and records a new one
-            if (self.lr, self.momentum, self.wd) != self._graph_hyper:
+            # ... and so does set_params / load_params on a frozen weight: its derived operands are formed outside the recording
+            if (self.lr, self.momentum, self.wd) != self._graph_hyper or self.g.frozen_stale:
                 self._graph = None
                 if not self.capture(warmup=0):
                     self._train_forward(); self.backward(); self.update()
@@ -311,6 +396,7 @@ class MultiTaskSolver:
         # the recording keeps the range guard's decisions it is made with: they come from a calibration pass (a graph
         # recorded before any step would otherwise never be calibrated) and are settled BEFORE the recording starts
         def settle():
+            self.g.refresh_frozen()
             self._calibrate_guard()
             for _ in range(warmup):               # first-use work (function attributes, workspace growth) happens eagerly
                 self._step()
@@ -386,6 +472,9 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
     from .metric import CustomAccuracyMetric, MultiBoxMetric
     logger = logger or logging
     net = solver.net
+    fixed = list(getattr(net, "fixed_param_names", None) or ())
+    if fixed:
+        logger.info("Freezed parameters: [" + ','.join(fixed) + ']')      # (train_multitask.py:231)
     multibox_metric = MultiBoxMetric()
     # a detection-only graph (get_det_symbol_train) has no segmentation output: no pixel-accuracy metric, as in the
     # reference's det_solver.py; a segmentation-only graph keeps MultiBoxMetric's SegCrossEntropy slot only

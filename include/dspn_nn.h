@@ -396,7 +396,10 @@ int dspn_bn_apply_planes_f32(const float *x, const float *scale, const float *sh
 /* Backward of the fused op.  If relu != 0, dy is first masked with (x*scale + shift > 0), i.e. the
  * forward output's sign recomputed from x (the forward output itself is not read).
  * dx (+)= gamma*rstd*(dy - mean(dy) - xhat*mean(dy*xhat)); dgamma = sum dy*xhat; dbeta = sum dy.
- * dgamma may be NULL (fix_gamma).  accumulate != 0: dx += .
+ * dgamma may be NULL (fix_gamma), dbeta may be NULL (frozen beta).  accumulate != 0: dx += .
+ * dx == NULL: the parameter gradients alone (an input that needs no gradient) -- the reductions and the finalize run, the
+ * apply pass does not; dgamma / dbeta have the bits of the full call.  The same holds for dspn_bn_backward_maxpool_f32, and
+ * for dspn_bn_backward_from_sums_* with the finalize-only flag word 2 (nothing may be parked, no apply half follows).
  * dx_absmax (optional, float tensors): DSPN_ABSMAX_SLOTS floats that receive the partial maxima of |dx| AS STORED (after
  * the accumulation), i.e. dspn_absmax_f32(dx) without its pass over dx: the magnitude the convolution that produced x
  * needs for its data / weight gradient in DSPN_MATH_F32_F16X2.  The caller zeroes it, as for dspn_absmax_f32. */
@@ -490,7 +493,7 @@ int dspn_maxpool_forward_bn_f32(const float *x, const float *in_scale, const flo
 /* ... and its backward (round 4): the backward of that BatchNorm(+ReLU) with its output gradient formed ON THE FLY from the
  * pooled gradient dy_pool (N, Ho, Wo, C) and the argmax record (the gather of dspn_maxpool_backward_argmax_f32) -- the dense
  * (N, H, W, C) gradient of the pooling input is neither written nor read back twice.  x: the BatchNorm input (N, H, W, C);
- * dx, dgamma (may be NULL), dbeta as dspn_bn_backward_f32; dx_absmax (optional): magnitude block of dx, zeroed by the caller;
+ * dx (NULL: parameters only), dgamma, dbeta (each may be NULL) as dspn_bn_backward_f32; dx_absmax (optional): magnitude block of dx, zeroed by the caller;
  * workspace: dspn_bn_workspace_bytes(N * H * W, C). */
 int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float *shift, const float *dy_pool,
                                  const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
@@ -620,6 +623,22 @@ int dspn_sum_f32(const float *a, long long n, float *out, void *stream);
  * g = rescale*grad + wd*w ; mom = momentum*mom - lr*g ; w += mom, over a flat parameter arena. */
 int dspn_sgd_momentum_f32(float *w, const float *grad, float *mom, long long n, float lr, float momentum,
                           float wd, float rescale, void *stream);
+
+/* Segmented update: the same rule over the rows of a DEVICE table, one launch, with per-row multipliers:
+ *   g = rescale*grad + (wd*wd_mult)*w ; mom = momentum*mom - (lr*lr_mult)*g ; w += mom
+ * (lr*lr_mult and wd*wd_mult formed in float32: rows with both multipliers 1.0 give dspn_sgd_momentum_f32's bits).
+ * Rows: offset and length in floats, both multiples of 4, disjoint and sorted by offset; total4 = sum(length) / 4;
+ * 1 <= nseg <= DSPN_SGD_MAX_SEGMENTS.  Floats outside every row are neither read nor written (frozen parameters and their
+ * momenta).  lr, momentum, wd and rescale travel by value, so a recorded launch keeps its table and changes only them. */
+#define DSPN_SGD_MAX_SEGMENTS 8192
+typedef struct dspn_sgd_segment {
+  long long offset;
+  long long length;
+  float lr_mult;
+  float wd_mult;
+} dspn_sgd_segment;
+int dspn_sgd_momentum_segments_f32(float *w, const float *grad, float *mom, const dspn_sgd_segment *segments, int nseg,
+                                   long long total4, float lr, float momentum, float wd, float rescale, void *stream);
 
 /* ---- bfloat16 twins of the HBM-bound kernels (same conventions as the convolution twins above: activation pointers
  * are bfloat16, everything per-channel / reduced / float-only keeps its type; dspn_nchw_to_nhwc_bf16 takes the float
