@@ -18,12 +18,13 @@ arenas) so the optimizer is one kernel and data-parallel reduction works on a
 few large contiguous buckets.
 """
 import math
+import os
 import re
 
 import numpy as np
 import torch
 
-from . import functional as fn
+from . import functional as fn, graph_plan
 
 
 # Test switch: with FUSE_BATCHNORM = False every BatchNorm runs its own statistics / apply / backward kernels and
@@ -34,8 +35,7 @@ FUSE_BATCHNORM = True
 COMMUTE_RESIZE_CONV = True
 # A/B switch (bf16 tensors): BatchNorm outputs read by multi-tap convolutions are materialised instead of being applied in
 # the loaders ("auto" BatchNorms: inceptionv3 towers; the residual units set theirs in symbol/resnet.py)
-import os as _os
-MATERIALISE_MULTITAP_INPUT_BF16 = _os.environ.get("DSPN_MAT3X3", "1") != "0"
+MATERIALISE_MULTITAP_INPUT_BF16 = os.environ.get("DSPN_MAT3X3", "1") != "0"
 
 
 _SHARED_STREAMS = {}
@@ -118,6 +118,7 @@ class Tensor:
         # their tile loaders, see BatchNorm(defer_apply=True)); .data stays None so any other consumer fails loudly
         self.affine_src = None
         self.producer = None       # the Conv node that writes this tensor (it can emit BatchNorm tile statistics)
+        self.bn_node = None        # the BatchNorm node that writes (or, deferred, describes) this tensor
         # "f16x2" math: index of a magnitude block that BOUNDS |values| once the producer has run in this step (a materialised
         # BatchNorm takes it while it writes the tensor; pooled / aliased tensors inherit their source's -- a bound that is too
         # large by less than 2^17 costs the two-piece math nothing), and the tensor whose values this one shares (BlockGrad)
@@ -174,8 +175,27 @@ class Param:
         return int(np.prod(self.shape))
 
 
+class Wiring:
+    """What a node writes and reads, recorded ONCE (Graph.add) and read by everything that plans from the graph's structure:
+    the freeze rule, the passes of graph_plan, the solver's bucket owners.  A node is wired completely in its constructor."""
+
+    def __init__(self, outputs):
+        self.outputs = outputs     # the engine Tensors the node's constructor made, in creation order
+        self.reads = []            # (attribute name, Tensor) of every other Tensor it holds: the name is the role (x, x_raw, residual ...)
+        self.params = []           # the Params it holds
+
+    def record(self, node):
+        made = {id(t) for t in self.outputs}
+        for k, v in vars(node).items():
+            for t in (v.values() if isinstance(v, dict) else v if isinstance(v, (list, tuple)) else (v,)):
+                if isinstance(t, Tensor) and id(t) not in made:
+                    self.reads.append((k, t))
+                elif isinstance(t, Param):
+                    self.params.append(t)
+
+
 class Node:
-    """Every node's constructor takes the graph first.  The tensors it creates are its outputs (Graph._derive_requires_grad):
+    """Every node's constructor takes the graph first.  The tensors it creates are its outputs (Wiring.outputs):
     __init_subclass__ brackets the outermost constructor with the graph's tensor count."""
 
     def __init_subclass__(cls, **kw):
@@ -185,12 +205,12 @@ class Node:
             return
 
         def wrapped(self, g, *args, __init=init, **kwargs):
-            if "_made" in self.__dict__:           # (a subclass constructor calling its parent's)
+            if "wiring" in self.__dict__:          # (a subclass constructor calling its parent's)
                 return __init(self, g, *args, **kwargs)
             start = len(g.all_tensors)
-            self._made = None
+            self.wiring = None
             __init(self, g, *args, **kwargs)
-            self._made = (start, len(g.all_tensors))
+            self.wiring = Wiring(g.all_tensors[start:])
         wrapped.__wrapped__ = init
         cls.__init__ = wrapped
 
@@ -231,8 +251,8 @@ class Graph:
         # ... and the BACKWARD of some of those nodes beside the decoder's (set_side_backward): only nodes whose gradients
         # stay inside the branch; every main-stream node of the branch waits for what the side stream has been given so far
         self.side_bwd = None
-        self.side_fwd_events, self.side_fwd_waits = {}, {}   # _plan_side_sync
-        self.side_plan = None      # what the builder asked for (any device) and what _plan_side_sync made of it
+        self.side_fwd_events, self.side_fwd_waits = {}, {}   # graph_plan.side_sync
+        self.side_plan = None      # what the builder asked for (any device) and what graph_plan.side_sync made of it
         self.slab_tables = {}      # key -> (conv nodes, device table) of deferred split-K slab reductions
         self.wt_table = None       # descriptor table of every Conv's (weight, transposed weight) pair
         self.wt_batched = False    # True while backward() runs after one batched transpose launch
@@ -260,7 +280,7 @@ class Graph:
         # gradients from the BatchNorm backward's per-channel bounds); a convolution one of whose operands spanned more than
         # 2^GUARD_BITS in the PREVIOUS pass runs all three of its calls in the three-piece bf16 math this step (guard_fb on the
         # node; the span of a trained net's channels moves over many steps, not within one).  DSPN_RANGE_GUARD=0 switches it off.
-        self.guard = dict(enabled=_os.environ.get("DSPN_RANGE_GUARD", "1") != "0", have_stats=False, risk=frozenset(),
+        self.guard = dict(enabled=os.environ.get("DSPN_RANGE_GUARD", "1") != "0", have_stats=False, risk=frozenset(),
                           calls=0, calls_total=0, at_risk_slots=0)
         self.wmin_table = None     # descriptor table of the per-output-channel weight minima (one launch per step)
         # frozen parameters (set_freeze, before the first node is built): names and / or a regex matched with re.match
@@ -271,7 +291,6 @@ class Graph:
         self.wt_frozen = self.wp_frozen = self.am_frozen = self.wmin_frozen = None
         self.frozen_stale = False
         self._nscal_step = 0
-        self._add_mark = 0         # len(all_tensors) after the last add(): the tensors a node's constructor made follow it
 
     def set_freeze(self, fixed_param_names=None, freeze_pattern=None):
         """Freeze parameters of the nodes built from now on: every name in fixed_param_names and every name freeze_pattern
@@ -307,28 +326,16 @@ class Graph:
         return p
 
     def add(self, node):
+        """Records the node's wiring; while freezing, applies MXNet's gradient rule: its outputs need a gradient only if an input
+        does or it owns a parameter that is not frozen.  Only ever switches a gradient off: a node nothing behind asks a
+        gradient of never runs its backward (Tensor._gw stays False), so a frozen prefix leaves backward altogether."""
         self.nodes.append(node)
-        if self.freezing:
-            self._derive_requires_grad(node)
-        self._add_mark = len(self.all_tensors)
-        return node
-
-    def _derive_requires_grad(self, node):
-        """MXNet's gradient rule for a node just built: its outputs (the tensors its constructor made) need a gradient only if
-        an input does or it owns a parameter that is not frozen.  Only ever switches a gradient off: a node nothing behind
-        asks a gradient of never runs its backward (Tensor._gw stays False), so a frozen prefix leaves backward altogether."""
-        lo, hi = getattr(node, "_made", None) or (self._add_mark, len(self.all_tensors))
-        made = {id(t) for t in self.all_tensors[lo:hi]}
-        ins, outs, trainable = [], [], False
-        for v in vars(node).values():
-            for t in (list(v.values()) if isinstance(v, dict) else v if isinstance(v, (list, tuple)) else [v]):
-                if isinstance(t, Tensor):
-                    (outs if id(t) in made else ins).append(t)
-                elif isinstance(t, Param) and not t.fixed:
-                    trainable = True
-        if not trainable and not any(t.requires_grad for t in ins):
-            for t in outs:
+        w = node.wiring
+        w.record(node)
+        if self.freezing and all(p.fixed for p in w.params) and not any(t.requires_grad for _, t in w.reads):
+            for t in w.outputs:
                 t.requires_grad = False
+        return node
 
     def new_scalar(self, backward=False):
         """index of a fresh slot of the operand-magnitude arena ("f16x2" math).  backward=True: the magnitude of a gradient;
@@ -476,157 +483,9 @@ class Graph:
         """(convolutions on the fallback this pass, fallback kernel calls this pass, slots whose span exceeded 2^GUARD_BITS last pass)"""
         return len(self.guard["risk"]), self.guard["calls"], self.guard["at_risk_slots"]
 
-    def _resolve_auto_deferred(self):
-        """BatchNorm(defer_apply="auto"): keep the output virtual only if every reader is a plain convolution input;
-        otherwise (a concat, a pooling layer, a residual operand ...) materialise it and unhook the convolutions."""
-        readers = {}
-        for n in self.nodes:
-            for k, v in vars(n).items():
-                if k in ("out", "x_raw"):
-                    continue
-                for t in (v if isinstance(v, (list, tuple)) else [v]):
-                    if isinstance(t, Tensor) and t.affine_src is not None:
-                        ok = isinstance(n, Conv) and k == "x" and not n.tap_expand
-                        # bf16 tensors: a multi-tap convolution would re-apply the affine once per tap on a main loop that
-                        # is 3x shorter than in fp32 (scratch/fuse_cost.py bf16: +45 %); its input is materialised instead
-                        if ok and MATERIALISE_MULTITAP_INPUT_BF16 and t.dtype == torch.bfloat16 and n.w.shape[1] * n.w.shape[2] > 1:
-                            ok = False
-                        readers.setdefault(id(t), []).append((n, ok))
-        for n in self.nodes:
-            if not isinstance(n, BatchNorm) or n.defer_apply != "auto":
-                continue
-            rs = readers.get(id(n.out), [])
-            if rs and all(ok for _, ok in rs):
-                n.defer_apply = True
-                continue
-            n.defer_apply = False
-            n.out.affine_src = None
-            n.out.data = fn.zeros(*n.out.shape, device=self.device, dtype=n.out.dtype)
-            for c in n.conv_consumers:
-                c.x_raw, c.in_affine = c.x, None
-            n.mat_consumers = list(n.conv_consumers)     # still candidates for gathering the backward reductions
-            n.conv_consumers = []
-
-    def _plan_bn_backward_fusion(self):
-        """For every BatchNorm whose output only convolutions read: the convolution that runs LAST in backward (the
-        first in forward order) gathers the BatchNorm-backward reductions in its data-gradient epilogue."""
-        # every reader of a tensor, to make sure the convolutions are the ONLY readers of a materialised BatchNorm output
-        readers = {}
-        for m in self.nodes:
-            for k, v in vars(m).items():
-                if k == "out":
-                    continue
-                for t in (v if isinstance(v, (list, tuple)) else [v]):
-                    if isinstance(t, Tensor):
-                        readers.setdefault(id(t), set()).add(id(m))
-        for n in self.nodes:
-            if not isinstance(n, BatchNorm) or not n.out.requires_grad:
-                continue
-            cons = n.conv_consumers if n.defer_apply else n.mat_consumers
-            if not cons or (not n.defer_apply and readers.get(id(n.out), set()) != {id(c) for c in cons}):
-                continue
-            last = min(cons, key=self.nodes.index)
-            if last.stride not in (1, 2) or (last.stride == 2 and last.dil != 1) or last.x.shape[3] % 4 != 0:
-                continue
-            tiles = fn.conv_dgrad_bn_tiles(last.x.shape, last.stride)
-            if tiles <= 0:
-                continue
-            n.bwd_sums = (fn.zeros(tiles, 2, last.x.shape[3], device=self.device), tiles)
-            n.bwd_ws = fn.bn_from_sums_workspace(tiles, n.x.shape[-1], self.device)
-            last.bn_bwd_node = n
-
-    def _plan_gradient_magnitudes(self):
-        """"f16x2" math: a BatchNorm whose backward is the LAST writer of its input's gradient (backward runs the nodes in
-        reverse: the reader with the smallest index) stores the complete gradient, so its apply kernel can also take the
-        magnitude the producing convolution needs (BatchNorm.completes_x_grad)."""
-        first_reader, readers = {}, {}
-        for idx, m in enumerate(self.nodes):
-            for k, v in vars(m).items():
-                if k == "out":
-                    continue
-                for t in (v if isinstance(v, (list, tuple)) else [v]):
-                    if isinstance(t, Tensor):
-                        first_reader.setdefault(id(t), idx)
-                        readers.setdefault(id(t), set()).add(idx)
-        for idx, n in enumerate(self.nodes):
-            if isinstance(n, BatchNorm):
-                n.completes_x_grad = first_reader.get(id(n.x)) == idx
-        # a convolution read by nothing but another convolution's residual add (the projection shortcut of a unit) receives
-        # that convolution's output gradient itself (Tensor.give_grad aliases it): one magnitude slot serves both
-        for idx, n in enumerate(self.nodes):
-            r = getattr(n, "residual", None)
-            if isinstance(n, Conv) and n.am_dy is not None and r is not None and r.requires_grad:
-                prod = getattr(r, "producer", None)
-                if (isinstance(prod, Conv) and prod.am_dy is not None and prod.out is r and readers.get(id(r)) == {idx}
-                        and not prod.relu and prod.b is None):
-                    prod.am_dy = n.am_dy
-
-    def _plan_gradient_planes(self):
-        """"f16x2" math, round 4: a BatchNorm whose backward (from the sums its consumer's data gradient gathered) is the ONLY
-        writer of its input's gradient, and whose input is the dense output of a plain convolution, writes that gradient as
-        fp16 piece planes -- same buffer, same bytes -- cut by a bound it forms beforehand (dspn_bn_backward_from_sums_f32,
-        dx_planes); the convolution's data gradient and weight gradient then copy their dy operand instead of cutting it
-        once per tap and column tile.  In the residual units: bn2 -> conv1 and bn3 -> conv2."""
-        if self.math != "f16x2" or self.device.type != "cuda":
-            return
-        readers = {}
-        for idx, m in enumerate(self.nodes):
-            for k, v in vars(m).items():
-                if k in ("out", "x_raw"):      # (x_raw: a convolution reading THROUGH a deferred BatchNorm; the gradient goes to the BatchNorm)
-                    continue
-                for t in (v if isinstance(v, (list, tuple)) else [v]):
-                    if isinstance(t, Tensor):
-                        readers.setdefault(id(t), set()).add(idx)
-        gatherer = {id(n.bn_bwd_node): n for n in self.nodes if isinstance(n, Conv) and getattr(n, "bn_bwd_node", None) is not None}
-        for idx, n in enumerate(self.nodes):
-            if not isinstance(n, BatchNorm) or n.bwd_sums is None or id(n) not in gatherer:
-                continue
-            prod, x = getattr(n.x, "producer", None), n.x
-            if not (isinstance(prod, Conv) and prod.out is x and readers.get(id(x)) == {idx} and x.requires_grad
-                    and x.dtype == torch.float32 and n.completes_x_grad and n.tile_stats is not None):
-                continue
-            if (prod.tap_expand or prod.relu or prod.b is not None or prod.residual is not None or prod.input_sum_grad is not None
-                    or prod.am_dy is None or x.shape[3] != prod.cout or prod.cout % 32 != 0 or prod.out_minmax is None
-                    or gatherer[id(n)].math != "f16x2"):
-                continue
-            n.dx_planes = True
-            n.x_ext = fn.zeros(2, x.shape[3], device=self.device)
-            n.am_dyin = self.new_scalar(backward=True)
-
-    def _plan_input_planes(self):
-        """"f16x2" math, round 4: a deferred BatchNorm whose readers re-read it often (X_PLANES_MIN_READS) also writes
-        (relu)(x * scale + shift) as fp16 piece planes (dspn_bn_apply_planes_f32), cut by the magnitude its statistics finalize
-        has just formed; that convolution's forward and weight gradient then copy their x operand into LDS instead of applying
-        the affine and cutting every element once per (tap, column tile) -- 9 x Cout / 128 times for a 3 x 3.  The 1 x 1 readers
-        (and the BatchNorm backward) keep reading the raw tensor.  In the residual units: bn2 -> conv2."""
-        if self.math != "f16x2" or self.device.type != "cuda":
-            return
-        for n in self.nodes:
-            if not isinstance(n, BatchNorm) or n.defer_apply is not True or n.tile_stats is None:
-                continue
-            x = n.x
-            if (x.dtype != torch.float32 or x.shape[3] % 32 != 0 or x.data is None
-                    or getattr(getattr(x, "producer", None), "out_minmax", None) is None):
-                continue
-            cons = [c for c in n.conv_consumers if c.math == "f16x2" and c.wp is not None and c.x_raw is x]
-            # how often the tile loaders would apply the affine to (and cut) one element: once per tap and 128-column tile
-            reads = sum(c.w.shape[1] * c.w.shape[2] * ((c.cout + 127) // 128) for c in cons)
-            if reads < X_PLANES_MIN_READS:
-                continue
-            n.planes = fn.zeros(*x.shape, device=self.device)
-            for c in cons:
-                c.x_planes_bn = n
-
     def finalize(self, seed=0):
         """allocate the flat parameter / gradient / momentum arenas and initialise"""
-        self._resolve_auto_deferred()
-        self._plan_side_sync()
-        if _os.environ.get("DSPN_X_PLANES", "1") != "0":       # (A/B switch)
-            self._plan_input_planes()
-        self._plan_bn_backward_fusion()
-        self._plan_gradient_magnitudes()
-        if _os.environ.get("DSPN_DY_PLANES", "1") != "0":      # (A/B switch)
-            self._plan_gradient_planes()
+        graph_plan.plan(self)
         self._wt_pairs_nodes = [n for n in self.nodes if isinstance(n, Conv) and (n.wt is not None or n.wh is not None)]
         off = 0
         for p in self.param_order:
@@ -742,11 +601,9 @@ class Graph:
         for k, v in values.items():
             self.params[k].data.copy_(torch.from_numpy(np.ascontiguousarray(v, np.float32)).view(self.params[k].shape))
 
-
-    # -- stream ordering of the side segment (round 5) ---------------------------------------------
     def _node_tensors(self, n):
-        """every engine Tensor a node holds (attributes, lists / tuples of them), each with the tensors whose buffers it reads
-        through: the raw input of a deferred BatchNorm (affine_src) and the source of a BlockGrad alias"""
+        """every engine Tensor a node holds (its wiring record), each with the tensors whose buffers it reads through: the raw
+        input of a deferred BatchNorm (affine_src) and the source of a BlockGrad alias"""
         seen, out = set(), []
 
         def take(t):
@@ -757,83 +614,9 @@ class Graph:
                     take(t.affine_src[0])
                 t = t.alias_of
 
-        for v in vars(n).values():
-            for t in (v if isinstance(v, (list, tuple)) else [v]):
-                if isinstance(t, Tensor):
-                    take(t)
+        for t in [t for _, t in n.wiring.reads] + n.wiring.outputs:
+            take(t)
         return out
-
-    @staticmethod
-    def _node_outputs(n):
-        outs = []
-        for k, v in vars(n).items():
-            if k == "out" or k.startswith("out_") or k in ("outs", "cls_prob", "cls_preds", "prob"):
-                outs += [t for t in (v if isinstance(v, (list, tuple)) else [v]) if isinstance(t, Tensor)]
-        return outs
-
-    def _plan_side_sync(self):
-        """Called by finalize().  The builder only says WHICH nodes run beside the main stream; what orders the two streams
-        is derived here from the tensors the nodes hold, so that a preset whose wiring differs (vgg16_reduced, inceptionv3,
-        resnet-101: the decoder reads an SSD extra layer's output, symbol/multitask_symbol_builder.py `conv_feat`) cannot
-        silently become a race:
-        * forward: a main-stream node behind the segment that holds a tensor written inside it waits for an event recorded
-          behind the LAST in-segment node that writes (or, failing that, last holds) that tensor -- not for the whole branch;
-        * backward: a node leaves the side set if it shares a tensor with a main-stream node that runs between the fork and
-          itself (the decoder writes that tensor's gradient on the main stream while the side stream, which only waits for
-          the fork event, would read or accumulate into it), repeated until nothing changes."""
-        plan = self.side_plan
-        self.side_fwd_events, self.side_fwd_waits = {}, {}
-        if plan is None:
-            return
-        first, last = plan["first"], plan["last"]
-        cuda = self.side_segment is not None
-        refs = [self._node_tensors(n) for n in self.nodes]
-        holders = {}
-        for i, ts in enumerate(refs):
-            for t in ts:
-                holders.setdefault(id(t), []).append(i)
-        before = set()
-        for i in range(first):
-            before.update(id(t) for t in refs[i])
-        for tid, idxs in holders.items():
-            inside = [i for i in idxs if first <= i <= last]
-            outside = [i for i in idxs if i > last]
-            if not inside or not outside or tid in before:
-                continue
-            writers = [i for i in inside if any(id(t) == tid for t in self._node_outputs(self.nodes[i]))]
-            # no declared writer (a node type whose output attribute _node_outputs does not know): behind the LAST in-segment
-            # holder, which is safe whichever of them writes
-            src = max(writers) if writers else max(inside)
-            if src not in self.side_fwd_events:
-                self.side_fwd_events[src] = torch.cuda.Event() if cuda else None
-            for r in outside:
-                w = self.side_fwd_waits.setdefault(r, [])
-                if src not in w:
-                    w.append(src)
-        plan["fwd_waits"] = {r: list(w) for r, w in self.side_fwd_waits.items()}
-        sb = plan["bwd"]
-        if sb is None:
-            return
-        side, fork_after = set(sb["side"]), sb["fork_after"]
-        has_bwd = [type(n).backward is not Node.backward for n in self.nodes]
-        changed = True
-        while changed:
-            changed = False
-            for i in sorted(side):
-                mine = {id(t) for t in refs[i]}
-                for x in range(i + 1, fork_after):
-                    if x in side or not has_bwd[x]:
-                        continue
-                    if mine & {id(t) for t in refs[x]}:
-                        side.discard(i)
-                        changed = True
-                        break
-        sb["removed"] = frozenset(sb["side"]) - side
-        sb["side"] = frozenset(side)
-        if self.side_bwd is not None:
-            self.side_bwd["side"] = frozenset(side)
-            if not side:
-                self.side_bwd = None
 
     # -- execution ------------------------------------------------------------
     def forward(self):
@@ -867,7 +650,7 @@ class Graph:
         self.join_side()
         for i, n in enumerate(self.nodes):
             if i < first or i > last:
-                for src in self.side_fwd_waits.get(i, ()):     # (a tensor written inside the segment: _plan_side_sync)
+                for src in self.side_fwd_waits.get(i, ()):     # (a tensor written inside the segment: graph_plan.side_sync)
                     torch.cuda.current_stream(self.device).wait_event(self.side_fwd_events[src])
                 n.forward()
                 continue
@@ -903,7 +686,7 @@ class Graph:
 
     def set_side_segment(self, first, last):
         """nodes [first, last] run their forward on the branch stream.  On a CPU graph only the plan is kept (side_plan):
-        tests/test_side_plan.py checks what _plan_side_sync derives from it for every preset without a GPU."""
+        tests/test_side_plan.py checks what graph_plan.side_sync derives from it for every preset without a GPU."""
         assert 0 <= first <= last < len(self.nodes)
         self.side_plan = dict(first=first, last=last, bwd=None)
         if self.device.type == "cuda":
@@ -949,7 +732,7 @@ class Graph:
         without BatchNorm the chain is as MFMA-bound as the weight gradients and sharing the chip costs (vgg16_reduced)"""
         if self._bn_chain is None:
             convs = [n for n in self.nodes if isinstance(n, Conv)]
-            self._bn_chain = 2 * sum(1 for n in convs if getattr(n, "bn_bwd_node", None) is not None) > len(convs)
+            self._bn_chain = 2 * sum(1 for n in convs if n.bn_bwd_node is not None) > len(convs)
         return self._bn_chain
 
     def wgrad_beside(self, conv, dy, planes, xa, dya):
@@ -1194,10 +977,10 @@ class InputNCHW(Node):
         fn.nchw_to_nhwc(self.src.data, out=self.out.data)
 
 
-# Graph._plan_input_planes: a deferred BatchNorm output is ALSO written as piece planes when its readers would otherwise apply
+# graph_plan.input_planes: a deferred BatchNorm output is ALSO written as piece planes when its readers would otherwise apply
 # the affine to each element at least this many times (taps x 128-column tiles, summed over the readers)
-FUSE_MAXPOOL_BACKWARD = _os.environ.get("DSPN_FUSE_POOL_BWD", "1") != "0"      # (A/B switch)
-X_PLANES_MIN_READS = int(_os.environ.get("DSPN_X_PLANES_MIN_READS", "6"))
+FUSE_MAXPOOL_BACKWARD = os.environ.get("DSPN_FUSE_POOL_BWD", "1") != "0"      # (A/B switch)
+X_PLANES_MIN_READS = int(os.environ.get("DSPN_X_PLANES_MIN_READS", "6"))
 
 
 class BatchNorm(Node):
@@ -1238,7 +1021,7 @@ class BatchNorm(Node):
         # statistics gathered by the producing convolution's epilogue (one (mean, M2) pair per row tile) instead of a
         # separate pass over x
         self.tile_stats = (x.producer.enable_out_stats()
-                           if FUSE_BATCHNORM and getattr(x, "producer", None) is not None else None)
+                           if FUSE_BATCHNORM and x.producer is not None else None)
         self.out = g.tensor(x.shape, name + ("_relu" if relu else "_out"), requires_grad=not beta_grad_from_consumer,
                             virtual=bool(defer_apply))
         if defer_apply:
@@ -1253,10 +1036,10 @@ class BatchNorm(Node):
         self.bwd_sums = None         # (buffer, tiles) written by the LAST data gradient into self.out.grad
         self.bwd_sums_ready = False
         self.bwd_ws = None           # with bwd_sums: this node's workspace of the backward from them (coefficients, grouped tiles)
-        # round 4 (Graph._plan_gradient_planes): dx leaves as fp16 piece planes; x_ext = per-channel extremes of x from the
+        # round 4 (graph_plan.gradient_planes): dx leaves as fp16 piece planes; x_ext = per-channel extremes of x from the
         # forward finalize, am_dyin = slot of the magnitude of this node's own output gradient (from the data gradient's epilogue)
         self.dx_planes, self.x_ext, self.am_dyin = False, None, None
-        # round 4 (Graph._plan_input_planes): the output as fp16 piece planes for the multi-tap convolutions behind a DEFERRED
+        # round 4 (graph_plan.input_planes): the output as fp16 piece planes for the multi-tap convolutions behind a DEFERRED
         # apply; planes_ready: written by this step's forward (the magnitude they are cut by came out of the finalize)
         self.planes, self.planes_ready = None, False
         self.pool_grad = None        # (argmax, pooled gradient, k, stride, pad) left by a MaxPool that folds this node (one backward)
@@ -1354,7 +1137,7 @@ class BatchNorm(Node):
             # "f16x2" math: dx is the output gradient of the convolution that produced x; when this call completes it (a
             # tensor read by this BatchNorm alone, or the residual stream, whose last writer in backward order is the next
             # unit's first BatchNorm), its magnitude comes out of the apply kernel instead of a pass of its own
-            prod, g = getattr(self.x, "producer", None), self._g
+            prod, g = self.x.producer, self._g
             if (isinstance(prod, Conv) and prod.am_dy is not None and g.scalars is not None and dx.dtype == torch.float32
                     and self.completes_x_grad):
                 am = g.scalar(prod.am_dy)
@@ -1402,16 +1185,16 @@ class BatchNorm(Node):
 # them still reads: WgradSide.before_write).  Same kernels, same bits; +1.9 % on the step (profiles/r06_wgrad_beside_ab.txt).
 # DSPN_WGRAD_SIDE=0: on the step's stream, with the BatchNorm finalize riding in their launches (below).  bench.py switches
 # it off for its instrumented steps: a kernel timed beside another one measures the pair, not the kernel.
-WGRAD_SIDE = int(_os.environ.get("DSPN_WGRAD_SIDE", "1"))
-WGRAD_SIDE_MIN_US = float(_os.environ.get("DSPN_WGRAD_SIDE_MIN_US", "30"))      # (Conv._wgrad_worth_a_stream)
+WGRAD_SIDE = int(os.environ.get("DSPN_WGRAD_SIDE", "1"))
+WGRAD_SIDE_MIN_US = float(os.environ.get("DSPN_WGRAD_SIDE_MIN_US", "30"))      # (Conv._wgrad_worth_a_stream)
 
 # round 6: the finalize half of a BatchNorm backward rides in the weight-gradient launch of the layer behind it
 # (DSPN_FINALIZE_BESIDE=0: launches of its own, as round 5 -- same-box A/B; the results do not depend on it)
-FINALIZE_BESIDE = _os.environ.get("DSPN_FINALIZE_BESIDE", "1") != "0"
+FINALIZE_BESIDE = os.environ.get("DSPN_FINALIZE_BESIDE", "1") != "0"
 
 # round 5: convolutions no BatchNorm reads leave the magnitude of their output (forward epilogue) and of their masked gradient
 # (the ReLU-backward / bias-gradient pass) as by-products; DSPN_CONV_MAGNITUDES=0 keeps the stand-alone passes (same-box A/B)
-FUSE_CONV_MAGNITUDES = _os.environ.get("DSPN_CONV_MAGNITUDES", "1") != "0"
+FUSE_CONV_MAGNITUDES = os.environ.get("DSPN_CONV_MAGNITUDES", "1") != "0"
 
 
 def xa_unavailable(conv):
@@ -1436,7 +1219,7 @@ class Conv(Node):
             self.x_raw, self.in_affine = raw, (sc, sh, arelu)
             assert not tap_expand
             x.bn_node.conv_consumers.append(self)
-        elif getattr(x, "bn_node", None) is not None and not tap_expand:
+        elif x.bn_node is not None and not tap_expand:
             x.bn_node.mat_consumers.append(self)
         self.cout = num_filter
         # Param that receives sum_pixels(dx) instead of a full data gradient (see conv2d_input_sum_grad)
@@ -1487,7 +1270,9 @@ class Conv(Node):
             self.out.am_slot = self.am_out       # (pooled / aliased tensors built on it inherit the slot)
         if self.am_x is not None and self.in_affine is None:
             g.want_magnitude(self.x_raw)         # the producer of this input leaves its magnitude if it can
-        self.x_planes_bn = None      # the deferred BatchNorm that also leaves this node's input as piece planes (Graph._plan_input_planes)
+        self.x_planes_bn = None      # the deferred BatchNorm that also leaves this node's input as piece planes (graph_plan.input_planes)
+        self.bn_bwd_node = None      # the BatchNorm whose backward sums this node's data gradient gathers (graph_plan.bn_backward_fusion)
+        self._wg_worth = None        # _wgrad_worth_a_stream, once estimated
         self.guard_fb = False        # range guard (Graph._update_guard): this pass's calls run in the three-piece bf16 math
         self.wp = self.wtp = None
         if g.device.type == "cuda":
@@ -1548,7 +1333,7 @@ class Conv(Node):
             src = self.x_raw
             while src.alias_of is not None:       # BlockGrad: the same values under another name
                 src = src.alias_of
-            prod = getattr(src, "producer", None)
+            prod = src.producer
             # the producer's per-tile extremes of x_raw (written when some BatchNorm reads it): with an affine, its extremes
             # sit at the extremes of x (monotone per channel); without one, |x| is largest at one of them
             table = getattr(prod, "out_minmax", None) if getattr(prod, "out", None) is src else None
@@ -1654,7 +1439,7 @@ class Conv(Node):
             self._g._am_done.add(self.am_dy)      # (a projection shortcut that shares this slot reads the same gradient)
         # round 6: when this data gradient gathers the backward sums of the BatchNorm in front (bn_bwd_node), it goes FIRST and
         # that node's finalize rides in front of the weight gradient's grid (BatchNorm.finalize_beside)
-        bn = getattr(self, "bn_bwd_node", None) if self.x.requires_grad else None
+        bn = self.bn_bwd_node if self.x.requires_grad else None
         isg = self.input_sum_grad if (self.input_sum_grad is not None and not self.input_sum_grad.fixed) else None
         if self.w.fixed:
             # frozen weight: no weight gradient, so nothing for a BatchNorm finalize to ride in (it runs on its own) and no
@@ -1690,7 +1475,7 @@ class Conv(Node):
         vgg16_reduced (no BatchNorm: the chain is MFMA-bound like the weight gradients) -3.4 %, inceptionv3 1024 x 512 bs 8
         (launches of ~15 us) -7 % (profiles/r06_wgrad_beside_other_configs.txt).  Estimate: the larger of multiply-adds at
         250 TFLOP/s and operand bytes at 4 TB/s, at least WGRAD_SIDE_MIN_US."""
-        w = getattr(self, "_wg_worth", None)
+        w = self._wg_worth
         if w is None:
             P = float(np.prod(self.out.shape[:-1]))
             cout, kh, kw, cin = self.w.shape
@@ -1740,7 +1525,7 @@ class Conv(Node):
         elif self.wtp is None and not (g.wt_frozen is not None if self.w.fixed else g.wt_batched):
             fn.weight_transpose(self.w.data, out=self.wt, copy=self.wh)
         dx, acc = self.x.grad_target()
-        bn = getattr(self, "bn_bwd_node", None)   # set by Graph.finalize on the LAST writer of a deferred BN's gradient
+        bn = self.bn_bwd_node   # set by Graph.finalize on the LAST writer of a deferred BN's gradient
         bn_bwd, bn_dya = None, None
         if bn is not None:
             bn_bwd = (bn.x.data, bn.scale, bn.shift, bn.mean, bn.rstd, bn.relu, bn.bwd_sums[0])
@@ -1997,7 +1782,7 @@ class MaxPool(Node):
         if not self.out._gw or not self.x.requires_grad:
             return
         assert not self.x._gw, "maxpool input has a single consumer"
-        bn = getattr(self.x, "bn_node", None)
+        bn = self.x.bn_node
         if (self.in_affine is not None and self.argmax is not None and bn is not None and FUSE_MAXPOOL_BACKWARD
                 and self.out.grad.dtype == torch.float32 and self.out.grad.device.type == "cuda"):
             # round 4: the BatchNorm(+ReLU) folded into this pooling forms its output gradient from (pooled gradient, argmax)

@@ -6,6 +6,7 @@ count that is a multiple of 4; conv weights are [Cout, R, S, Cin]."""
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -328,7 +329,6 @@ def absmax(x, in_affine=None, out=None):
 
 def absmax_table(pairs, device):
     """pairs: [(float32 tensor, 64-element float32 output)] -> (device table, rows, total chunks) for absmax_batch"""
-    import numpy as np
     rows = np.zeros(len(pairs), dtype=[("x", "<u8"), ("out", "<u8"), ("n4", "<i8"), ("begin", "<i8")])
     total = 0
     for i, (t, o) in enumerate(pairs):
@@ -341,7 +341,6 @@ def absmax_table(pairs, device):
 
 def absmin_rows_table(pairs, device):
     """pairs: [(float32 weight [rows, ...], 1-element float32 output)] -> (device table, rows, total rows) for absmin_rows_batch"""
-    import numpy as np
     rows = np.zeros(len(pairs), dtype=[("w", "<u8"), ("out", "<u8"), ("rows", "<i4"), ("row_len", "<i4"), ("begin", "<i8")])
     begin = 0
     for i, (w, out) in enumerate(pairs):
@@ -408,7 +407,6 @@ def weight_planes_table(entries, device):
     """entries: [(w float32 [Cout,R,S,Cin], planes or None, planes_t or None[, w_absmax])] -> (device table, rows, total
     tiles) for weight_planes_batch: every piece-plane operand of a graph refreshed from the float masters by ONE launch.
     With w_absmax (the weight's magnitude block, filled before the launch) the row's planes are the two float16 pieces."""
-    import numpy as np
     rows = np.zeros(len(entries), dtype=[("w", "<u8"), ("planes", "<u8"), ("planes_t", "<u8"), ("K", "<i4"), ("T", "<i4"),
                                          ("C", "<i4"), ("cols_t", "<i4"), ("begin", "<i8"), ("absmax", "<u8"),
                                          ("npc", "<i4"), ("pad", "<i4")])
@@ -488,7 +486,6 @@ def weight_transpose_table(triples, device):
     """triples: [(w float32 [Cout,R,S,Cin], wt [Cin,R,S,Kp], wh or None)] -> (device table, rows, total tiles, bf16?)
     for weight_transpose_batch.  float32 operands: wt float32, wh None.  bfloat16 operands: wt bfloat16 and wh = the
     bfloat16 copy of w itself (the forward operand), both refreshed from the float32 master by the one launch."""
-    import numpy as np
     rows = np.zeros(len(triples), dtype=[("w", "<u8"), ("wt", "<u8"), ("K", "<i4"), ("T", "<i4"), ("C", "<i4"),
                                          ("Kp", "<i4"), ("begin", "<i8"), ("wh", "<u8")])
     total = 0
@@ -658,7 +655,6 @@ def conv2d_wgrad_slabs(x, dy, w_shape, slabs, stride=1, pad=0, dil=1, in_affine=
 
 def slab_reduce_table(entries, device):
     """entries: [(slabs (splits, ...), dw, accumulate)] -> (device table, rows, total float4)"""
-    import numpy as np
     rows = np.zeros(len(entries), dtype=[("slab", "<u8"), ("dw", "<u8"), ("n4", "<i8"), ("splits", "<i4"),
                                          ("acc", "<i4"), ("begin", "<i8")])
     total = 0
@@ -898,7 +894,6 @@ def nhwc_to_nchw(src, C=None, out=None):
 def copy_block_table(entries, device):
     """entries: [(src, dst, samples, rows_per_sample, C, src_sample_stride, lds, soff, dst_sample_stride, ldd, doff, accumulate)]
     (the arguments of copy_block, float32 tensors) -> (device table, rows, total elements) for copy_block_batch"""
-    import numpy as np
     rows = np.zeros(len(entries), dtype=[("src", "<u8"), ("dst", "<u8"), ("rps", "<i8"), ("sss", "<i8"), ("dss", "<i8"),
                                          ("C", "<i4"), ("lds", "<i4"), ("soff", "<i4"), ("ldd", "<i4"), ("doff", "<i4"),
                                          ("acc", "<i4"), ("begin", "<i8")])
@@ -1203,7 +1198,6 @@ SGD_MAX_SEGMENTS = 8192
 def sgd_segment_table(rows, numel, device):
     """rows: [(offset, length, lr_mult, wd_mult)] in floats, sorted, disjoint, multiples of 4, inside an arena of `numel`
     floats -> (device table, nseg, total4) for sgd_momentum_segments.  The rows are checked here: the kernel trusts them."""
-    import numpy as np
     if not 0 < len(rows) <= SGD_MAX_SEGMENTS:
         raise ValueError("sgd_segment_table: need 1 .. %d rows, got %d" % (SGD_MAX_SEGMENTS, len(rows)))
     tab = np.zeros(len(rows), dtype=SGD_SEGMENT_FIELDS)

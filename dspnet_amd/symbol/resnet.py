@@ -30,7 +30,7 @@ def residual_unit(g, data, num_filter, stride, dim_match, name, plus_name, bottl
     # act1/act2/act3 feed convolutions only: their BN-apply + ReLU runs inside those convolutions' loaders
     act1 = g.add(E.BatchNorm(g, data, name + "_bn1", relu=True, defer_apply=True)).out
     # conv1 is created before the projection shortcut so that its (dense, stride-1) data gradient is the last
-    # writer of act1's gradient in backward and can gather bn1's backward reductions (engine._plan_bn_backward_fusion)
+    # writer of act1's gradient in backward and can gather bn1's backward reductions (graph_plan.bn_backward_fusion)
     conv1 = g.add(E.Conv(g, act1, name + "_conv1", q, 1, 1, 0)).out
     shortcut = data if dim_match else g.add(E.Conv(g, act1, name + "_sc", num_filter, 1, stride, 0)).out
     # bf16 tensors: the 3x3 convolution would re-apply the folded BatchNorm+ReLU to every element once per tap (9x) on a

@@ -216,12 +216,10 @@ class MultiTaskSolver:
         self._rerecord = False
         self._replays, self.graph_rerecorded = 0, 0     # replays of the recorded step / recordings dropped by the range guard
         g = self.g
-        owner = {}
+        owner = {}                 # parameter -> the first node that holds it
         for idx, n in enumerate(g.nodes):
-            for v in vars(n).values():
-                if hasattr(v, "offset") and hasattr(v, "wd_mult"):
-                    owner.setdefault(v.name, idx)
-                    owner[v.name] = min(owner[v.name], idx)
+            for p in n.wiring.params:
+                owner.setdefault(p.name, idx)
         params = [(p.name, p.offset, (p.size + 3) // 4 * 4) for p in g.param_order]
         fixed = {p.name for p in g.param_order if p.fixed}
         self.buckets = plan_buckets(params, owner, g.arena.numel(), int(bucket_mb * (1 << 20) / 4), frozen=fixed or None)

@@ -1424,7 +1424,7 @@ def test_side_stream_detection_branch_gives_the_bits_of_the_main_stream_schedule
     each of several SGD steps must equal, bit for bit, those of the same graph built with the whole schedule on the main stream
     (DSPN_TARGET_SIDE = DSPN_DET_SIDE = 0), and a second run of the side-stream schedule must reproduce the first.
     Round 5: all three presets -- for vgg16_reduced / inceptionv3 the decoder reads a tensor written INSIDE the branch (conv_feat
-    is the first SSD extra layer), which the stream ordering derived in Graph._plan_side_sync has to cover (structure:
+    is the first SSD extra layer), which the stream ordering derived in graph_plan.side_sync has to cover (structure:
     tests/test_side_plan.py) -- and the steps are issued back to back, so that the host runs ahead of the device as it
     does in training."""
     import os

@@ -1,4 +1,4 @@
-"""Stream ordering of the side-stream detection branch, derived from the graph (engine.Graph._plan_side_sync): structural
+"""Stream ordering of the side-stream detection branch, derived from the graph (graph_plan.side_sync): structural
 checks for every preset, on CPU (no kernels run: MultiBoxPrior, the one operator a graph BUILD calls, is stubbed).
 
 The wiring differs between presets: for resnet-50 the decoder's `conv_feat` is a backbone map (symbol/
