@@ -1084,7 +1084,8 @@ __global__ void tap_spread_kernel_(const CA1Ptr dy, const A1Ptr dz, int H, int W
 
 // ------------------------------------------------------------------ pooling
 // optional argmax record: position r*k+s of the FIRST maximum of each window in (h, w) scan order, one
-// byte per element (255 = no finite maximum); the backward pass then needs neither x nor y
+// byte per element (255 = nothing in the window compared above -inf: only -inf / NaN); the backward pass then needs
+// neither x nor y.  NaN never wins a comparison, so it is skipped; a 255 window yields -inf and takes no gradient.
 // AFF (round 4): the pooled tensor is (relu)(x * scale[c] + shift[c]) -- a BatchNorm(+ReLU) folded into the pooling pass
 // (symbol/resnet.py:96-98: bn0 -> relu0 -> pooling0): the normalised 32 x 256 x 256 x 64 tensor (537 MB at the bench shape) is
 // neither written nor read back; same fmaf as every other evaluation of the affine, so the ReLU mask the BatchNorm backward
@@ -1194,7 +1195,10 @@ __global__ void maxpool_bwd_kernel(const CA4Ptr x, const CA4Ptr y,
       for (int wo = wo_lo; wo <= wo_hi; ++wo) {
         const long long oi = ((n * Ho + ho) * Wo + wo) * C4 + c4;
         const float4 yv = y[oi];
-        bool cand[4] = {yv.x == xv.x, yv.y == xv.y, yv.z == xv.z, yv.w == xv.w};
+        // y == -inf: the window held nothing above -inf (only -inf / NaN); the record says 255 and routes nothing, so neither
+        // does this form
+        bool cand[4] = {yv.x == xv.x && yv.x > -INFINITY, yv.y == xv.y && yv.y > -INFINITY,
+                        yv.z == xv.z && yv.z > -INFINITY, yv.w == xv.w && yv.w > -INFINITY};
         if (!(cand[0] | cand[1] | cand[2] | cand[3])) continue;
         // an earlier position of this window holding the same (max) value takes the gradient instead
         const int h0 = ho * stride - pad, w0 = wo * stride - pad;

@@ -191,15 +191,7 @@ def test_dgrad_epilogue_batchnorm_sums_bf16_tensors(gpu_device, case):
 # The HBM-bound kernels: each `*_bf16` twin runs the SAME fp32 arithmetic as its `*_f32` original on widened inputs and
 # rounds once on store.  On bf16-representable inputs therefore: a stored result == round_to_bf16(float result) bit
 # for bit, and a float result (statistics, column sums, probabilities) == the float kernel's, bit for bit.
-def _pair(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    h = (torch.randn(*shape, generator=g) * scale).to(BF).cuda()
-    return h, h.float()
-
-
-def _same_stored(h_out, f_out, what):
-    assert h_out.dtype == BF and f_out.dtype == torch.float32
-    assert torch.equal(h_out, f_out.to(BF)), f"{what}: bf16 kernel != round(float kernel), max diff {float((h_out.float() - f_out).abs().max()):.3e}"
+from bf16_twins import _pair, _same_stored  # noqa: E402  (shared with test_nn_edges_gpu.py)
 
 
 def test_batchnorm_kernels_bf16_twins(gpu_device):
@@ -243,7 +235,8 @@ def test_elementwise_pool_layout_kernels_bf16_twins(gpu_device):
     _same_stored(fn.avgpool_forward(ah, 2), fn.avgpool_forward(af, 2), "avgpool")
     _same_stored(fn.avgpool_backward(gh, ah.shape, 2), fn.avgpool_backward(gf, af.shape, 2), "avgpool_bwd")
     _same_stored(fn.avgpool2d_forward(ah, 3, 1, 1), fn.avgpool2d_forward(af, 3, 1, 1), "avgpool2d")
-    _same_stored(fn.avgpool2d_backward(ah, ah.shape, 3, 1, 1), fn.avgpool2d_backward(af, af.shape, 3, 1, 1), "avgpool2d_bwd")
+    g2h, g2f = _pair(tuple(ah.shape), 16)       # a gradient of its own (3/1/1 keeps the shape, the values are independent)
+    _same_stored(fn.avgpool2d_backward(g2h, ah.shape, 3, 1, 1), fn.avgpool2d_backward(g2f, af.shape, 3, 1, 1), "avgpool2d_bwd")
     # tap sum / spread
     zh, zf = _pair((2, 8, 8, 48), 7)
     bias = torch.randn(5).cuda()
