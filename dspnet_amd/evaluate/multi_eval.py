@@ -7,6 +7,7 @@ What the reference does per batch, and where it runs here:
   detections with id >= 0 and score > .1 (:329-335), MApMetric (:376-377)  -> host, a few hundred rows
   seg probabilities upsampled to 1024x2048 + argmax (:28-34, :355)         -> dspn_seg_upsample_argmax_f32 (fused)
   DistanceAccuracyMetric against the disparity maps (:379-384)             -> host, as in the reference
+  (offline, on the PNGs the script writes) Cityscapes IoU / iIoU           -> evaluate.cityscapes_eval (device counts)
 The image display / file writing of the script (cv2) is not part of the numerics contract and is not built."""
 import numpy as np
 import torch
@@ -53,16 +54,25 @@ def filter_detections(det, score_thresh=0.1):
 
 
 def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use_difficult=False,
-                 voc07_metric=False, full_res=None, score_thresh=0.1):
+                 voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False):
     """net: training graph (symbol.multitask_symbol_factory.get_multi_symbol_train); batches: iterable of dicts with
     'data' (B,3,H,W), 'label_det' (B,L,6), 'label_seg' (B,H/4,W/4) and optionally 'disparity' (B,hh,ww) host maps.
-    -> dict name -> value, plus 'class_maps' (list of uint8 device tensors) when full_res=(H, W) is given."""
+    -> dict name -> value, plus 'class_maps' (list of uint8 device tensors) when full_res=(H, W) is given.
+    cityscapes=True: every batch also carries 'gt_label_ids' (B, H, W) uint8 and 'gt_instance_ids' (B, H, W) int32, the
+    *_gtFine_labelIds / *_gtFine_instanceIds images at full resolution (full_res when that is given); the dict gains the
+    scores of the dataset's pixel-level evaluation script, 'cityscapes/IoU_class', 'cityscapes/iIoU_class',
+    'cityscapes/IoU_category', 'cityscapes/iIoU_category' and the per-class 'cityscapes/IoU/<name>' / 'cityscapes/iIoU/<name>'
+    (cityscapes_eval.CityscapesPixelMetric, fed from the probabilities without writing a class map)."""
     multibox_metric = MultiBoxMetric()
     acc_metric = CustomAccuracyMetric(num_classes=len(seg_class_names))
     depth_metric = DistanceAccuracyMetric(class_names=list(class_names))
     det_metric = (VOC07MApMetric if voc07_metric else MApMetric)(ovp_thresh, use_difficult, list(class_names))
     seg_metric = IoUMetric(class_names=list(seg_class_names), axis=1)
     class_maps = []
+    city_metric = None
+    if cityscapes:
+        from .cityscapes_eval import CityscapesPixelMetric
+        city_metric = CityscapesPixelMetric(device=net.seg_out.prob.data.device)
     for batch in batches:
         net.data.data.copy_(batch["data"])
         net.label_det.data.copy_(batch["label_det"])
@@ -77,6 +87,11 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
         det_metric.update([batch["label_det"][:, :, :5]], [pred_det[:, :, :6]])
         if full_res is not None:
             class_maps.append(prob_upsampling(seg_prob, full_res, len(seg_class_names)))
+        if city_metric is not None:
+            gt_ids = batch["gt_label_ids"]
+            if full_res is not None and tuple(gt_ids.shape[-2:]) != tuple(int(v) for v in full_res):
+                raise ValueError("evaluate_net: gt_label_ids are %s, full_res is %s" % (tuple(gt_ids.shape[-2:]), tuple(full_res)))
+            city_metric.update_from_prob(seg_prob, gt_ids, batch["gt_instance_ids"], num_classes=len(seg_class_names))
         if batch.get("disparity") is not None:
             depth_metric.update(batch["disparity"], list(pred_det[:, None]))
     out = {}
@@ -89,4 +104,6 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
         out.update(zip(names, values))
     if full_res is not None:
         out["class_maps"] = class_maps
+    if city_metric is not None:
+        out.update(city_metric.get_name_value())
     return out

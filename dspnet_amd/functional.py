@@ -82,6 +82,8 @@ _lib.register({
     "dspn_bilinear_backward_ws_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "dspn_seg_counts_f32": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     "dspn_seg_upsample_argmax_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "dspn_cityscapes_counts_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dspn_cityscapes_counts_prob_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dspn_tap_sum_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dspn_tap_spread_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dspn_maxpool_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -1132,6 +1134,49 @@ def seg_upsample_argmax(prob, C, Ho, Wo):
     check(L().dspn_seg_upsample_argmax_f32(ptr(prob), ptr(out), N, Hin, Win, C, ld, Ho, Wo, stream()),
           "seg_upsample_argmax")
     return out
+
+
+# include/dspn_nn.h DSPN_CITYSCAPES_*: labelIds of the confusion matrix, and the dense per-image instance table
+CITYSCAPES_LABELS, CITYSCAPES_INST_LABEL0, CITYSCAPES_INST_LABELS, CITYSCAPES_INST_PER_LABEL = 34, 24, 10, 1000
+
+
+def cityscapes_tables(n_images, device):
+    """zeroed outputs of the two count calls below: conf (34, 34) int64, inst (n_images, 10, 1000, 3) int32, errors (1,) int64"""
+    return (torch.zeros(CITYSCAPES_LABELS, CITYSCAPES_LABELS, dtype=torch.int64, device=device),
+            torch.zeros(n_images, CITYSCAPES_INST_LABELS, CITYSCAPES_INST_PER_LABEL, 3, dtype=torch.int32, device=device),
+            torch.zeros(1, dtype=torch.int64, device=device))
+
+
+def _cityscapes_args(N, H, W, gt_label, gt_inst, category, conf, inst, errors):
+    for t, dtype, shape in ((gt_label, torch.uint8, (N, H, W)), (gt_inst, torch.int32, (N, H, W)), (category, torch.uint8, (256,)),
+                            (conf, torch.int64, (CITYSCAPES_LABELS, CITYSCAPES_LABELS)),
+                            (inst, torch.int32, (N, CITYSCAPES_INST_LABELS, CITYSCAPES_INST_PER_LABEL, 3)),
+                            (errors, torch.int64, (1,))):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, shape)
+
+
+def cityscapes_counts(pred, gt_label, gt_inst, category, conf, inst, errors):
+    """conf / inst / errors (cityscapes_tables) += the Cityscapes evaluation counts of the labelId maps pred, gt_label
+    (N, H, W) uint8 and the instance-id map gt_inst (N, H, W) int32; category: (256,) uint8 labelId -> category number.
+    Nothing is allocated and nothing waits (include/dspn_nn.h dspn_cityscapes_counts_u8)."""
+    assert pred.dim() == 3 and pred.dtype == torch.uint8 and pred.is_contiguous()
+    N, H, W = pred.shape
+    _cityscapes_args(N, H, W, gt_label, gt_inst, category, conf, inst, errors)
+    check(L().dspn_cityscapes_counts_u8(ptr(pred), ptr(gt_label), ptr(gt_inst), N, H, W, ptr(category), ptr(conf), ptr(inst),
+                                        ptr(errors), stream()), "cityscapes_counts")
+
+
+def cityscapes_counts_prob(prob, C, label_of_train_id, gt_label, gt_inst, category, conf, inst, errors):
+    """the same from prob (N, Hin, Win, ld >= C) NHWC class probabilities: the prediction of a pixel of the ground truth's
+    (H, W) grid is label_of_train_id[seg_upsample_argmax's class], never written (dspn_cityscapes_counts_prob_f32)"""
+    assert prob.dim() == 4 and prob.is_contiguous() and prob.dtype == torch.float32 and gt_label.dim() == 3
+    N, Hin, Win, ld = prob.shape
+    H, W = gt_label.shape[1:]
+    _cityscapes_args(N, H, W, gt_label, gt_inst, category, conf, inst, errors)
+    assert label_of_train_id.dtype == torch.uint8 and label_of_train_id.numel() == 256 and label_of_train_id.is_contiguous()
+    check(L().dspn_cityscapes_counts_prob_f32(ptr(prob), N, Hin, Win, C, ld, ptr(label_of_train_id), ptr(gt_label), ptr(gt_inst),
+                                              H, W, ptr(category), ptr(conf), ptr(inst), ptr(errors), stream()),
+          "cityscapes_counts_prob")
 
 
 # ------------------------------------------------------------------ losses / optimizer

@@ -456,7 +456,7 @@ def do_checkpoint(prefix):
 
 def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None, epoch_end_callback=None,
         eval_data=None, class_names=None, seg_class_names=None, logger=None, eval_score_thresh=0.25,
-        check_label_errors=True):
+        check_label_errors=True, eval_cityscapes=False):
     """The epoch loop of MultiTaskSolver.fit (multi_solver.py:229-345 + the evaluation pass :353-436): per epoch
     train_data.reset(), metric reset, one solver.step() per batch with the MultiBoxMetric / CustomAccuracyMetric
     read-outs, batch_end_callback(BatchEndParam), epoch_end_callback(epoch, net), the 'Train-<name>' log lines, and
@@ -465,7 +465,9 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
     batch.data[0], batch.label[0], batch.label[1] device tensors).  -> list of per-epoch dicts of metric values.
     eval_score_thresh: the in-training evaluation keeps detections with score > .25 (multi_solver.py:428; multi_eval.py
     uses .1).  check_label_errors: after every step (at the metric read-out, which synchronises anyway) raise DspnError
-    where the reference's MultiBoxTarget would have CHECK-failed on the batch (multibox_target.cc:98-101, :236)."""
+    where the reference's MultiBoxTarget would have CHECK-failed on the batch (multibox_target.cc:98-101, :236).
+    eval_cityscapes: evaluate_net's `cityscapes` argument -- the evaluation batches then carry the full-resolution
+    ground truth as batch.gt_label_ids / batch.gt_instance_ids."""
     import logging
     from .metric import CustomAccuracyMetric, MultiBoxMetric
     logger = logger or logging
@@ -514,8 +516,12 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
                 eval_data.reset()
                 while eval_data.iter_next():
                     b, _ = eval_data.next()
-                    yield {"data": b.data[0], "label_det": b.label[0], "label_seg": b.label[1]}
-            ev = evaluate_net(net, batches(), class_names, seg_class_names, score_thresh=eval_score_thresh)
+                    d = {"data": b.data[0], "label_det": b.label[0], "label_seg": b.label[1]}
+                    if eval_cityscapes:
+                        d["gt_label_ids"], d["gt_instance_ids"] = b.gt_label_ids, b.gt_instance_ids
+                    yield d
+            ev = evaluate_net(net, batches(), class_names, seg_class_names, score_thresh=eval_score_thresh,
+                              cityscapes=eval_cityscapes)
             for k, v in ev.items():
                 if not isinstance(v, list):
                     logger.info("                     --->Epoch[%d] Validation-%s=%f", epoch, k, v)

@@ -594,6 +594,39 @@ int dspn_seg_counts_f32(const float *scores, const float *label, long long rows,
 int dspn_seg_upsample_argmax_f32(const float *prob, unsigned char *out, int N, int Hin, int Win, int C, int ld,
                                  int Ho, int Wo, void *stream);
 
+/* ---- Cityscapes pixel-level evaluation counts (data/cityscapes/Scripts/evaluation/evalPixelLevelSemanticLabeling.py,
+ * evaluatePair :583-635): everything the script's IoU / iIoU scores are computed from, counted in one pass over the
+ * pixels.  Both entry points ADD to the same caller-owned integer outputs (zero them once per evaluation; the order
+ * of the additions does not matter, no floating-point value is formed on the device):
+ *   conf    [L][L] unsigned 64-bit, L = DSPN_CITYSCAPES_LABELS (labelIds 0..33): conf[gt][pred] += 1;
+ *   inst    [N][DSPN_CITYSCAPES_INST_LABELS][DSPN_CITYSCAPES_INST_PER_LABEL][3] unsigned 32-bit -- a dense table with
+ *           one entry per possible ground-truth instance id of each of the call's N images: entry (n, l, k) belongs to
+ *           the instance gt_inst == (DSPN_CITYSCAPES_INST_LABEL0 + l) * 1000 + k of image n (only labelIds 24..33
+ *           have instances, k < 1000; a gt_inst value <= 1000 is no instance).  Its three counters:
+ *           [0] size = pixels of the instance, [1] tp = those predicted as the instance's labelId, [2] cat_tp = those
+ *           whose prediction p has category[p] == category[labelId] != 0.  Entries of instances that do not occur
+ *           stay as they were (size 0 in a zeroed table).  120 000 bytes per image; one image must hold fewer than
+ *           2^32 pixels, N <= 214 748, one call at most 2^40 pixels (a workgroup counts in 32 bits before it adds);
+ *   errors  one unsigned 64-bit word: += the pixels with gt_label >= L or prediction >= L (they are left out of
+ *           conf), or with gt_inst > 1000 whose labelId gt_inst / 1000 is outside 24..33 (left out of inst) -- the
+ *           inputs on which the script stops with an error.
+ * category: 256 bytes, labelId -> category number, 0 = a category without instance scores.
+ * pred, gt_label: (N, H, W) bytes (labelIds); gt_inst: (N, H, W) 32-bit ints as a 16-bit *_instanceIds.png holds them. */
+#define DSPN_CITYSCAPES_LABELS 34
+#define DSPN_CITYSCAPES_INST_LABEL0 24
+#define DSPN_CITYSCAPES_INST_LABELS 10
+#define DSPN_CITYSCAPES_INST_PER_LABEL 1000
+int dspn_cityscapes_counts_u8(const unsigned char *pred, const unsigned char *gt_label, const int *gt_inst, int N, int H,
+                              int W, const unsigned char *category, unsigned long long *conf, unsigned int *inst,
+                              unsigned long long *errors, void *stream);
+/* The same counts from the class probabilities, fused: the prediction of pixel (n, ho, wo) is
+ * label_of_train_id[the class dspn_seg_upsample_argmax_f32 gives it] (prob, Hin, Win, C, ld, Ho, Wo as there;
+ * label_of_train_id: 256 bytes); the (N, Ho, Wo) class map is never written.  gt_label / gt_inst are (N, Ho, Wo). */
+int dspn_cityscapes_counts_prob_f32(const float *prob, int N, int Hin, int Win, int C, int ld,
+                                    const unsigned char *label_of_train_id, const unsigned char *gt_label,
+                                    const int *gt_inst, int Ho, int Wo, const unsigned char *category,
+                                    unsigned long long *conf, unsigned int *inst, unsigned long long *errors, void *stream);
+
 /* SoftmaxOutput(multi_output, use_ignore) over the last (channel) axis of logits (rows, ld):
  * prob (rows, ld) = softmax over the first C channels (pad channels -> 0);
  * grad (rows, ld) = (prob - onehot(label)) * scale, 0 for rows whose label == ignore_label.
