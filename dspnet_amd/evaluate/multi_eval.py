@@ -6,7 +6,8 @@ What the reference does per batch, and where it runs here:
   CustomAccuracyMetric + IoUMetric over seg_out (:375, :378)               -> dspn_seg_counts_f32 (device counts)
   detections with id >= 0 and score > .1 (:329-335), MApMetric (:376-377)  -> host, a few hundred rows
   seg probabilities upsampled to 1024x2048 + argmax (:28-34, :355)         -> dspn_seg_upsample_argmax_f32 (fused)
-  DistanceAccuracyMetric against the disparity maps (:379-384)             -> host, as in the reference
+  DistanceAccuracyMetric against the disparity maps (:379-384)             -> host, as in the reference; with
+      device_depth=True the box medians come from the device (evaluate.distance_eval, dspn_box_rank_select_*)
   (offline, on the PNGs the script writes) Cityscapes IoU / iIoU           -> evaluate.cityscapes_eval (device counts)
 The image display / file writing of the script (cv2) is not part of the numerics contract and is not built."""
 import numpy as np
@@ -54,7 +55,7 @@ def filter_detections(det, score_thresh=0.1):
 
 
 def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use_difficult=False,
-                 voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False):
+                 voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False, device_depth=False):
     """net: training graph (symbol.multitask_symbol_factory.get_multi_symbol_train); batches: iterable of dicts with
     'data' (B,3,H,W), 'label_det' (B,L,6), 'label_seg' (B,H/4,W/4) and optionally 'disparity' (B,hh,ww) host maps.
     -> dict name -> value, plus 'class_maps' (list of uint8 device tensors) when full_res=(H, W) is given.
@@ -62,10 +63,18 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
     *_gtFine_labelIds / *_gtFine_instanceIds images at full resolution (full_res when that is given); the dict gains the
     scores of the dataset's pixel-level evaluation script, 'cityscapes/IoU_class', 'cityscapes/iIoU_class',
     'cityscapes/IoU_category', 'cityscapes/iIoU_category' and the per-class 'cityscapes/IoU/<name>' / 'cityscapes/iIoU/<name>'
-    (cityscapes_eval.CityscapesPixelMetric, fed from the probabilities without writing a class map)."""
+    (cityscapes_eval.CityscapesPixelMetric, fed from the probabilities without writing a class map).
+    device_depth=True: the distance metric reads the device's unfiltered detections and takes every box median on the
+    device (distance_eval.DeviceDistanceAccuracyMetric; 'disparity' may then be a device tensor, uint16 or float32);
+    the box table is sized from det_out, B * N rows, so no batch the host path scores can overflow it; the values are
+    those of the host metric, which stays the default."""
     multibox_metric = MultiBoxMetric()
     acc_metric = CustomAccuracyMetric(num_classes=len(seg_class_names))
-    depth_metric = DistanceAccuracyMetric(class_names=list(class_names))
+    if device_depth:
+        from .distance_eval import DeviceDistanceAccuracyMetric
+        depth_metric = DeviceDistanceAccuracyMetric(class_names=list(class_names), device=net.det.out.data.device)
+    else:
+        depth_metric = DistanceAccuracyMetric(class_names=list(class_names))
     det_metric = (VOC07MApMetric if voc07_metric else MApMetric)(ovp_thresh, use_difficult, list(class_names))
     seg_metric = IoUMetric(class_names=list(seg_class_names), axis=1)
     class_maps = []
@@ -93,7 +102,10 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
                 raise ValueError("evaluate_net: gt_label_ids are %s, full_res is %s" % (tuple(gt_ids.shape[-2:]), tuple(full_res)))
             city_metric.update_from_prob(seg_prob, gt_ids, batch["gt_instance_ids"], num_classes=len(seg_class_names))
         if batch.get("disparity") is not None:
-            depth_metric.update(batch["disparity"], list(pred_det[:, None]))
+            if device_depth:
+                depth_metric.update_filtered(batch["disparity"], net.det.out.data, score_thresh)
+            else:
+                depth_metric.update(batch["disparity"], list(pred_det[:, None]))
     out = {}
     names, values = multibox_metric.get()
     out.update(zip(names, values))

@@ -135,6 +135,13 @@ _lib.register({
     "dspn_copy_block_bf16_f32": _lib.SIGNATURES["dspn_copy_block_f32"],
     "dspn_copy_block_f32_bf16": _lib.SIGNATURES["dspn_copy_block_f32"],
 })
+# include/dspn_distance.h
+_lib.register({
+    "dspn_box_rank_select_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dspn_box_rank_select_u16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dspn_distance_boxes_workspace_bytes": (_sz, [_i]),
+    "dspn_distance_boxes_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+})
 
 
 class BnMoving(_c.Structure):
@@ -1177,6 +1184,56 @@ def cityscapes_counts_prob(prob, C, label_of_train_id, gt_label, gt_inst, catego
     check(L().dspn_cityscapes_counts_prob_f32(ptr(prob), N, Hin, Win, C, ld, ptr(label_of_train_id), ptr(gt_label), ptr(gt_inst),
                                               H, W, ptr(category), ptr(conf), ptr(inst), ptr(errors), stream()),
           "cityscapes_counts_prob")
+
+
+def slice_bounds(start, stop, size):
+    """the numpy slice [start:stop] of an axis of `size` elements -> (lo, hi), hi == lo when it is empty: a bound beyond
+    the size is clipped, a negative one counts from the end (the form dspn_box_rank_select_* takes its boxes in)"""
+    start, stop, size = int(start), int(stop), int(size)
+    lo = min(max(start + size if start < 0 else start, 0), size)
+    hi = min(max(stop + size if stop < 0 else stop, 0), size)
+    return lo, max(lo, hi)
+
+
+def box_rank_select(image, boxes, count=None, out=None):
+    """image (B, hh, ww) uint16 or float32 device maps, boxes (K, 5) int32 [image index, x0, x1, y0, y1] (slice_bounds form)
+    -> (q (K,) float32, n (K,) int32): n pixels in image[index, y0:y1, x0:x1], q the element of rank n // 2 of their ascending
+    float32 values (np.sort order); n == 0 gives q == 0.  count: optional device int32 (1,), rows k >= count are not touched."""
+    assert image.dim() == 3 and image.is_contiguous() and image.dtype in (torch.uint16, torch.float32), (image.dtype, image.shape)
+    assert boxes.dim() == 2 and boxes.shape[1] == 5 and boxes.dtype == torch.int32 and boxes.is_contiguous()
+    B, hh, ww = image.shape
+    K = boxes.shape[0]
+    q, n = out if out is not None else (torch.zeros(K, dtype=torch.float32, device=image.device),
+                                        torch.zeros(K, dtype=torch.int32, device=image.device))
+    assert q.numel() >= K and n.numel() >= K and q.dtype == torch.float32 and n.dtype == torch.int32
+    call = L().dspn_box_rank_select_u16 if image.dtype == torch.uint16 else L().dspn_box_rank_select_f32
+    check(call(ptr(image), B, hh, ww, ptr(boxes), K, ptr(count), ptr(q), ptr(n), stream()), "box_rank_select")
+    return q, n
+
+
+def distance_boxes(det, hh, ww, score_thresh, mode, max_boxes, out=None, sync=True):
+    """det (B, N, 7) float32 device detections -> (boxes (max_boxes, 5) int32, src (max_boxes,) int32, count (1,) int32):
+    the pixel boxes (slice_bounds form) of the rows that DistanceAccuracyMetric walks, in its order, and image * N + row of
+    each.  mode 0: the rows of an image before its first id < 0; mode 1: id >= 0 and score > score_thresh.
+    sync=True reads the count back and raises DspnError when it exceeds max_boxes (never a truncated table); with
+    sync=False nothing waits (graph capture) and the caller checks count itself."""
+    assert det.dim() == 3 and det.shape[2] == 7 and det.dtype == torch.float32 and det.is_contiguous(), (det.dtype, det.shape)
+    B, N = det.shape[:2]
+    boxes, src, count = out if out is not None else (torch.zeros(max_boxes, 5, dtype=torch.int32, device=det.device),
+                                                     torch.zeros(max_boxes, dtype=torch.int32, device=det.device),
+                                                     torch.zeros(1, dtype=torch.int32, device=det.device))
+    assert boxes.numel() >= 5 * max_boxes and src.numel() >= max_boxes
+    ws = _scratch(L().dspn_distance_boxes_workspace_bytes(B), det.device)
+    check(L().dspn_distance_boxes_f32(ptr(det), B, N, int(hh), int(ww), float(score_thresh), int(mode), int(max_boxes),
+                                      ptr(boxes), ptr(src), ptr(count), ptr(ws), ws.numel(), stream()), "distance_boxes")
+    if sync:
+        check_box_count(int(count.item()), max_boxes)
+    return boxes, src, count
+
+
+def check_box_count(count, max_boxes):
+    if count > max_boxes:
+        raise _lib.DspnError("distance_boxes: %d rows selected, room for max_boxes = %d" % (count, max_boxes))
 
 
 # ------------------------------------------------------------------ losses / optimizer

@@ -456,7 +456,7 @@ def do_checkpoint(prefix):
 
 def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None, epoch_end_callback=None,
         eval_data=None, class_names=None, seg_class_names=None, logger=None, eval_score_thresh=0.25,
-        check_label_errors=True, eval_cityscapes=False):
+        check_label_errors=True, eval_cityscapes=False, eval_device_depth=False):
     """The epoch loop of MultiTaskSolver.fit (multi_solver.py:229-345 + the evaluation pass :353-436): per epoch
     train_data.reset(), metric reset, one solver.step() per batch with the MultiBoxMetric / CustomAccuracyMetric
     read-outs, batch_end_callback(BatchEndParam), epoch_end_callback(epoch, net), the 'Train-<name>' log lines, and
@@ -467,7 +467,11 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
     uses .1).  check_label_errors: after every step (at the metric read-out, which synchronises anyway) raise DspnError
     where the reference's MultiBoxTarget would have CHECK-failed on the batch (multibox_target.cc:98-101, :236).
     eval_cityscapes: evaluate_net's `cityscapes` argument -- the evaluation batches then carry the full-resolution
-    ground truth as batch.gt_label_ids / batch.gt_instance_ids."""
+    ground truth as batch.gt_label_ids / batch.gt_instance_ids.
+    An evaluation batch may carry its disparity maps as batch.disparity ((B, hh, ww), uint16 or float32, host array or
+    device tensor): they go to evaluate_net as 'disparity' and the distance metric ('derror', per-class errors) is scored;
+    a batch without the attribute leaves it out, as before.  eval_device_depth: evaluate_net's `device_depth` argument
+    (the box medians of that metric taken on the device; the values are the host metric's)."""
     import logging
     from .metric import CustomAccuracyMetric, MultiBoxMetric
     logger = logger or logging
@@ -519,9 +523,11 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
                     d = {"data": b.data[0], "label_det": b.label[0], "label_seg": b.label[1]}
                     if eval_cityscapes:
                         d["gt_label_ids"], d["gt_instance_ids"] = b.gt_label_ids, b.gt_instance_ids
+                    if getattr(b, "disparity", None) is not None:      # a batch that carries its disparity maps
+                        d["disparity"] = b.disparity
                     yield d
             ev = evaluate_net(net, batches(), class_names, seg_class_names, score_thresh=eval_score_thresh,
-                              cityscapes=eval_cityscapes)
+                              cityscapes=eval_cityscapes, device_depth=eval_device_depth)
             for k, v in ev.items():
                 if not isinstance(v, list):
                     logger.info("                     --->Epoch[%d] Validation-%s=%f", epoch, k, v)
