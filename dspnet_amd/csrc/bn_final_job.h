@@ -3,12 +3,14 @@
 // rides in the next weight-gradient launch on the same stream instead of a launch of its own (bn_bwd_final_kernel: 1 - 32
 // workgroups, 6 - 9 us during which the chip idles, 58 of them per training step).
 //
-// dspn_bn_backward_from_sums(flag | 2 | 8) launches tile_group_kernel<1> where the table is long (>= 1024 row tiles: that level
-// needs hundreds of workgroups and stays a launch), fills a BnFinalJob for the rest and parks it (bn_job_defer); conv2d_wgrad_one takes it
+// A BnFinalJob is THE description of a finalize: every BatchNorm backward entry point of nn.hip fills one (bn_final_job) and
+// either launches bn_bwd_final_kernel from it (bn_final_launch) or parks it.  dspn_bn_backward_from_sums with
+// DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_PARKED launches tile_group_kernel<1> where the table is long (>= 1024 row tiles: that
+// level needs hundreds of workgroups and stays a launch) and parks the job for the rest (bn_job_defer); conv2d_wgrad_one takes it
 // (bn_job_take) and adds rows of workgroups IN FRONT of its grid (blockIdx.y < job_rows: dispatched first) that run
 // bn_final_job_run -- sixteen channels per workgroup, beside the weight gradient's own workgroups; the apply half
-// (flag | 4) is launched behind that kernel by stream order.  If no weight gradient came by, the apply call launches the
-// stand-alone form itself.  The sums are formed in bn_bwd_final_kernel's ORDER (sixteen double accumulators over the table rows,
+// (DSPN_BN_SUMS_APPLY_ONLY) is launched behind that kernel by stream order.  If no weight gradient came by, the apply call launches
+// the stand-alone form itself.  The sums are formed in bn_bwd_final_kernel's ORDER (sixteen double accumulators over the table rows,
 // then 1 .. 15 onto 0): same bits.  (The first form of the job also summed the groups of a long table itself, sixteen channels per
 // workgroup: 500 dependent loads per thread made it the LONGEST workgroup of a stage-1 weight gradient and its registers spilled
 // the 128-register kernels -- the step lost 3.6 %.)
@@ -21,7 +23,7 @@ constexpr int kBnJobChannels = 16;     // channels per job workgroup
 
 struct BnFinalJob {
   const float *tile_sums;              // [tiles][2][C]
-  int tiles, C, blocks;                // blocks = ceil(C / 16) workgroups
+  int tiles, C, blocks;                // blocks = ceil(C / 16) workgroups of the job form
   double inv_rows;
   const float *mean, *rstd, *gamma;
   float *coef, *dgamma, *dbeta;

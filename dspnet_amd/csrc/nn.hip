@@ -1950,8 +1950,7 @@ int bn_slabs(long long rows) { const int sr = slab_rows_for(rows); return (int)(
 
 #define S_(x) ((hipStream_t)(x))
 
-extern "C" {
-
+// ------------------------------------------------------------------ BatchNorm host side: one owner per launch
 static size_t bn_workspace_bytes(long long rows, int C) {
   if (rows <= 0 || C <= 0) return 0;
   return sizeof(float) * ((size_t)bn_slabs(rows) * 2 * C + 4 * (size_t)C);
@@ -1960,13 +1959,78 @@ static size_t bn_tiles_workspace_bytes(int tiles, int C) {
   if (tiles <= 0 || C <= 0) return 0;
   return sizeof(float) * 4 * (size_t)((tiles + kTileGroup - 1) / kTileGroup) * C;     // grouped statistics + grouped (min, max)
 }
+
+static const BnMovingK kNoMoving{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0};     // mode 0: no moving statistics
+
+// A per-tile table [tiles][2][C] -- (mean, M2) of `rows` rows in tiles of tile_rows, or plain sums (tile_rows 1, rows = tiles)
+// -- and the optional (min, max) table of the same tiles
+struct BnTiles { const float *table; int tiles, tile_rows; long long rows; const float *mm; };
+// Groups a long table into `scratch` (tile_group_kernel<MODE>) and re-points t at the result.  Only where the table is long AND
+// the scratch holds the result: grouped sums have other bits, so a caller keeps its results by keeping its workspace size
+template <int MODE>
+static void bn_group_tiles(hipStream_t s, BnTiles &t, int C, void *scratch, size_t scratch_bytes) {
+  if (t.tiles < tile_group_min() || !scratch || scratch_bytes < bn_tiles_workspace_bytes(t.tiles, C)) return;
+  const int groups = (t.tiles + kTileGroup - 1) / kTileGroup;
+  float *grouped = static_cast<float *>(scratch);
+  float *grouped_mm = t.mm ? grouped + 2 * (size_t)groups * C : nullptr;
+  hipLaunchKernelGGL(tile_group_kernel<MODE>, dim3(groups, (C + 63) / 64), dim3(256), 0, s, t.table, t.tiles, t.tile_rows, t.rows, C,
+                     grouped, t.mm, grouped_mm);
+  t = BnTiles{grouped, groups, t.tile_rows * kTileGroup, t.rows, grouped_mm};
+}
+
+// The finalize of a BatchNorm backward over a table of sums, described once (bn_final_job.h): launched by bn_final_launch or
+// parked as it is.  The last four (piece planes only): what the bound of dx is formed from and where it goes
+static dspn::BnFinalJob bn_final_job(const float *table, int tiles, int C, long long rows, const float *mean, const float *rstd,
+                                     const float *gamma, float *coef, float *dgamma, float *dbeta, const float *dy_absmax = nullptr,
+                                     const float *x_minmax = nullptr, float *dx_bound = nullptr, float *dx_bound_min = nullptr) {
+  dspn::BnFinalJob j;
+  j.tile_sums = table; j.tiles = tiles; j.C = C;
+  j.blocks = (C + dspn::kBnJobChannels - 1) / dspn::kBnJobChannels;
+  j.inv_rows = 1.0 / (double)rows; j.mean = mean; j.rstd = rstd; j.gamma = gamma; j.coef = coef; j.dgamma = dgamma; j.dbeta = dbeta;
+  j.dy_absmax = dy_absmax; j.x_minmax = x_minmax;
+  j.dx_bound = reinterpret_cast<unsigned *>(dx_bound); j.dx_bound_min = reinterpret_cast<unsigned *>(dx_bound_min);
+  return j;
+}
+static void bn_final_launch(hipStream_t s, const dspn::BnFinalJob &j) {
+  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((j.C + 63) / 64), dim3(1024), 0, s, j.tile_sums, j.tiles, j.C, j.inv_rows, j.mean,
+                     j.rstd, j.gamma, j.coef, j.dgamma, j.dbeta, j.dy_absmax, j.x_minmax, j.dx_bound, j.dx_bound_min);
+}
+
+// The apply pass dx (+)= a dy' + c1 x + c0 from the finalize's coefficients.  what: the entry point's name for the error text
+static int bn_bwd_apply_launch(hipStream_t s, const st_t *x, const float *scale, const float *shift, const st_t *dy,
+                               const float *coef, st_t *dx, long long rows, int C, int relu, int accumulate, float *dx_absmax,
+                               const char *what) {
+  const int C4 = C / 4;
+  const long long n4 = rows * C4;
+  int fixed = 0, u4 = 0;
+#ifdef DSPN_HALF
+  if (C % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
+    const int grid8 = grid_fixed_channel(n4 / 2, C / 8, &fixed, &u4);
+    hipLaunchKernelGGL(u4 ? bn_bwd_apply8_kernel<4> : bn_bwd_apply8_kernel<1>, dim3(grid8), dim3(kT), 0, s,
+                       reinterpret_cast<const dspn::u32x4_t *>(x), reinterpret_cast<const float4 *>(scale),
+                       reinterpret_cast<const float4 *>(shift), reinterpret_cast<const dspn::u32x4_t *>(dy),
+                       reinterpret_cast<const float4 *>(coef), reinterpret_cast<dspn::u32x4_t *>(dx), n4 / 2, C / 8, relu,
+                       accumulate, fixed);
+    return dspn::check_launch(what);
+  }
+#endif
+  const int grid4 = grid_fixed_channel(n4, C4, &fixed, &u4);
+  hipLaunchKernelGGL(u4 ? bn_bwd_apply_kernel<4> : bn_bwd_apply_kernel<1>, dim3(grid4), dim3(kT), 0, s, CA4Ptr(x),
+                     reinterpret_cast<const float4 *>(scale), reinterpret_cast<const float4 *>(shift), CA4Ptr(dy),
+                     reinterpret_cast<const float4 *>(coef), A4Ptr(dx), n4, C4, relu, accumulate,
+                     dspn::kHalf ? nullptr : reinterpret_cast<unsigned *>(dx_absmax), fixed);
+  return dspn::check_launch(what);
+}
+
+extern "C" {
+
 #ifndef DSPN_HALF
 size_t dspn_bn_workspace_bytes(long long rows, int C) { return bn_workspace_bytes(rows, C); }
 #endif
 
 // the dspn_bn_moving block of an `_ex` call -> the kernels' by-value form (mode 0 for NULL), checked before any HIP call
 static int bn_moving_arg(const dspn_bn_moving *mv, long long rows, int C, const char *what, BnMovingK *out) {
-  *out = BnMovingK{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0};
+  *out = kNoMoving;
   if (!mv) return 0;
   DSPN_REQUIRE(mv->moving_mean && mv->moving_var, "%s: moving_mean and moving_var must not be NULL", what);
   DSPN_REQUIRE(mv->momentum >= 0.f && mv->momentum <= 1.f, "%s: momentum must be in [0, 1]", what);
@@ -2003,7 +2067,7 @@ int DSPN_FN(dspn_bn_stats)(const st_t *x, long long rows, int C, float eps, cons
                       const float *beta, float *mean, float *rstd, float *scale, float *shift,
                       void *workspace, size_t workspace_bytes, void *stream) {
   return bn_stats_run(x, rows, C, eps, gamma, beta, mean, rstd, scale, shift, workspace, workspace_bytes,
-                      BnMovingK{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0}, stream);
+                      kNoMoving, stream);
 }
 
 int DSPN_FN(dspn_bn_stats_ex)(const st_t *x, long long rows, int C, float eps, const float *gamma,
@@ -2027,18 +2091,11 @@ static int bn_stats_from_tiles_run(const float *tile_stats, int tiles, int tile_
                    rows > (long long)(tiles - 1) * tile_rows && rows <= (long long)tiles * tile_rows,
                "bn_stats_from_tiles: bad argument");
   DSPN_REQUIRE((tile_minmax != nullptr) == (out_absmax != nullptr), "bn_stats_from_tiles: tile_minmax and out_absmax go together");
-  int mm_tiles = tiles;
-  if (tiles >= tile_group_min() && workspace && workspace_bytes >= bn_tiles_workspace_bytes(tiles, C)) {
-    const int groups = (tiles + kTileGroup - 1) / kTileGroup;
-    float *grouped = static_cast<float *>(workspace);
-    float *grouped_mm = tile_minmax ? grouped + 2 * (size_t)groups * C : nullptr;
-    hipLaunchKernelGGL(tile_group_kernel<0>, dim3(groups, (C + 63) / 64), dim3(256), 0, S_(stream), tile_stats, tiles,
-                       tile_rows, rows, C, grouped, tile_minmax, grouped_mm);
-    tile_stats = grouped; tiles = groups; tile_rows *= kTileGroup;
-    if (tile_minmax) { tile_minmax = grouped_mm; mm_tiles = groups; }
-  }
-  hipLaunchKernelGGL(bn_stats_tiles_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, S_(stream), tile_stats,
-                     mv.mode == DSPN_BN_GLOBAL ? 0 : tiles, tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, tile_minmax, mm_tiles, relu,
+  BnTiles t{tile_stats, tiles, tile_rows, rows, tile_minmax};
+  bn_group_tiles<0>(S_(stream), t, C, workspace, workspace_bytes);
+  // (t.tiles twice: the statistics table, not read in DSPN_BN_GLOBAL, and the (min, max) table are grouped together)
+  hipLaunchKernelGGL(bn_stats_tiles_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, S_(stream), t.table,
+                     mv.mode == DSPN_BN_GLOBAL ? 0 : t.tiles, t.tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, t.mm, t.tiles, relu,
                      reinterpret_cast<unsigned *>(out_absmax), reinterpret_cast<unsigned *>(tile_minmax ? out_absmin : nullptr),
                      tile_minmax ? out_chan_minmax : nullptr, mv);
   return dspn::check_launch("bn_stats_from_tiles");
@@ -2049,7 +2106,7 @@ int dspn_bn_stats_from_tiles_f32(const float *tile_stats, int tiles, int tile_ro
                                  float *out_chan_minmax, void *workspace, size_t workspace_bytes, void *stream) {
   return bn_stats_from_tiles_run(tile_stats, tiles, tile_rows, rows, C, eps, gamma, beta, mean, rstd, scale, shift, tile_minmax,
                                  relu, out_absmax, out_absmin, out_chan_minmax, workspace, workspace_bytes,
-                                 BnMovingK{nullptr, nullptr, 0.0, 0.0, 1.0, 0, 0}, stream);
+                                 kNoMoving, stream);
 }
 int dspn_bn_stats_from_tiles_ex_f32(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
                                     const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
@@ -2108,31 +2165,9 @@ int DSPN_FN(dspn_bn_backward)(const st_t *x, const float *scale, const float *sh
                      sizeof(float4) * 2 * kT, S_(stream), CA4Ptr(x),
                      reinterpret_cast<const float4 *>(scale), reinterpret_cast<const float4 *>(shift),
                      CA4Ptr(dy), mean, rstd, rows, C4, CL, relu, partial, slab_rows_for(rows), PoolGrad{});
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(1024), 0, S_(stream), partial, ns, C,
-                     1.0 / (double)rows, mean, rstd, gamma, coef, dgamma, dbeta, nullptr, nullptr, nullptr,
-                     static_cast<unsigned *>(nullptr));
+  bn_final_launch(S_(stream), bn_final_job(partial, ns, C, rows, mean, rstd, gamma, coef, dgamma, dbeta));
   if (!dx) return dspn::check_launch("bn_backward (parameters only)");     // dx == NULL: the reductions and the finalize alone
-  const long long n4 = rows * C4;
-#ifdef DSPN_HALF
-  if (C % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
-    int fixed8 = 0, u4 = 0;
-    const int grid8 = grid_fixed_channel(n4 / 2, C / 8, &fixed8, &u4);
-    hipLaunchKernelGGL(u4 ? bn_bwd_apply8_kernel<4> : bn_bwd_apply8_kernel<1>, dim3(grid8), dim3(kT), 0, S_(stream),
-                       reinterpret_cast<const dspn::u32x4_t *>(x), reinterpret_cast<const float4 *>(scale),
-                       reinterpret_cast<const float4 *>(shift), reinterpret_cast<const dspn::u32x4_t *>(dy),
-                       reinterpret_cast<const float4 *>(coef), reinterpret_cast<dspn::u32x4_t *>(dx), n4 / 2, C / 8, relu,
-                       accumulate, fixed8);
-    return dspn::check_launch("bn_backward");
-  }
-#endif
-  int fixed4 = 0, u4 = 0;
-  const int grid4 = grid_fixed_channel(n4, C4, &fixed4, &u4);
-  hipLaunchKernelGGL(u4 ? bn_bwd_apply_kernel<4> : bn_bwd_apply_kernel<1>, dim3(grid4), dim3(kT), 0, S_(stream),
-                     CA4Ptr(x), reinterpret_cast<const float4 *>(scale),
-                     reinterpret_cast<const float4 *>(shift), CA4Ptr(dy),
-                     reinterpret_cast<const float4 *>(coef), A4Ptr(dx), n4, C4, relu,
-                     accumulate, dspn::kHalf ? nullptr : reinterpret_cast<unsigned *>(dx_absmax), fixed4);
-  return dspn::check_launch("bn_backward");
+  return bn_bwd_apply_launch(S_(stream), x, scale, shift, dy, coef, dx, rows, C, relu, accumulate, dx_absmax, "bn_backward");
 }
 
 #ifndef DSPN_HALF
@@ -2155,9 +2190,7 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
   hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3(ns, (C4 + CL - 1) / CL), dim3(kT), sizeof(float4) * 2 * kT, S_(stream),
                      CA4Ptr(x), reinterpret_cast<const float4 *>(scale), reinterpret_cast<const float4 *>(shift),
                      CA4Ptr(x), mean, rstd, rows, C4, CL, relu, partial, slab_rows_for(rows), pool);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(1024), 0, S_(stream), partial, ns, C,
-                     1.0 / (double)rows, mean, rstd, gamma, coef, dgamma, dbeta, nullptr, nullptr, nullptr,
-                     static_cast<unsigned *>(nullptr));
+  bn_final_launch(S_(stream), bn_final_job(partial, ns, C, rows, mean, rstd, gamma, coef, dgamma, dbeta));
   if (!dx) return dspn::check_launch("bn_backward_maxpool (parameters only)");
   const long long n4 = rows * C4;
   hipLaunchKernelGGL(bn_bwd_apply_pool_kernel, dim3(grid_for(n4)), dim3(256), 0, S_(stream), reinterpret_cast<const float4 *>(x),
@@ -2190,67 +2223,47 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
                                    const float *mean, const float *rstd, const float *gamma, const float *tile_sums,
                                    int tiles, st_t *dx, float *dgamma, float *dbeta, long long rows, int C, int relu,
                                    int accumulate, float *dx_absmax, float *dx_absmin, const float *dy_absmax, const float *x_chan_minmax,
-                                   int dx_planes_phase, void *workspace, size_t workspace_bytes, void *stream) {
-  // round 6: bits 1 / 2 of the flag word split the call in two -- 2 = the finalize alone (the per-channel coefficients into the
-  // workspace, dgamma / dbeta, the bound of dx), 4 = the apply pass alone from the coefficients an earlier call with bit 2 left
-  // in the SAME workspace -- so that a caller can run the latency-bound finalize on a second stream beside a weight gradient
-  // | 8 (with | 2): the finalize is PARKED as a job for the next weight-gradient launch on this stream (bn_final_job.h); the
-  // apply-only call runs it stand-alone if no weight gradient took it
-  const int dx_planes = dx_planes_phase & 1, phase = (dx_planes_phase >> 1) & 3, defer = (dx_planes_phase >> 3) & 1;
-  DSPN_REQUIRE(dx_planes_phase >= 0 && dx_planes_phase < 16 && phase <= 2 && (!defer || phase == 1),
+                                   int flags, void *workspace, size_t workspace_bytes, void *stream) {
+  // the flag word (DSPN_BN_SUMS_*, include/dspn_nn.h): dx as piece planes; which half of the call runs (0: both); parked
+  const int planes = flags & DSPN_BN_SUMS_PLANES, half = flags & (DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY),
+            parked = flags & DSPN_BN_SUMS_PARKED;
+  DSPN_REQUIRE((flags & ~(DSPN_BN_SUMS_PLANES | DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY | DSPN_BN_SUMS_PARKED)) == 0 &&
+                   half != (DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY) && (!parked || half == DSPN_BN_SUMS_FINALIZE_ONLY),
                "bn_backward_from_sums: flag word = dx_planes | 2 (finalize only, | 8: parked for the next weight gradient) | 4 (apply only)");
   DSPN_REQUIRE(x && dy && mean && rstd && workspace && tile_sums && tiles > 0, "bn_backward_from_sums: null pointer");
-  // dx == NULL (parameters only): the finalize alone, i.e. flag word 2 -- no apply half follows
-  DSPN_REQUIRE(dx || dx_planes_phase == 2, "bn_backward_from_sums: dx == NULL needs the finalize-only flag word 2");
-  DSPN_REQUIRE(!dx_planes || (!dspn::kHalf && !accumulate && C % 32 == 0 && dx_absmax && dy_absmax && x_chan_minmax &&
-                              static_cast<const void *>(dx) != static_cast<const void *>(dy) && static_cast<const void *>(dx) != static_cast<const void *>(x)),
+  // dx == NULL (parameters only): the finalize alone, nothing parked -- no apply half follows
+  DSPN_REQUIRE(dx || flags == DSPN_BN_SUMS_FINALIZE_ONLY, "bn_backward_from_sums: dx == NULL needs the finalize-only flag word 2");
+  DSPN_REQUIRE(!planes || (!dspn::kHalf && !accumulate && C % 32 == 0 && dx_absmax && dy_absmax && x_chan_minmax &&
+                           static_cast<const void *>(dx) != static_cast<const void *>(dy) && static_cast<const void *>(dx) != static_cast<const void *>(x)),
                "bn_backward_from_sums: dx as piece planes needs float tensors, C %% 32 == 0, no accumulation, dx apart from x and dy, "
                "and dx_absmax / dy_absmax / x_chan_minmax (the bound of dx is formed from the last two)");
   DSPN_REQUIRE(!relu || (scale && shift), "bn_backward_from_sums: relu needs the forward scale/shift");
   DSPN_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, "bn_backward_from_sums: C must be a positive multiple of 4");
-  if (workspace_bytes < sizeof(float) * 3 * (size_t)C)
+  const size_t coef_bytes = sizeof(float) * 3 * (size_t)C;
+  if (workspace_bytes < coef_bytes)
     return dspn::fail(DSPN_ERR_WORKSPACE_, "bn_backward_from_sums: workspace too small (3*C floats)");
-  const int C4 = C / 4;
-  float *coef = static_cast<float *>(workspace);
-  const bool group_first = tiles >= tile_group_min() && workspace_bytes >= sizeof(float) * 3 * (size_t)C + bn_tiles_workspace_bytes(tiles, C);
-  if (defer) {
-    if (group_first) {      // (the group level needs hundreds of workgroups: a launch of its own, now)
-      const int groups = (tiles + kTileGroup - 1) / kTileGroup;
-      float *grouped = coef + 3 * (size_t)C;
-      hipLaunchKernelGGL(tile_group_kernel<1>, dim3(groups, (C + 63) / 64), dim3(256), 0, S_(stream), tile_sums, tiles, 1,
-                         (long long)tiles, C, grouped, static_cast<const float *>(nullptr), static_cast<float *>(nullptr));
-      tile_sums = grouped; tiles = groups;
+  float *coef = static_cast<float *>(workspace);      // the finalize hands the apply pass its coefficients here
+  if (half == DSPN_BN_SUMS_APPLY_ONLY) {      // jobs of this stream no weight gradient took: here, before the apply pass
+    for (dspn::BnFinalJob job; dspn::bn_job_take(S_(stream), &job);)
+      hipLaunchKernelGGL(bn_final_job_kernel, dim3(job.blocks), dim3(256), 0, S_(stream), job);
+  } else {
+    // a long table is grouped by a launch of its own, now, also where the rest is parked (that level needs hundreds of workgroups)
+    BnTiles t{tile_sums, tiles, 1, tiles, nullptr};
+    bn_group_tiles<1>(S_(stream), t, C, coef + 3 * (size_t)C, workspace_bytes - coef_bytes);
+    const dspn::BnFinalJob job = bn_final_job(t.table, t.tiles, C, rows, mean, rstd, gamma, coef, dgamma, dbeta,
+                                              planes ? dy_absmax : nullptr, planes ? x_chan_minmax : nullptr,
+                                              planes ? dx_absmax : nullptr, planes ? dx_absmin : nullptr);
+    if (parked) {      // for the next weight-gradient launch on this stream (bn_final_job.h)
+      dspn::bn_job_defer(S_(stream), job);
+      return dspn::check_launch("bn_backward_from_sums (parked)");
     }
-    dspn::BnFinalJob j;
-    j.tile_sums = tile_sums; j.tiles = tiles; j.C = C;
-    j.blocks = (C + dspn::kBnJobChannels - 1) / dspn::kBnJobChannels;
-    j.inv_rows = 1.0 / (double)rows; j.mean = mean; j.rstd = rstd; j.gamma = gamma; j.coef = coef; j.dgamma = dgamma; j.dbeta = dbeta;
-    j.dy_absmax = dx_planes ? dy_absmax : nullptr; j.x_minmax = dx_planes ? x_chan_minmax : nullptr;
-    j.dx_bound = dx_planes ? reinterpret_cast<unsigned *>(dx_absmax) : nullptr;
-    j.dx_bound_min = dx_planes ? reinterpret_cast<unsigned *>(dx_absmin) : nullptr;
-    dspn::bn_job_defer(S_(stream), j);
-    return dspn::check_launch("bn_backward_from_sums (parked)");
+    bn_final_launch(S_(stream), job);
   }
-  if (phase == 2)      // (jobs of this stream no weight gradient took: here, before the apply pass)
-    for (dspn::BnFinalJob parked; dspn::bn_job_take(S_(stream), &parked);)
-      hipLaunchKernelGGL(bn_final_job_kernel, dim3(parked.blocks), dim3(256), 0, S_(stream), parked);
-  if (phase != 2) {
-  if (group_first) {
-    const int groups = (tiles + kTileGroup - 1) / kTileGroup;
-    float *grouped = coef + 3 * (size_t)C;
-    hipLaunchKernelGGL(tile_group_kernel<1>, dim3(groups, (C + 63) / 64), dim3(256), 0, S_(stream), tile_sums, tiles, 1,
-                       (long long)tiles, C, grouped, static_cast<const float *>(nullptr), static_cast<float *>(nullptr));
-    tile_sums = grouped; tiles = groups;
-  }
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(1024), 0, S_(stream), tile_sums, tiles, C,
-                     1.0 / (double)rows, mean, rstd, gamma, coef, dgamma, dbeta, dx_planes ? dy_absmax : nullptr,
-                     dx_planes ? x_chan_minmax : nullptr, dx_planes ? reinterpret_cast<unsigned *>(dx_absmax) : nullptr,
-                     dx_planes ? reinterpret_cast<unsigned *>(dx_absmin) : nullptr);
-  }
-  if (phase == 1) return dspn::check_launch("bn_backward_from_sums (finalize)");
-  const long long n4 = rows * C4;
+  if (half == DSPN_BN_SUMS_FINALIZE_ONLY) return dspn::check_launch("bn_backward_from_sums (finalize)");
 #ifndef DSPN_HALF
-  if (dx_planes) {
+  if (planes) {
+    const int C4 = C / 4;
+    const long long n4 = rows * C4;
     int fixed4 = 0, u4 = 0;
     const int grid4 = grid_fixed_channel(n4, C4, &fixed4, &u4);
     hipLaunchKernelGGL(u4 ? bn_bwd_apply_planes_kernel<4> : bn_bwd_apply_planes_kernel<1>, dim3(grid4), dim3(kT), 0, S_(stream),
@@ -2259,26 +2272,7 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
     return dspn::check_launch("bn_backward_from_sums");
   }
 #endif
-#ifdef DSPN_HALF
-  if (C % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
-    int fixed8 = 0, u4 = 0;
-    const int grid8 = grid_fixed_channel(n4 / 2, C / 8, &fixed8, &u4);
-    hipLaunchKernelGGL(u4 ? bn_bwd_apply8_kernel<4> : bn_bwd_apply8_kernel<1>, dim3(grid8), dim3(kT), 0, S_(stream),
-                       reinterpret_cast<const dspn::u32x4_t *>(x), reinterpret_cast<const float4 *>(scale),
-                       reinterpret_cast<const float4 *>(shift), reinterpret_cast<const dspn::u32x4_t *>(dy),
-                       reinterpret_cast<const float4 *>(coef), reinterpret_cast<dspn::u32x4_t *>(dx), n4 / 2, C / 8, relu,
-                       accumulate, fixed8);
-    return dspn::check_launch("bn_backward");
-  }
-#endif
-  int fixed4 = 0, u4 = 0;
-  const int grid4 = grid_fixed_channel(n4, C4, &fixed4, &u4);
-  hipLaunchKernelGGL(u4 ? bn_bwd_apply_kernel<4> : bn_bwd_apply_kernel<1>, dim3(grid4), dim3(kT), 0, S_(stream),
-                     CA4Ptr(x), reinterpret_cast<const float4 *>(scale),
-                     reinterpret_cast<const float4 *>(shift), CA4Ptr(dy),
-                     reinterpret_cast<const float4 *>(coef), A4Ptr(dx), n4, C4, relu,
-                     accumulate, dspn::kHalf ? nullptr : reinterpret_cast<unsigned *>(dx_absmax), fixed4);
-  return dspn::check_launch("bn_backward_from_sums");
+  return bn_bwd_apply_launch(S_(stream), x, scale, shift, dy, coef, dx, rows, C, relu, accumulate, dx_absmax, "bn_backward_from_sums");
 }
 
 int DSPN_FN(dspn_add)(const st_t *a, const st_t *b, st_t *out, long long n, void *stream) {

@@ -544,6 +544,8 @@ def conv_dgrad_bn_tiles(x_shape, stride):
 
 MATH_DY_PLANES = 0x200       # include/dspn_nn.h DSPN_MATH_DY_PLANES
 MATH_X_PLANES = 0x400        # include/dspn_nn.h DSPN_MATH_X_PLANES
+# the flag word of dspn_bn_backward_from_sums_* (include/dspn_nn.h DSPN_BN_SUMS_*)
+BN_SUMS_PLANES, BN_SUMS_FINALIZE_ONLY, BN_SUMS_APPLY_ONLY, BN_SUMS_PARKED = 1, 2, 4, 8
 
 
 def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=False, bn_bwd=None, wt_planes=None,
@@ -810,17 +812,18 @@ def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, r
     C = x.shape[-1]
     rows = _rows(x)
     dx, dgamma, dbeta = _bn_outputs(x, gamma, dx, dgamma, dbeta)
-    if dx is None:                # parameters only: the finalize alone (flag word 2), nothing parked, no apply half
+    if dx is None:                # parameters only: the finalize alone, nothing parked, no apply half
         assert phase == 0 and not park and not dx_planes, "dx=NO_OUTPUT is a whole call"
         phase = 1
+    flags = ((BN_SUMS_PLANES if dx_planes else 0) | {0: 0, 1: BN_SUMS_FINALIZE_ONLY, 2: BN_SUMS_APPLY_ONLY}[phase] |
+             (BN_SUMS_PARKED if park else 0))
     if workspace is None:
         workspace = _scratch(12 * C + L().dspn_bn_tiles_workspace_bytes(tiles, C), x.device, "bn_from_sums")
     assert dy.dtype == x.dtype
     check(_f("dspn_bn_backward_from_sums", x)(ptr(x), ptr(scale), ptr(shift), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma),
                                              ptr(sums), tiles, ptr(dx), ptr(dgamma), ptr(dbeta), rows, C, int(relu),
                                              int(accumulate), ptr(dx_absmax), ptr(dx_absmin), ptr(dy_absmax), ptr(x_chan_minmax),
-                                             int(bool(dx_planes)) | (phase << 1) | (8 if park else 0), ptr(workspace),
-                                             workspace.numel(), stream()),
+                                             flags, ptr(workspace), workspace.numel(), stream()),
           "bn_backward_from_sums")
     return dx, dgamma, dbeta
 

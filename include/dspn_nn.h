@@ -411,16 +411,21 @@ int dspn_bn_backward_from_sums_f32(const float *x, const float *scale, const flo
                                    const float *mean, const float *rstd, const float *gamma, const float *tile_sums,
                                    int tiles, float *dx, float *dgamma, float *dbeta, long long rows, int C, int relu,
                                    int accumulate, float *dx_absmax, float *dx_absmin, const float *dy_absmax, const float *x_chan_minmax,
-                                   int dx_planes, void *workspace, size_t workspace_bytes, void *stream);
-/* dx_planes is a flag word (round 6): bit 0 = dx as piece planes (below); | 2 = the FINALIZE alone (per-channel coefficients
- * into the first 3 * C floats of the workspace, dgamma / dbeta, the bound of dx); | 4 = the APPLY pass alone, from the
- * coefficients an earlier call with | 2 (same arguments, same workspace) left there.  The finalize is a chain of one or two
- * latency-bound launches on 1 - 64 workgroups: a caller runs it on a second stream beside the layer's weight gradient
- * (dspnet_amd/engine.py, Conv.backward) and the apply behind both.  0 / 1: both, as before. */
-/* dx_absmin (optional, with dx_planes; round 5): ONE float, preset to +inf by the caller, that receives the smallest non-zero
+                                   int flags, void *workspace, size_t workspace_bytes, void *stream);
+/* flags is a word of DSPN_BN_SUMS_* bits (round 6): PLANES = dx as piece planes (below); | FINALIZE_ONLY = the finalize alone
+ * (per-channel coefficients into the first 3 * C floats of the workspace, dgamma / dbeta, the bound of dx); | APPLY_ONLY = the apply pass
+ * alone, from the coefficients an earlier FINALIZE_ONLY call (same arguments, same workspace) left there; | PARKED (with
+ * FINALIZE_ONLY) = the finalize is not launched but parked for the next weight-gradient launch on this stream, and the
+ * APPLY_ONLY call runs it if none took it.  The finalize is a chain of one or two latency-bound launches on 1 - 64
+ * workgroups: a caller keeps it off the critical path this way (dspnet_amd/engine.py, Conv.backward).  0 / 1: both halves. */
+#define DSPN_BN_SUMS_PLANES 1
+#define DSPN_BN_SUMS_FINALIZE_ONLY 2
+#define DSPN_BN_SUMS_APPLY_ONLY 4
+#define DSPN_BN_SUMS_PARKED 8
+/* dx_absmin (optional, with DSPN_BN_SUMS_PLANES; round 5): ONE float, preset to +inf by the caller, that receives the smallest non-zero
  * per-channel bound of |dx| -- with dx_absmax, the span of channel magnitudes the planes are cut over (the range guard of
  * DSPN_MATH_F32_F16X2 reads it; elements more than 2^17 below the tensor's largest magnitude lose relative accuracy). */
-/* dx_planes != 0 (round 4; float tensors, C % 32 == 0, accumulate == 0): dx is written as fp16 PIECE PLANES for
+/* DSPN_BN_SUMS_PLANES (round 4; float tensors, C % 32 == 0, accumulate == 0): dx is written as fp16 PIECE PLANES for
  * DSPN_MATH_F32_F16X2 instead of floats -- [row][C / 32][piece][32] 16-bit elements, the same 4 bytes per element and the
  * same byte offset for every group of four channels as the float tensor, (p0, p1) = (f16(s dx), f16(s dx - p0)) -- so that
  * the data gradient and the weight gradient of the convolution that produced x (DSPN_MATH_DY_PLANES) copy it into LDS
@@ -430,7 +435,7 @@ int dspn_bn_backward_from_sums_f32(const float *x, const float *scale, const flo
  * [lo, hi] = the channel's extremes of x in x_chan_minmax (2 x C floats: dspn_bn_stats_from_tiles_f32's out_chan_minmax).
  * dx_absmax (zeroed by the caller) RECEIVES that bound and is the block the consuming convolutions are given as their dy
  * magnitude -- a few times the true maximum at most, which the two-piece math does not feel (2^17). */
-/* Drops the finalize jobs parked on `stream` (dx_planes | 2 | 8 above) that no weight gradient and no apply-only call has
+/* Drops the finalize jobs parked on `stream` (DSPN_BN_SUMS_PARKED above) that no weight gradient and no apply-only call has
  * taken, without launching them: for a host that abandons a backward pass (a failed graph capture) before its apply-only
  * calls.  Host only; returns the number of jobs dropped. */
 int dspn_bn_discard_parked(void *stream);
@@ -693,7 +698,7 @@ int dspn_bn_backward_from_sums_bf16(const dspn_bf16 *x, const float *scale, cons
                                    const float *mean, const float *rstd, const float *gamma, const float *tile_sums,
                                    int tiles, dspn_bf16 *dx, float *dgamma, float *dbeta, long long rows, int C, int relu,
                                    int accumulate, float *dx_absmax_unused, float *dx_absmin_unused, const float *dy_absmax_unused,
-                                   const float *x_chan_minmax_unused, int dx_planes /* must be 0 */, void *workspace,
+                                   const float *x_chan_minmax_unused, int flags /* no DSPN_BN_SUMS_PLANES */, void *workspace,
                                    size_t workspace_bytes, void *stream);
 int dspn_add_bf16(const dspn_bf16 *a, const dspn_bf16 *b, dspn_bf16 *out, long long n, void *stream);
 int dspn_relu_backward_bf16(const dspn_bf16 *y, const dspn_bf16 *dy, dspn_bf16 *dx, long long n, int accumulate, void *stream);

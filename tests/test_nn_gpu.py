@@ -818,12 +818,13 @@ def test_dgrad_epilogue_batchnorm_backward_sums(gpu_device, conv_math, case, acc
 
 @pytest.mark.parametrize("case", [(2, 24, 24, 96, 1), (2, 16, 16, 48, 1), (8, 128, 128, 64, 1), (4, 128, 128, 256, 1), (3, 25, 23, 64, 2)])
 @pytest.mark.parametrize("planes", [False, True])
-@pytest.mark.parametrize("rider", ["wgrad", "wide wgrad", "nobody"])
+@pytest.mark.parametrize("rider", ["wgrad", "wide wgrad", "nobody", "unparked"])
 def test_parked_finalize_rides_in_the_weight_gradient_with_the_same_bits(gpu_device, case, planes, rider):
     """Round 6: dspn_bn_backward_from_sums split in two -- the finalize PARKED (flag | 2 | 8) and run by extra workgroups in
     front of the next weight-gradient launch on the stream (csrc/bn_final_job.h), or by the apply-only call (flag | 4) itself
     when no weight gradient came by -- against the one-call form: dx, dgamma, dbeta, the bound of dx and its per-channel minimum
-    bit for bit (grouped and plain tile tables, float dx and piece planes), and the weight gradient that carried the job unchanged."""
+    bit for bit (grouped and plain tile tables, float dx and piece planes), and the weight gradient that carried the job unchanged.
+    "unparked": the split call without parking -- the finalize launched by the finalize-only call (flag | 2), then flag | 4."""
     N, H, W, C, stride = case
     if planes and (fn.get_conv_math() != "f16x2" or C % 32):
         pytest.skip("piece planes: the two-piece math, C % 32 == 0")
@@ -864,8 +865,8 @@ def test_parked_finalize_rides_in_the_weight_gradient_with_the_same_bits(gpu_dev
         if not split:
             out = fn.bn_backward_from_sums(*args, **kw)
         else:
-            fn.bn_backward_from_sums(*args, phase=1, park=True, **kw)
-            if rider != "nobody":
+            fn.bn_backward_from_sums(*args, phase=1, park=rider != "unparked", **kw)
+            if rider not in ("nobody", "unparked"):
                 dw = wgrad()
             out = fn.bn_backward_from_sums(*args, phase=2, **kw)
         return out + (bound, bmin), dw
