@@ -55,9 +55,9 @@ int reserved_cus() { return g_reserved_cus.load(std::memory_order_relaxed); }
 static std::atomic<int> g_wide_tiles{0};
 int wide_tiles_mode() { return g_wide_tiles.load(std::memory_order_relaxed); }
 // round 6: the tile-spanning loop of the short-K members of the wide family (conv_wide.h, XT); DSPN_XT=0 starts with it off
-static std::atomic<int> g_tile_spanning{[] { const char *e = getenv("DSPN_XT"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 2 ? 2 : v); }()};
+static std::atomic<int> g_tile_spanning{(int)std::clamp<long long>(env_int("DSPN_XT", 1), 0, 2)};
 int tile_spanning() { return g_tile_spanning.load(std::memory_order_relaxed); }
-static std::atomic<int> g_sampler_batched{[] { const char *e = getenv("DSPN_SAMPLER_BATCHED"); return (e && atoi(e) == 0) ? 0 : 1; }()};
+static std::atomic<int> g_sampler_batched{env_int("DSPN_SAMPLER_BATCHED", 1) == 0 ? 0 : 1};
 int sampler_batched() { return g_sampler_batched.load(std::memory_order_relaxed); }
 // round 6: a BatchNorm-backward finalize parked for the next weight-gradient launch on its stream (bn_final_job.h).  One job
 // per stream (a second one for the same stream replaces nothing: the first is handed to whoever asks first, then the second)

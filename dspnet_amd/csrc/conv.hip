@@ -1809,8 +1809,6 @@ __global__ void nt_split_reduce_kernel(const float *__restrict__ slab, const flo
 // caller-provided scratch for split-K partial tiles (set per call by the C entry points)
 struct SplitWs { float *ptr; size_t bytes; };
 
-
-
 template <int WAVES_M, int WAVES_N, int TM, int TN, bool UNIFORM_TAP, int MATH, bool INTF, int EPI>
 int launch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g,
                    hipStream_t s, int splits, int ksteps_per_split, float *slab, const st_t *residual) {
@@ -1824,22 +1822,11 @@ int launch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, 
                                       : MATH == 1 ? sizeof(__bf16) * 2 * (BM + BN) * kLdsRowH
                                                   : sizeof(float) * 2 * (BM + BN) * kLdsRow,
                                       sizeof(float) * BM * (BN + 4));
-  auto kern = conv_nt_kernel<WAVES_M, WAVES_N, TM, TN, UNIFORM_TAP, MATH, INTF, EPI>;
-  // persistent grid: as many workgroups as the chip holds at once (occupancy x CUs, a multiple of 8 so that
-  // a workgroup's tiles t, t + grid, ... stay on its XCD's run of the tile order); each walks its tiles
-  static dspn::KernelDeviceState st;
-  const bool first = !st.slots[0] && !st.slots[1];
-  const int dev = dspn::ensure_persistent_grid(reinterpret_cast<const void *>(kern), WAVES_M * WAVES_N * 64, lds, st, "conv_nt");
-  if (dev < 0) return dev;
-  const int slots = st.slots[dev], slots_per_cu = st.slots_per_cu[dev], slots_cus = st.cus[dev];
-  if (first && getenv("DSPN_DEBUG_PRINT"))
-    fprintf(stderr, "[dspn] conv_nt<%d,%d,%d,%d,uni=%d,bf16=%d,intf=%d,epi=%d>: %zu B LDS, occupancy %d/CU x %d CUs -> grid %d\n",
-            WAVES_M, WAVES_N, TM, TN, (int)UNIFORM_TAP, MATH, (int)INTF, EPI, lds, slots_per_cu, slots_cus, slots);
-  // dspn_conv_set_reserved_cus(k): the persistent grid leaves k CUs' worth of workgroup slots free, so that the kernels of
-  // another queue (RCCL's all-reduce of the gradient buckets) find room beside a convolution instead of only between two
-  const int reserved = dspn::reserved_cus();
-  const int avail = reserved > 0 ? std::max(8, slots_per_cu * std::max(8, slots_cus - reserved) / 8 * 8) : slots;
-  const int grid_x = (int)std::min<long long>((long long)mt * nt, avail);
+  constexpr auto kern = conv_nt_kernel<WAVES_M, WAVES_N, TM, TN, UNIFORM_TAP, MATH, INTF, EPI>;
+  const int grid_x = dspn::persistent_grid<kern>(WAVES_M * WAVES_N * 64, lds, (long long)mt * nt, "conv_nt",
+                                                 "conv_nt<%d,%d,%d,%d,uni=%d,bf16=%d,intf=%d,epi=%d>", WAVES_M, WAVES_N, TM, TN,
+                                                 (int)UNIFORM_TAP, MATH, (int)INTF, EPI);
+  if (grid_x < 0) return grid_x;
   {
     dspn::ProfScope prof(0, s);
     hipLaunchKernelGGL(kern, dim3(grid_x, splits), dim3(WAVES_M * WAVES_N * 64), lds, s, in, w, bias, out, g, mt, nt,
@@ -1895,37 +1882,33 @@ int nt_config(long long M, int Cout) {
   // measured on MI355X (scratch/cfgtest.py, scratch/x3_knobs.sh): 128x128 wins once it yields >= one workgroup per CU
   // in the split math (667 vs 656 images/s against the round-1 threshold of two per CU, which the fp32-MFMA and bf16-tensor
   // modes prefer by 0.3 .. 0.5 %); otherwise the 64x64 tile (4 workgroups of 36 KiB LDS per CU, 4 waves per SIMD)
-  static const long long min_tiles = [] { const char *e = getenv("DSPN_NT_MINTILES"); return e ? atoll(e) : 256ll; }();   // experiments
+  static const long long min_tiles = dspn::env_int("DSPN_NT_MINTILES", 256);   // experiments
   if (Cout <= 32) cfg = tiles(256, 32) >= min_tiles ? 3 : 2;
   else cfg = (Cout > 64 && tiles(128, 128) >= min_tiles) ? 0 : 2;
   // a Cout just past a multiple of 128 (171 = 19 classes x 9 taps) wastes up to half of the last
   // 128-wide column tile: 64-wide columns cut the padding to < 64
   if (cfg == 0 && (Cout + 63) / 64 * 64 < (Cout + 127) / 128 * 128) cfg = 1;
-  static const int cfg64 = [] { const char *e = getenv("DSPN_NT_CFG64"); return e ? atoi(e) : -1; }();   // experiments
+  static const int cfg64 = (int)dspn::env_int("DSPN_NT_CFG64", -1);   // experiments
   if (cfg64 >= 0 && Cout > 32 && Cout <= 64 && tiles(kNtBm[cfg64], kNtBn[cfg64]) >= min_tiles) cfg = cfg64;
   if ((g_debug_bits >> 8) & 7) cfg = ((g_debug_bits >> 8) & 7) - 1;   // timing experiments only
   return cfg;
 }
-int dispatch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g_in,
-                     hipStream_t s, SplitWs ws, const st_t *residual, bool *wide_used);
-// one convolution launch; g.bn_dy_absmax without g.bn_sums = the magnitude block of the stored output (conv2d_forward_one):
-// written by the wide family's epilogue, by a pass over the output behind any other kernel
-int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g_in,
-                hipStream_t s, SplitWs ws, const st_t *residual = nullptr) {
-  bool wide = false;
-  const int rc = dispatch_nt_impl(in, w, bias, out, g_in, s, ws, residual, &wide);
+// g.bn_dy_absmax without g.bn_sums = the magnitude block of the stored output (conv2d_forward_one): written by the wide family's
+// epilogue, by this pass over the output behind any other kernel
+int output_absmax_pass(const st_t *out, const ConvGeom &g, hipStream_t s) {
 #ifndef DSPN_HALF
-  if (!rc && g_in.bn_dy_absmax && !g_in.bn_sums && !wide) {
-    if (!(g_in.dense && g_in.obs == (long long)g_in.Hg * g_in.Wg * g_in.ldc && g_in.ldc % 4 == 0))
+  if (g.bn_dy_absmax && !g.bn_sums) {
+    if (!(g.dense && g.obs == (long long)g.Hg * g.Wg * g.ldc && g.ldc % 4 == 0))
       return dspn::fail(DSPN_ERR_ARG_, "conv2d_forward: the output magnitude block needs a dense output with ldc %% 4 == 0");
-    return dspn_absmax_f32(out, (long long)g_in.N * g_in.Hg * g_in.Wg, g_in.ldc, nullptr, nullptr, 0,
-                           reinterpret_cast<float *>(g_in.bn_dy_absmax), s);
+    return dspn_absmax_f32(out, (long long)g.N * g.Hg * g.Wg, g.ldc, nullptr, nullptr, 0, reinterpret_cast<float *>(g.bn_dy_absmax), s);
   }
 #endif
-  return rc;
+  return 0;
 }
-int dispatch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g_in,
-                     hipStream_t s, SplitWs ws, const st_t *residual, bool *wide_used) {
+// one convolution launch: the checks every kernel shares, then the wide family where it is legal and dspn::conv::wide_route
+// names a member, conv_nt_kernel on the tile of nt_config everywhere else
+int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g_in,
+                hipStream_t s, SplitWs ws, const st_t *residual = nullptr) {
   ConvGeom g = g_in;
   g.dbg = g_debug_bits;
   // the 4-element-vector epilogue needs aligned rows (16 bytes float, 8 bytes bf16) in every operand it touches
@@ -1941,7 +1924,7 @@ int dispatch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out
     g.in_bytes = (unsigned)ib; g.w_bytes = (unsigned)wb;
   }
   const long long M = (long long)g.N * g.Hg * g.Wg;
-  if (M <= 0) return 0;
+  if (M <= 0) return output_absmax_pass(out, g, s);
   // split mode with whole 32-channel blocks per tap: the kernels read the weights as piece planes
   const bool pre = !kHalf && g.bf16 >= 2 && ((g.Cin / kEPC) & 7) == 0;
   if (pre) {
@@ -1950,10 +1933,8 @@ int dispatch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out
     w = static_cast<const st_t *>(g.w_planes);
     g.w_bytes = (unsigned)((g.bf16 == 3 ? 4ll : 6ll) * g.Cout * g.WTAPS * g.Cin);
   }
-  auto tiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((g.Cout + bn - 1) / bn); };
   const int cfg = nt_config(M, g.Cout);
-  const int *bm_ = kNtBm, *bn_ = kNtBn;
-  const long long nblk = tiles(bm_[cfg], bn_[cfg]);
+  const long long nblk = ((M + kNtBm[cfg] - 1) / kNtBm[cfg]) * ((g.Cout + kNtBn[cfg] - 1) / kNtBn[cfg]);
   const int nk = (g.TR * g.TS * (g.Cin / kEPC) + 7) >> 3;
   int splits = 1, per = nk;
   if (g.a_planes && !(pre && g.bf16 == 3 && !g.in_scale))
@@ -1975,8 +1956,7 @@ int dispatch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out
   // per SIMD reaches 67 % of the MFMA rate in this loop, two 81 %, four 93 % on a plain 1x1 layer (in-kernel stamps,
   // scratch/clock_probe.py) -- but the 128-VGPR budget leaves no room for the fused-BatchNorm epilogues, which lose
   // more than the main loop gains.  Used for the plain epilogue only (measured +4..6 %); DSPN_NT_8WAVE=1|0 forces it.
-  static const char *eight_env = getenv("DSPN_NT_8WAVE");
-  const int eight_mode = eight_env ? atoi(eight_env) : -1;   // -1 default, 0 never, 1 always, 2 default + 1x1 dgrads, 3 default + every 1x1
+  static const int eight_mode = (int)dspn::env_int("DSPN_NT_8WAVE", -1);   // -1 default, 0 never, 1 always, 2 default + 1x1 dgrads, 3 default + every 1x1
   const bool one_tap = g.TR * g.TS == 1;
   // bf16 tensors: the main loop is ~3x shorter, the fused epilogues cost relatively more, and the 8-wave form wins for
   // every epilogue (measured on the resnet-50 step: 28.6 -> 26.1 ms)
@@ -1988,29 +1968,22 @@ int dispatch_nt_impl(const st_t *in, const st_t *w, const float *bias, st_t *out
   // columns (cfg 2) -- the layouts the wide epilogue writes -- and the A operand is a pure copy: fp16 piece planes in the float
   // build (=> two-piece math, whole 32-channel blocks, no input affine), the bf16 tensor itself in the bf16 build (whole
   // 64-channel blocks, no input affine).
-  {
-    bool wide_ok = splits == 1 && (cfg == 0 || (cfg == 2 && g.Cout > 32 && g.Cout <= 64)) && (g.flags & 16) && g.Cout % 4 == 0 &&
-                   g.TR * g.TS > 0;
-    // bf16 tensors: legal, bit-identical (tests/test_wide_tiles_gpu.py) and NOT faster -- the training step measured 1340 - 1343
-    // images/s with the family against 1345 - 1347 without, every forced shape lower still (profiles/r05_bf16_wide_ab.txt): those
-    // kernels are bound by the bytes they ask the L2 for, which a 128 x 128 tile does not change.  Only a forced mode routes them.
-    if (kHalf) wide_ok = wide_ok && !g.in_scale && g.Cin % 64 == 0 && dspn::wide_tiles_mode() >= 2;
-    else wide_ok = wide_ok && pre && g.bf16 == 3;       // (pre: whole 32-channel blocks, the weights as piece planes)
-    if (wide_ok) {
-      int shape = dspn::conv::wide_tile_choice(M, g.Cout, nk, (g.stats || g.bn_sums) ? 1 : 0);
-      // a float A operand (with or without the folded BatchNorm affine) goes through the family's register-staged member:
-      // shapes 12 / 13 / 14 = 128 x 256, 128 x 128 on four waves, 256 x 64 (conv_wide.h, conv_ntv_kernel)
-      if (shape && !kHalf && !g.a_planes) shape = 10 + (shape == 1 ? 3 : shape);
-      if (shape) { *wide_used = true; return dspn::conv::launch_wide(shape, in, w, bias, out, g, s, residual); }
-    }
-  }
-  if (cfg == 0 && eight) return launch_nt<4, 2, 1, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
-  switch (cfg) {
-    case 0: return launch_nt<2, 2, 2, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
-    case 1: return launch_nt<2, 2, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
-    case 2: return launch_nt<2, 2, 1, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
-    default: return launch_nt<4, 1, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
-  }
+  bool wide_ok = splits == 1 && (cfg == 0 || (cfg == 2 && g.Cout > 32 && g.Cout <= 64)) && (g.flags & 16) && g.Cout % 4 == 0 &&
+                 g.TR * g.TS > 0;
+  // bf16 tensors: legal, bit-identical (tests/test_wide_tiles_gpu.py) and NOT faster -- the training step measured 1340 - 1343
+  // images/s with the family against 1345 - 1347 without, every forced shape lower still (profiles/r05_bf16_wide_ab.txt): those
+  // kernels are bound by the bytes they ask the L2 for, which a 128 x 128 tile does not change.  Only a forced mode routes them.
+  if (kHalf) wide_ok = wide_ok && !g.in_scale && g.Cin % 64 == 0 && dspn::wide_tiles_mode() >= 2;
+  else wide_ok = wide_ok && pre && g.bf16 == 3;       // (pre: whole 32-channel blocks, the weights as piece planes)
+  // (whole channel blocks per tap there: nk is the family's k-step count)
+  if (const dspn::conv::WideRoute route = wide_ok ? dspn::conv::wide_route(g, M, nk) : dspn::conv::WideRoute{})
+    return dspn::conv::launch_wide(route, in, w, bias, out, g, s, residual);
+  const int rc = cfg == 0 && eight ? launch_nt<4, 2, 1, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
+                 : cfg == 0        ? launch_nt<2, 2, 2, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
+                 : cfg == 1        ? launch_nt<2, 2, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
+                 : cfg == 2        ? launch_nt<2, 2, 1, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
+                                   : launch_nt<4, 1, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
+  return rc ? rc : output_absmax_pass(out, g, s);
 }
 
 struct WgradPlan { int bm; int bn; int splits; int pps; };
@@ -2023,6 +1996,8 @@ static_assert(kPlanPK % kPK == 0, "split sizes must be whole k-steps");
 // holds at once, set by LDS per workgroup), each costs its pixels plus a fixed prologue/epilogue, and
 // every split adds one slab to write and re-read.  (A plain "about 1024 workgroups" rule lands just
 // past a round boundary for the 3x3 layers: 36 tiles x 29 splits = 1044 = 2.04 rounds.)
+// x_bytes of wgrad_plan: the bytes of x that P output pixels touch, for a layer whose taps re-read them (one tap: 0, no bound)
+long long wgrad_x_footprint(long long P, int Cin, int taps, int stride) { return taps > 1 ? 4ll * P * Cin * std::min(stride, 2) * std::min(stride, 2) : 0; }
 WgradPlan wgrad_plan(long long P, int Cout, int J, long long x_bytes = 0, long long max_splits = 1 << 30) {
   WgradPlan p;
   p.bm = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128);
@@ -2066,6 +2041,59 @@ WgradPlan wgrad_plan(long long P, int Cout, int J, long long x_bytes = 0, long l
   return p;
 }
 
+// one weight-gradient launch: the slab grid (kt x jt tiles, one row per split) and, in front of it, the rows of a parked
+// BatchNorm-backward finalize
+struct WgradLaunch { const st_t *x, *dy; float *slab; const WgradGeom &g; int kt, jt, rows; size_t lds; hipStream_t s; };
+// MODE: the math (0 fp32 MFMA .. 3 two-piece), 4 = two-piece with dy as piece planes, 5 = x, 6 = both; INTF: the input affine
+template <int WM, int WN, int TM, int TN, int MODE, bool INTF>
+int launch_wgrad_impl(const WgradLaunch &a) {
+  auto kern = conv_wgrad_kernel<WM, WN, TM, TN, MODE, INTF>;
+  static dspn::KernelDeviceState st;
+  if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), a.lds, st, "conv_wgrad"); dev < 0) return dev;
+  hipLaunchKernelGGL(kern, dim3(a.kt * a.jt, a.rows), dim3(WM * WN * 64), a.lds, a.s, a.x, a.dy, a.slab, a.g, a.kt, a.jt);
+  return 0;
+}
+template <int WM, int WN, int TM, int TN, int MODE>
+int launch_wgrad_mode(const WgradLaunch &a) {
+  return a.g.in_scale ? launch_wgrad_impl<WM, WN, TM, TN, MODE, true>(a) : launch_wgrad_impl<WM, WN, TM, TN, MODE, false>(a);
+}
+template <int WM, int WN, int TM, int TN>
+int launch_wgrad_tile(const WgradLaunch &a) {
+  // the math, or the two-piece math with fp16 piece planes of dy (4), of x (5: never behind an input affine, the entries check), of both (6)
+  switch (kHalf ? 1 : a.g.bf16 != 3 ? a.g.bf16 : a.g.x_planes ? 5 + a.g.dy_planes : 3 + a.g.dy_planes) {
+#ifndef DSPN_HALF
+    case 6: return launch_wgrad_impl<WM, WN, TM, TN, 6, false>(a);
+    case 5: return launch_wgrad_impl<WM, WN, TM, TN, 5, false>(a);
+    case 4: return launch_wgrad_mode<WM, WN, TM, TN, 4>(a);
+    case 3: return launch_wgrad_mode<WM, WN, TM, TN, 3>(a);
+    case 2: return launch_wgrad_mode<WM, WN, TM, TN, 2>(a);
+    case 0: return launch_wgrad_mode<WM, WN, TM, TN, 0>(a);
+#endif
+    default: return launch_wgrad_mode<WM, WN, TM, TN, 1>(a);
+  }
+}
+static int launch_wgrad(int BM, int BN, const WgradLaunch &a) {
+#ifndef DSPN_HALF
+  // round 6: both operands as piece planes on a 128 x 128 tile -- global -> LDS directly, 64 x 64 per wave (conv_wgrad_wide.h);
+  // same split plan, same slabs, same bits.  dspn_conv_set_wide_tiles(1) / DSPN_WGW=0: conv_wgrad_kernel (tests, same-box A/B)
+  static const bool wgw_env = dspn::env_int("DSPN_WGW", 1) != 0;
+  // (eight waves on 128 x 256 with a three-slot ring measured no faster where the plan fills the chip -- stages 3 and 4: 0.37 - 0.39
+  // of 833.3 either way -- and 1.5 x slower where it does not; profiles/r06_wgrad_wide_tile.txt)
+  if (a.g.bf16 == 3 && a.g.x_planes && a.g.dy_planes && BM == 128 && BN == 128 && wgw_env && dspn::wide_tiles_mode() != 1) {
+    auto kern = conv_wgw_kernel<2, 2, 2>;
+    const size_t lds_w = std::max<size_t>(2 * (size_t)kPK * (128 + 128) * 4, sizeof(float) * 128 * (128 + 4));
+    static dspn::KernelDeviceState st;
+    if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_w, st, "conv_wgrad (wide)"); dev < 0) return dev;
+    hipLaunchKernelGGL(kern, dim3(a.kt * a.jt, a.rows), dim3(256), lds_w, a.s, a.x, a.dy, a.slab, a.g, a.kt, a.jt);
+    return 0;
+  }
+#endif
+  if (BM == 32) return launch_wgrad_tile<1, 4, 1, 1>(a);                     // 32 x 128
+  if (BM == 64) return launch_wgrad_tile<2, 2, 1, 2>(a);                     // 64 x 128
+  if (BN == 64) return launch_wgrad_tile<2, 2, 2, 1>(a);                     // 128 x 64
+  return launch_wgrad_tile<4, 2, 1, 2>(a);   // 128 x 128 on 8 waves: two workgroups = 4 waves per SIMD (+3..6 % over <2,2,2,2>)
+}
+
 }  // namespace
 
 extern "C" {
@@ -2092,6 +2120,22 @@ size_t dspn_conv2d_split_workspace_bytes(long long out_pixels, int Cout) {
 }
 #endif
 
+// The `math` argument of an entry point: *math keeps the mode (DSPN_MATH_FP32 .. DSPN_MATH_F32_F16X2; a plane flag the entry does
+// not take -- not in plane_bits -- stays in it and fails check_math_mode), -> DSPN_MATH_UNSCALED_OK and the plane flags that were set
+static int split_math(int *math, int plane_bits) {
+  const int flags = *math & (DSPN_MATH_UNSCALED_OK | plane_bits);
+  *math &= ~flags;
+  return flags;
+}
+static int check_math_mode(const char *who, int math) {
+  DSPN_REQUIRE(math >= DSPN_MATH_FP32 && math <= DSPN_MATH_F32_F16X2, "%s: math is one of DSPN_MATH_*", who);
+  return 0;
+}
+static int check_math_blocks(const char *who, int math, int flags, const float *a_absmax, const float *b_absmax) {
+  DSPN_REQUIRE(dspn::kHalf || math != DSPN_MATH_F32_F16X2 || (flags & DSPN_MATH_UNSCALED_OK) || (a_absmax && b_absmax),
+               "%s: DSPN_MATH_F32_F16X2 needs the magnitude block of both operands (dspn_absmax_f32); a caller who knows that every |operand| < 65504 passes math | DSPN_MATH_UNSCALED_OK", who);
+  return 0;
+}
 struct InAffine { const float *scale, *shift; int relu; };
 struct OpScales { const float *a, *b; int a_planes = 0; };   // device scalars: largest magnitudes of the two operands (DSPN_MATH_F32_F16X2); a_planes: DSPN_MATH_DY_PLANES
 
@@ -2171,13 +2215,11 @@ int DSPN_FN(dspn_conv2d_forward_bn)(const st_t *x, const float *in_scale, const 
                                int math, const float *x_absmax, const float *w_absmax,
                                void *workspace, size_t workspace_bytes, void *stream) {
   DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0, "conv2d_forward: bad geometry");
-  const int math_vouch = math & DSPN_MATH_UNSCALED_OK, x_planes = (math & DSPN_MATH_X_PLANES) ? 1 : 0;
-  math &= ~(DSPN_MATH_UNSCALED_OK | DSPN_MATH_X_PLANES);
-  DSPN_REQUIRE(math >= DSPN_MATH_FP32 && math <= DSPN_MATH_F32_F16X2, "conv2d_forward: math is one of DSPN_MATH_*");
+  const int flags = split_math(&math, DSPN_MATH_X_PLANES), x_planes = (flags & DSPN_MATH_X_PLANES) ? 1 : 0;
+  if (const int rc = check_math_mode("conv2d_forward", math)) return rc;
   DSPN_REQUIRE(!x_planes || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && Cin % 32 == 0 && x_absmax && !in_scale),
                "conv2d_forward: DSPN_MATH_X_PLANES needs DSPN_MATH_F32_F16X2, Cin %% 32 == 0, no input affine and the block the planes were cut by (x_absmax)");
-  DSPN_REQUIRE(dspn::kHalf || math != DSPN_MATH_F32_F16X2 || math_vouch || (x_absmax && w_absmax),
-               "conv2d_forward: DSPN_MATH_F32_F16X2 needs the magnitude block of both operands (dspn_absmax_f32); a caller who knows that every |operand| < 65504 passes math | DSPN_MATH_UNSCALED_OK");
+  if (const int rc = check_math_blocks("conv2d_forward", math, flags, x_absmax, w_absmax)) return rc;
   DSPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv2d_forward: in_scale and in_shift go together");
   if (out_stats) {
     int tile_rows = 0;
@@ -2394,13 +2436,11 @@ int DSPN_FN(dspn_conv2d_dgrad_bn)(const st_t *dy, const st_t *wt, const void *wt
                              int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
                              void *stream) {
   DSPN_REQUIRE(N > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_dgrad: bad geometry");
-  const int math_vouch = math & DSPN_MATH_UNSCALED_OK, dy_planes = (math & DSPN_MATH_DY_PLANES) ? 1 : 0;
-  math &= ~(DSPN_MATH_UNSCALED_OK | DSPN_MATH_DY_PLANES);
+  const int flags = split_math(&math, DSPN_MATH_DY_PLANES), dy_planes = (flags & DSPN_MATH_DY_PLANES) ? 1 : 0;
   DSPN_REQUIRE(!dy_planes || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && ldy % 32 == 0 && dy_absmax),
                "conv2d_dgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy %% 32 == 0 and the block the planes were cut by (dy_absmax)");
-  DSPN_REQUIRE(math >= DSPN_MATH_FP32 && math <= DSPN_MATH_F32_F16X2, "conv2d_dgrad: math is one of DSPN_MATH_*");
-  DSPN_REQUIRE(dspn::kHalf || math != DSPN_MATH_F32_F16X2 || math_vouch || (dy_absmax && w_absmax),
-               "conv2d_dgrad: DSPN_MATH_F32_F16X2 needs the magnitude block of both operands (dspn_absmax_f32); a caller who knows that every |operand| < 65504 passes math | DSPN_MATH_UNSCALED_OK");
+  if (const int rc = check_math_mode("conv2d_dgrad", math)) return rc;
+  if (const int rc = check_math_blocks("conv2d_dgrad", math, flags, dy_absmax, w_absmax)) return rc;
   const int ldc = dx_ldc > 0 ? dx_ldc : Cin;
   const int nb = batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy);
   if (bn_sums) {
@@ -2460,10 +2500,11 @@ size_t dspn_conv2d_wgrad_workspace_bytes(int N, int Ho, int Wo, int Cin, int Cou
   const long long P = (long long)N * Ho * Wo;
   const int J = R * S * Cin;
   if (P <= 0 || J <= 0 || Cout <= 0) return 0;
-  // the plan depends on (P, Cout, J) and, for R*S > 1, on the stride (1 or 2) through the x footprint
+  // the plan depends on (P, Cout, J) and on the stride (1 or 2) through the x footprint: sized for either, and for every
+  // layer as if its taps re-read x
   size_t m = (size_t)wgrad_plan(P, Cout, J).splits;
   for (int stride = 1; stride <= 2; ++stride)
-    m = std::max(m, (size_t)wgrad_plan(P, Cout, J, 4ll * P * Cin * stride * stride).splits);
+    m = std::max(m, (size_t)wgrad_plan(P, Cout, J, wgrad_x_footprint(P, Cin, std::max(R * S, 2), stride)).splits);
   return sizeof(float) * m * Cout * J;
 }
 #endif
@@ -2492,7 +2533,7 @@ static int conv2d_wgrad_one(int math, OpScales scales, const st_t *x, InAffine t
   const long long ws_splits = (long long)(workspace_bytes / (sizeof(float) * (size_t)Cout * J));
   if (ws_splits < 1)
     return dspn::fail(DSPN_ERR_WORKSPACE_, "conv2d_wgrad: workspace %zu < %zu (one slab)", workspace_bytes, sizeof(float) * (size_t)Cout * J);
-  const WgradPlan plan = wgrad_plan(P, Cout, J, R * S > 1 ? 4ll * P * Cin * std::min(stride, 2) * std::min(stride, 2) : 0, ws_splits);
+  const WgradPlan plan = wgrad_plan(P, Cout, J, wgrad_x_footprint(P, Cin, R * S, stride), ws_splits);
   const int BM = plan.bm, BN = plan.bn;
   const int kt = (Cout + BM - 1) / BM, jt = (J + BN - 1) / BN;
   const long long splits = plan.splits;
@@ -2512,60 +2553,7 @@ static int conv2d_wgrad_one(int math, OpScales scales, const st_t *x, InAffine t
                            : std::max<size_t>(sizeof(float) * std::max(2 * kPK * (BM + BN), BM * (BN + 4)),
                                               3 * (size_t)kPK * (wg_row_bytes(BM) + wg_row_bytes(BN)));
   dspn::ProfScope prof(1, s);
-#ifdef DSPN_HALF
-#define DSPN_WGRAD_LAUNCH(WM, WN, TM_, TN_)                                                              \
-  {                                                                                                      \
-    if (g.in_scale) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 1, true)                                        \
-    else DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 1, false)                                                  \
-  }
-#else
-#define DSPN_WGRAD_LAUNCH(WM, WN, TM_, TN_)                                                              \
-  {                                                                                                      \
-    if (g.bf16 == 3 && g.x_planes) {                                                                     \
-      if (g.dy_planes) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 6, false)                                    \
-      else DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 5, false)                                                \
-    } else if (g.in_scale) {                                                                             \
-      if (g.bf16 == 3 && g.dy_planes) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 4, true)                      \
-      else if (g.bf16 == 3) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 3, true)                                \
-      else if (g.bf16 == 2) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 2, true)                                \
-      else if (g.bf16) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 1, true)                                     \
-      else DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 0, true)                                                 \
-    } else {                                                                                             \
-      if (g.bf16 == 3 && g.dy_planes) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 4, false)                     \
-      else if (g.bf16 == 3) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 3, false)                               \
-      else if (g.bf16 == 2) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 2, false)                               \
-      else if (g.bf16) DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 1, false)                                    \
-      else DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, 0, false)                                                \
-    }                                                                                                    \
-  }
-#endif
-#define DSPN_WGRAD_LAUNCH_(WM, WN, TM_, TN_, BF, TF)                                                     \
-  {                                                                                                      \
-    auto kern = conv_wgrad_kernel<WM, WN, TM_, TN_, BF, TF>;                                             \
-    static dspn::KernelDeviceState st;                                                                   \
-    if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, st, "conv_wgrad"); dev < 0) return dev; \
-    hipLaunchKernelGGL(kern, dim3(kt * jt, (int)splits + g.job_rows), dim3(WM * WN * 64), lds, s, x, dy, slab, g, kt, jt); \
-  }
-#ifndef DSPN_HALF
-  // round 6: both operands as piece planes on a 128 x 128 tile -- global -> LDS directly, 64 x 64 per wave (conv_wgrad_wide.h);
-  // same split plan, same slabs, same bits.  dspn_conv_set_wide_tiles(1) / DSPN_WGW=0: conv_wgrad_kernel (tests, same-box A/B)
-  static const bool wgw_env = [] { const char *e = getenv("DSPN_WGW"); return !(e && atoi(e) == 0); }();
-  // (eight waves on 128 x 256 with a three-slot ring measured no faster where the plan fills the chip -- stages 3 and 4: 0.37 - 0.39
-  // of 833.3 either way -- and 1.5 x slower where it does not; profiles/r06_wgrad_wide_tile.txt)
-  if (g.bf16 == 3 && g.x_planes && g.dy_planes && BM == 128 && BN == 128 && wgw_env && dspn::wide_tiles_mode() != 1) {
-    auto kern = conv_wgw_kernel<2, 2, 2>;
-    const size_t lds_w = std::max<size_t>(2 * (size_t)kPK * (128 + 128) * 4, sizeof(float) * 128 * (128 + 4));
-    static dspn::KernelDeviceState st;
-    if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_w, st, "conv_wgrad (wide)"); dev < 0) return dev;
-    hipLaunchKernelGGL(kern, dim3(kt * jt, (int)splits + g.job_rows), dim3(256), lds_w, s, x, dy, slab, g, kt, jt);
-  } else
-#endif
-  if (BM == 32) DSPN_WGRAD_LAUNCH(1, 4, 1, 1)                     // 32 x 128
-  else if (BM == 64) DSPN_WGRAD_LAUNCH(2, 2, 1, 2)                // 64 x 128
-  else if (BN == 64) DSPN_WGRAD_LAUNCH(2, 2, 2, 1)                // 128 x 64
-  else DSPN_WGRAD_LAUNCH(4, 2, 1, 2)   // 128 x 128 on 8 waves: two workgroups = 4 waves per SIMD (+3..6 % over <2,2,2,2>)
-#undef DSPN_WGRAD_LAUNCH
-#undef DSPN_WGRAD_LAUNCH_
+  if (const int rc = launch_wgrad(BM, BN, WgradLaunch{x, dy, slab, g, kt, jt, (int)splits + g.job_rows, lds, s})) return rc;
   int rc = dspn::check_launch("conv_wgrad");
   if (rc || !dw) return rc;
   const long long n4 = (long long)Cout * J / 4;
@@ -2576,28 +2564,33 @@ static int conv2d_wgrad_one(int math, OpScales scales, const st_t *x, InAffine t
   return dspn::check_launch("conv_wgrad_reduce");
 }
 
+// the argument checks of the weight-gradient entries; *math: the argument, then its mode; *planes: bit 0 dy, bit 1 x as piece planes
+static int wgrad_check(int *math, int *planes, int N, int H, int W, int Cin, int Cout, int ldy, int Ho, int Wo, const float *in_scale,
+                       const float *in_shift, const float *x_absmax, const float *dy_absmax) {
+  DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_wgrad: bad geometry");
+  DSPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv2d_wgrad: in_scale and in_shift go together");
+  const int flags = split_math(math, DSPN_MATH_DY_PLANES | DSPN_MATH_X_PLANES);
+  *planes = ((flags & DSPN_MATH_DY_PLANES) ? 1 : 0) | ((flags & DSPN_MATH_X_PLANES) ? 2 : 0);
+  DSPN_REQUIRE(!(*planes & 1) || (!dspn::kHalf && *math == DSPN_MATH_F32_F16X2 && ldy == Cout && Cout % 32 == 0 && dy_absmax),
+               "conv2d_wgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy == Cout, Cout %% 32 == 0 and the block the planes were cut by (dy_absmax)");
+  DSPN_REQUIRE(!(*planes & 2) || (!dspn::kHalf && *math == DSPN_MATH_F32_F16X2 && Cin % 32 == 0 && x_absmax && !in_scale),
+               "conv2d_wgrad: DSPN_MATH_X_PLANES needs DSPN_MATH_F32_F16X2, Cin %% 32 == 0, no input affine and the block the planes were cut by (x_absmax)");
+  if (const int rc = check_math_mode("conv2d_wgrad", *math)) return rc;
+  return check_math_blocks("conv2d_wgrad", *math, flags, x_absmax, dy_absmax);
+}
+
 int DSPN_FN(dspn_conv2d_wgrad_bn)(const st_t *x, const float *in_scale, const float *in_shift, int in_relu,
                              const st_t *dy, float *dw, int N, int H, int W, int Cin,
                              int Cout, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                              int Wo, int accumulate, int math, const float *x_absmax, const float *dy_absmax,
                              void *workspace, size_t workspace_bytes, void *stream) {
-  DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_wgrad: bad geometry");
-  DSPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv2d_wgrad: in_scale and in_shift go together");
-  const int math_vouch = math & DSPN_MATH_UNSCALED_OK;
-  const int dy_planes = ((math & DSPN_MATH_DY_PLANES) ? 1 : 0) | ((math & DSPN_MATH_X_PLANES) ? 2 : 0);     // bit 0: dy, bit 1: x
-  math &= ~(DSPN_MATH_UNSCALED_OK | DSPN_MATH_DY_PLANES | DSPN_MATH_X_PLANES);
-  DSPN_REQUIRE(!(dy_planes & 1) || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && ldy == Cout && Cout % 32 == 0 && dy_absmax),
-               "conv2d_wgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy == Cout, Cout %% 32 == 0 and the block the planes were cut by (dy_absmax)");
-  DSPN_REQUIRE(!(dy_planes & 2) || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && Cin % 32 == 0 && x_absmax && !in_scale),
-               "conv2d_wgrad: DSPN_MATH_X_PLANES needs DSPN_MATH_F32_F16X2, Cin %% 32 == 0, no input affine and the block the planes were cut by (x_absmax)");
-  DSPN_REQUIRE(math >= DSPN_MATH_FP32 && math <= DSPN_MATH_F32_F16X2, "conv2d_wgrad: math is one of DSPN_MATH_*");
-  DSPN_REQUIRE(dspn::kHalf || math != DSPN_MATH_F32_F16X2 || math_vouch || (x_absmax && dy_absmax),
-               "conv2d_wgrad: DSPN_MATH_F32_F16X2 needs the magnitude block of both operands (dspn_absmax_f32); a caller who knows that every |operand| < 65504 passes math | DSPN_MATH_UNSCALED_OK");
+  int planes = 0;
+  if (const int rc = wgrad_check(&math, &planes, N, H, W, Cin, Cout, ldy, Ho, Wo, in_scale, in_shift, x_absmax, dy_absmax)) return rc;
   const int nb = std::min(batch_chunk(N, (long long)sizeof(st_t) * H * W * Cin),
                           batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy));
   for (int n0 = 0; n0 < N; n0 += nb) {
     const int n = std::min(nb, N - n0);
-    const int rc = conv2d_wgrad_one(math, OpScales{dy_absmax, x_absmax, dy_planes}, x + (long long)n0 * H * W * Cin, InAffine{in_scale, in_shift, in_relu},
+    const int rc = conv2d_wgrad_one(math, OpScales{dy_absmax, x_absmax, planes}, x + (long long)n0 * H * W * Cin, InAffine{in_scale, in_shift, in_relu},
                                     dy + (long long)n0 * Ho * Wo * ldy, dw, n, H, W,
                                     Cin, Cout, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, accumulate || n0 > 0,
                                     workspace, workspace_bytes, stream);
@@ -2612,7 +2605,7 @@ int dspn_conv2d_wgrad_splits(int N, int Ho, int Wo, int Cin, int Cout, int R, in
   const long long P = (long long)N * Ho * Wo;
   const int J = R * S * Cin;
   if (P <= 0 || J <= 0 || Cout <= 0) return 0;
-  return wgrad_plan(P, Cout, J, R * S > 1 ? 4ll * P * Cin * std::min(stride, 2) * std::min(stride, 2) : 0).splits;
+  return wgrad_plan(P, Cout, J, wgrad_x_footprint(P, Cin, R * S, stride)).splits;
 }
 #endif
 
@@ -2622,22 +2615,12 @@ int DSPN_FN(dspn_conv2d_wgrad_slabs)(const st_t *x, const float *in_scale, const
                                 const st_t *dy, float *slabs, size_t slabs_bytes, int N, int H, int W, int Cin,
                                 int Cout, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                                 int Wo, int math, const float *x_absmax, const float *dy_absmax, void *stream) {
-  DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_wgrad: bad geometry");
-  DSPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv2d_wgrad: in_scale and in_shift go together");
-  const int math_vouch = math & DSPN_MATH_UNSCALED_OK;
-  const int dy_planes = ((math & DSPN_MATH_DY_PLANES) ? 1 : 0) | ((math & DSPN_MATH_X_PLANES) ? 2 : 0);     // bit 0: dy, bit 1: x
-  math &= ~(DSPN_MATH_UNSCALED_OK | DSPN_MATH_DY_PLANES | DSPN_MATH_X_PLANES);
-  DSPN_REQUIRE(!(dy_planes & 1) || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && ldy == Cout && Cout % 32 == 0 && dy_absmax),
-               "conv2d_wgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy == Cout, Cout %% 32 == 0 and the block the planes were cut by (dy_absmax)");
-  DSPN_REQUIRE(!(dy_planes & 2) || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && Cin % 32 == 0 && x_absmax && !in_scale),
-               "conv2d_wgrad: DSPN_MATH_X_PLANES needs DSPN_MATH_F32_F16X2, Cin %% 32 == 0, no input affine and the block the planes were cut by (x_absmax)");
-  DSPN_REQUIRE(math >= DSPN_MATH_FP32 && math <= DSPN_MATH_F32_F16X2, "conv2d_wgrad: math is one of DSPN_MATH_*");
-  DSPN_REQUIRE(dspn::kHalf || math != DSPN_MATH_F32_F16X2 || math_vouch || (x_absmax && dy_absmax),
-               "conv2d_wgrad: DSPN_MATH_F32_F16X2 needs the magnitude block of both operands (dspn_absmax_f32); a caller who knows that every |operand| < 65504 passes math | DSPN_MATH_UNSCALED_OK");
+  int planes = 0;
+  if (const int rc = wgrad_check(&math, &planes, N, H, W, Cin, Cout, ldy, Ho, Wo, in_scale, in_shift, x_absmax, dy_absmax)) return rc;
   DSPN_REQUIRE(std::min(batch_chunk(N, (long long)sizeof(st_t) * H * W * Cin),
                         batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy)) == N,
                "conv2d_wgrad_slabs: tensors of 2 GiB or more need dspn_conv2d_wgrad_f32");
-  return conv2d_wgrad_one(math, OpScales{dy_absmax, x_absmax, dy_planes}, x, InAffine{in_scale, in_shift, in_relu}, dy, nullptr, N, H, W, Cin, Cout, ldy, R, S, stride,
+  return conv2d_wgrad_one(math, OpScales{dy_absmax, x_absmax, planes}, x, InAffine{in_scale, in_shift, in_relu}, dy, nullptr, N, H, W, Cin, Cout, ldy, R, S, stride,
                           pad_h, pad_w, dil, Ho, Wo, 0, slabs, slabs_bytes, stream);
 }
 

@@ -65,17 +65,26 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 }
 
 
-// conv_wide.hip: which wide tile a plane-fed layer runs on: 0 none (conv_nt_kernel), 1 256 x 128, 2 128 x 256 (8 waves, one
-// workgroup per CU), 3 128 x 128 on four waves (two workgroups per CU), 4 256 x 64 on four waves (Cout <= 64, 64-row
-// BatchNorm tables); M output points, nk k-steps of 32 channels
-int wide_tile_choice(long long M, int Cout, int nk, int fused_epilogue);
-// conv_wide.hip: one launch of the wide family (shape 1: 256 x 128, 2: 128 x 256, 3: 128 x 128 on four waves) -- both operands
-// piece planes, vector epilogue, at least one tap (dispatch_nt checks)
-int launch_wide(int shape, const float *in, const float *w_planes, const float *bias, float *out, const ConvGeomT<float> &g,
+// The wide tile family (conv_wide.hip).  A member is a tile and the kernel that feeds it: P* take both operands as piece planes
+// (conv_ntw_kernel; bfloat16 tensors: the tensors themselves), F* a float A operand that the loader cuts, with or without the
+// folded BatchNorm affine (conv_ntv_kernel).  256 x 128 and 128 x 256 run on eight waves (one workgroup per CU), 128 x 128 and
+// 256 x 64 (Cout <= 64, 64-row BatchNorm tables) on four (two per CU).
+enum class WideTile { None, P256x128, P128x256, P128x128, P256x64, F128x256, F128x128, F256x64 };
+// ... and the loop a call takes: Plain = the round-5 loop with the staged epilogue; Spanning = the next tile's first operands
+// are requested before the epilogue of the current one (XT); Direct = the round-5 loop with the direct epilogue (F* only)
+enum class WideLoop { Plain, Spanning, Direct };
+struct WideRoute {
+  WideTile tile = WideTile::None; WideLoop loop = WideLoop::Plain;
+  explicit operator bool() const { return tile != WideTile::None; }
+};
+// the route of one call (M output points, nk k-steps) that is legal for the family -- vector epilogue, at least one tap, no split-K,
+// A a pure copy or a float tensor: dispatch_nt checks; every run-time setting and environment knob of the family is evaluated here, once
+WideRoute wide_route(const ConvGeomT<float> &g, long long M, int nk);
+WideRoute wide_route(const ConvGeomT<__bf16> &g, long long M, int nk);
+// one launch of the family; bfloat16 tensors (conv_wide_h.hip): whole 64-channel blocks, no input affine
+int launch_wide(WideRoute r, const float *in, const float *w_planes, const float *bias, float *out, const ConvGeomT<float> &g,
                 hipStream_t s, const float *residual);
-// ... and on bfloat16 tensors (conv_wide_h.hip): the activations / weight copies themselves are the operands; whole 64-channel
-// blocks, no input affine
-int launch_wide(int shape, const __bf16 *in, const __bf16 *w, const float *bias, __bf16 *out, const ConvGeomT<__bf16> &g,
+int launch_wide(WideRoute r, const __bf16 *in, const __bf16 *w, const float *bias, __bf16 *out, const ConvGeomT<__bf16> &g,
                 hipStream_t s, const __bf16 *residual);
 
 // conv_wide.hip (conv_stem.h): the 7x7 / 2, pad 3, 4 -> 64 channel stem convolution in the two-piece math with BatchNorm

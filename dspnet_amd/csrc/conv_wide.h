@@ -50,29 +50,6 @@ struct WideStamps {
 #define DSPN_STAMP_PARAM
 #endif
 
-// dspn_conv_set_tile_spanning / DSPN_XT=0: the tile-spanning loop off (tests, same-box A/B runs; the results do not depend on it)
-inline bool xt_enabled() { return dspn::tile_spanning() != 0; }
-// The eight-wave 128 x 256 member on the tile-spanning loop too: bit-identical (tests/test_wide_tiles_gpu.py) and small on the step --
-// its layers have 36+ k-steps and one to four tiles per workgroup, the epilogue is a tenth of a tile: 954.6 -> 958.8 images/s
-// (+0.2 ... +0.5 % in each of four alternating pairs on one box, beside the float-operand kernels' direct epilogue).  Default;
-// DSPN_XT8=0 keeps it on the round-5 loop (A/B runs).
-inline bool xt_wide8_enabled() {
-  static const bool on = [] { const char *e = getenv("DSPN_XT8"); return !e || atoi(e) != 0; }();
-  return on;
-}
-// The 256 x 64 members (<= 64 output columns, 64-row statistics tiles: stage 1 of the ResNets) on the round-6 loops too: bit-identical
-// stored tensors (tests), +0.2 ... +0.5 % on the step in each of three alternating pairs on one box.  Default; DSPN_XT64=0 keeps
-// them on the round-5 loops (A/B runs).
-inline bool xt_c64_enabled() {
-  static const bool on = [] { const char *e = getenv("DSPN_XT64"); return !e || atoi(e) != 0; }();
-  return on;
-}
-// ... whose direct epilogue addresses the output (and the tensors of its shape) as one buffer of M rows of ldc elements
-inline bool xt_output_ok(const ConvGeom &g, const int bm = 128) {
-  const long long M = (long long)g.N * g.Hg * g.Wg;
-  return g.dense && (g.flags & 16) && M % bm == 0 && M * g.ldc * (long long)sizeof(st_t) < (1ll << 31);
-}
-
 // The tile epilogue of the wide family, from the staged fp32 tile in LDS (st[row * (BN + 4) + col], written by the caller, which
 // has NOT yet met the barrier that publishes it) to the stored outputs and BatchNorm tables; ends with the barrier after which
 // the LDS may be overwritten.  conv_nt_kernel's epilogue per 128-row half: same arithmetic, same tables.
@@ -1240,7 +1217,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntv_kernel(
   }
 }
 
-template <int WAVES_M, int WAVES_N, bool INTF, int EPI, int SR, int XT = 0>
+template <int WAVES_M, int WAVES_N, bool INTF, int EPI, int SR, int XT>
 int launch_ntv_impl(const float *in, const float *w, const float *bias, float *out, const ConvGeom &g, hipStream_t s,
                     const float *residual) {
   constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64;
@@ -1251,67 +1228,37 @@ int launch_ntv_impl(const float *in, const float *w, const float *bias, float *o
                      : XT == 2 ? (size_t)2 * (BM + BN) * 128         // (the exchange lies inside ring slot 1)
                                : std::max<size_t>((size_t)2 * (BM + BN) * 128, sizeof(float) * BM * (BN + 4));
   static_assert(XT != 2 || (size_t)(BM + BN) * 128 >= sizeof(float) * 2 * WAVES_M * BN * 6, "the exchange fits a ring slot");
-  auto kern = conv_ntv_kernel<WAVES_M, WAVES_N, INTF, EPI, SR, XT>;
-  static dspn::KernelDeviceState st;
-  const bool first = !st.slots[0] && !st.slots[1];
-  const int dev = dspn::ensure_persistent_grid(reinterpret_cast<const void *>(kern), WAVES_M * WAVES_N * 64, lds, st, "conv_ntv");
-  if (dev < 0) return dev;
-  const int slots = st.slots[dev], slots_per_cu = st.slots_per_cu[dev], slots_cus = st.cus[dev];
-  if (first && getenv("DSPN_DEBUG_PRINT"))
-    fprintf(stderr, "[dspn] conv_ntv<%d,%d,intf=%d,epi=%d,xt=%d>: %zu B LDS, occupancy %d/CU x %d CUs -> grid %d\n", WAVES_M, WAVES_N,
-            (int)INTF, EPI, (int)XT, lds, slots_per_cu, slots_cus, slots);
-  const int reserved = dspn::reserved_cus();
-  const int avail = reserved > 0 ? std::max(8, slots_per_cu * std::max(8, slots_cus - reserved) / 8 * 8) : slots;
-  const int grid_x = (int)std::min<long long>((long long)mt * nt, avail);
+  constexpr auto kern = conv_ntv_kernel<WAVES_M, WAVES_N, INTF, EPI, SR, XT>;
+  const int grid_x = dspn::persistent_grid<kern>(WAVES_M * WAVES_N * 64, lds, (long long)mt * nt, "conv_ntv",
+                                                 "conv_ntv<%d,%d,intf=%d,epi=%d,xt=%d>", WAVES_M, WAVES_N, (int)INTF, EPI, (int)XT);
+  if (grid_x < 0) return grid_x;
   {
     dspn::ProfScope prof(0, s);
     hipLaunchKernelGGL(kern, dim3(grid_x), dim3(WAVES_M * WAVES_N * 64), lds, s, in, w, bias, out, g, mt, nt, residual);
   }
   return dspn::check_launch("conv_ntv");
 }
-template <int WAVES_M, int WAVES_N, int SR = 128>
-int launch_ntv(const float *in, const float *w, const float *bias, float *out, const ConvGeom &g, hipStream_t s, const float *residual) {
-#define DSPN_NTV_(T, X) \
-  (g.bn_sums ? launch_ntv_impl<WAVES_M, WAVES_N, T, 2, SR, X>(in, w, bias, out, g, s, residual) \
-   : g.stats ? launch_ntv_impl<WAVES_M, WAVES_N, T, 1, SR, X>(in, w, bias, out, g, s, residual) \
-             : launch_ntv_impl<WAVES_M, WAVES_N, T, 0, SR, X>(in, w, bias, out, g, s, residual))
-  if constexpr (WAVES_M == 2 && WAVES_N == 2 && SR == 128) {
-    const int nk = g.TR * g.TS * (g.Cin / 32);
-    // Measured (scratch/r06/xt_bench.hip, profiles/r06_xt_*): the float-operand member gains 5 - 15 % in isolation where the
-    // epilogue is a large share of the tile (K <= 256) and a workgroup walks several tiles, and LOSES inside the training step:
-    // its hot calls add a residual (the conv3 of every unit), and with the next tile's rows held in registers across the
-    // epilogue there is room for 2 - 4 residual rows in flight per lane where the staged epilogue keeps 16 (281 -> 305 us on
-    // the stage-1 conv3 layers).  Setting 2 of dspn_conv_set_tile_spanning routes it (experiments); the default does not.
-    const long long tiles = (((long long)g.N * g.Hg * g.Wg + 127) / 128) * ((g.Cout + 127) / 128);
-    if (dspn::tile_spanning() >= 2 && nk >= 2 && nk <= 8 && nk % 2 == 0 && tiles >= 2048 && xt_output_ok(g))
-      return g.in_scale ? DSPN_NTV_(true, 1) : DSPN_NTV_(false, 1);
-    // The direct epilogue ALONE (XT = 2: the round-5 loop, nothing held across the epilogue): measured on the step, three
-    // alternating runs on one box: 948.4 -> 953.9 images/s, conv family 27.04 -> 26.66 ms.  Default at setting >= 1;
-    // DSPN_NTV_DIRECT=0 keeps the staged epilogue (A/B runs).
-    static const bool direct_only = [] { const char *e = getenv("DSPN_NTV_DIRECT"); return !e || atoi(e) != 0; }();
-    if (direct_only && xt_enabled() && nk >= 2 && xt_output_ok(g))
-      return g.in_scale ? DSPN_NTV_(true, 2) : DSPN_NTV_(false, 2);
-  }
-  if constexpr (WAVES_M == 2 && WAVES_N == 4 && SR == 128) {
-    // ... and on the eight-wave 128 x 256 member: 953.9 -> 955.6 images/s (+0.1 ... +0.3 % in each of three alternating pairs);
-    // DSPN_NTV_DIRECT8=0 keeps the staged epilogue
-    static const bool direct8 = [] { const char *e = getenv("DSPN_NTV_DIRECT8"); return !e || atoi(e) != 0; }();
-    const int nk = g.TR * g.TS * (g.Cin / 32);
-    if (direct8 && xt_enabled() && nk >= 2 && xt_output_ok(g))
-      return g.in_scale ? DSPN_NTV_(true, 2) : DSPN_NTV_(false, 2);
-  }
-  if constexpr (WAVES_M == 4 && WAVES_N == 1 && SR == 64) {      // the 256 x 64 member (xt_c64_enabled)
-    const int nk = g.TR * g.TS * (g.Cin / 32);
-    if (xt_c64_enabled() && xt_enabled() && nk >= 2 && xt_output_ok(g, 256))
-      return g.in_scale ? DSPN_NTV_(true, 2) : DSPN_NTV_(false, 2);
-  }
-  return g.in_scale ? DSPN_NTV_(true, 0) : DSPN_NTV_(false, 0);
+// one member on the loop wide_route chose (XT: 0 Plain, 1 Spanning -- members with SPANS only --, 2 Direct): the epilogue and the input affine
+template <int WAVES_M, int WAVES_N, int SR, int XT>
+int launch_ntv_on(const float *in, const float *w, const float *bias, float *out, const ConvGeom &g, hipStream_t s, const float *residual) {
+#define DSPN_NTV_(T) \
+  (g.bn_sums ? launch_ntv_impl<WAVES_M, WAVES_N, T, 2, SR, XT>(in, w, bias, out, g, s, residual) \
+   : g.stats ? launch_ntv_impl<WAVES_M, WAVES_N, T, 1, SR, XT>(in, w, bias, out, g, s, residual) \
+             : launch_ntv_impl<WAVES_M, WAVES_N, T, 0, SR, XT>(in, w, bias, out, g, s, residual))
+  return g.in_scale ? DSPN_NTV_(true) : DSPN_NTV_(false);
 #undef DSPN_NTV_
+}
+template <int WAVES_M, int WAVES_N, int SR = 128, bool SPANS = false>
+int launch_ntv(WideLoop loop, const float *in, const float *w, const float *bias, float *out, const ConvGeom &g, hipStream_t s,
+               const float *residual) {
+  if constexpr (SPANS) if (loop == WideLoop::Spanning) return launch_ntv_on<WAVES_M, WAVES_N, SR, 1>(in, w, bias, out, g, s, residual);
+  return loop == WideLoop::Direct ? launch_ntv_on<WAVES_M, WAVES_N, SR, 2>(in, w, bias, out, g, s, residual)
+                                  : launch_ntv_on<WAVES_M, WAVES_N, SR, 0>(in, w, bias, out, g, s, residual);
 }
 #endif   // !DSPN_HALF
 
-// host side: one launch of the wide family.  Persistent grid as conv_nt_kernel's (occupancy x CUs, a multiple of 8).
-template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR, bool XT = false>
+// host side: one launch of the wide family.  Persistent grid as conv_nt_kernel's (dspn::persistent_grid).
+template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR, bool XT>
 int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s,
                     const st_t *residual) {
   constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64;
@@ -1321,42 +1268,26 @@ int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out,
   // eight waves keep it in the ring slot of the tile's last k-step)
   const size_t lds = XT ? (size_t)STAGES * (BM + BN) * 128 + ((WAVES_M * WAVES_N == 8 || BM == 256) ? 0 : sizeof(float) * 4 * BN * 6)
                         : std::max<size_t>((size_t)STAGES * (BM + BN) * 128, sizeof(float) * BM * (BN + 4));
-  auto kern = conv_ntw_kernel<WAVES_M, WAVES_N, STAGES, EPI, SR, XT>;
-  static dspn::KernelDeviceState st;
-  const bool first = !st.slots[0] && !st.slots[1];
-  const int dev = dspn::ensure_persistent_grid(reinterpret_cast<const void *>(kern), WAVES_M * WAVES_N * 64, lds, st, "conv_ntw");
-  if (dev < 0) return dev;
-  const int slots = st.slots[dev], slots_per_cu = st.slots_per_cu[dev], slots_cus = st.cus[dev];
-  if (first && getenv("DSPN_DEBUG_PRINT"))
-    fprintf(stderr, "[dspn] conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d>: %zu B LDS, occupancy %d/CU x %d CUs -> grid %d\n", WAVES_M, WAVES_N,
-            STAGES, EPI, (int)XT, lds, slots_per_cu, slots_cus, slots);
-  const int reserved = dspn::reserved_cus();
-  const int avail = reserved > 0 ? std::max(8, slots_per_cu * std::max(8, slots_cus - reserved) / 8 * 8) : slots;
-  const int grid_x = (int)std::min<long long>((long long)mt * nt, avail);
+  constexpr auto kern = conv_ntw_kernel<WAVES_M, WAVES_N, STAGES, EPI, SR, XT>;
+  const int grid_x = dspn::persistent_grid<kern>(WAVES_M * WAVES_N * 64, lds, (long long)mt * nt, "conv_ntw",
+                                                 "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d>", WAVES_M, WAVES_N, STAGES, EPI, (int)XT);
+  if (grid_x < 0) return grid_x;
   {
     dspn::ProfScope prof(0, s);
     hipLaunchKernelGGL(kern, dim3(grid_x), dim3(WAVES_M * WAVES_N * 64), lds, s, in, w, bias, out, g, mt, nt, residual);
   }
   return dspn::check_launch("conv_ntw");
 }
-
-template <int WAVES_M, int WAVES_N, int STAGES, int SR = 128>
-int launch_ntw(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s, const st_t *residual) {
-#ifndef DSPN_HALF
-  if constexpr ((WAVES_M == 2 && SR == 128) || (WAVES_M == 4 && WAVES_N == 1 && SR == 64)) {
-    // the four-wave 128 x 128 tile, the eight-wave 128 x 256 tile (xt_wide8_enabled) and the 256 x 64 tile of the <= 64-column
-    // layers (xt_c64_enabled) on layers of at least STAGES k-steps
-    const int nk = g.TR * g.TS * (g.Cin / 32);
-    if (xt_enabled() && nk >= STAGES && xt_output_ok(g, WAVES_M * 64) &&
-        (WAVES_M == 4 ? xt_c64_enabled() : (WAVES_N == 2 || xt_wide8_enabled()))) {
-      if (g.bn_sums) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, true>(in, w, bias, out, g, s, residual);
-      if (g.stats) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 1, SR, true>(in, w, bias, out, g, s, residual);
-      return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 0, SR, true>(in, w, bias, out, g, s, residual);
-    }
-  }
-#endif
-  if (g.bn_sums) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR>(in, w, bias, out, g, s, residual);
-  if (g.stats) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 1, SR>(in, w, bias, out, g, s, residual);
-  return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 0, SR>(in, w, bias, out, g, s, residual);
+// one member on the round-5 loop or (SPANS: the member has it; wide_route chose it) the tile-spanning one: the epilogue
+template <int WAVES_M, int WAVES_N, int STAGES, int SR, bool XT>
+int launch_ntw_on(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s, const st_t *residual) {
+  if (g.bn_sums) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT>(in, w, bias, out, g, s, residual);
+  if (g.stats) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 1, SR, XT>(in, w, bias, out, g, s, residual);
+  return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 0, SR, XT>(in, w, bias, out, g, s, residual);
 }
-
+template <int WAVES_M, int WAVES_N, int STAGES, int SR = 128, bool SPANS = false>
+int launch_ntw(WideLoop loop, const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s,
+               const st_t *residual) {
+  if constexpr (SPANS) if (loop == WideLoop::Spanning) return launch_ntw_on<WAVES_M, WAVES_N, STAGES, SR, true>(in, w, bias, out, g, s, residual);
+  return launch_ntw_on<WAVES_M, WAVES_N, STAGES, SR, false>(in, w, bias, out, g, s, residual);
+}

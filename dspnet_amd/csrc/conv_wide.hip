@@ -8,7 +8,6 @@
 #include "conv_geom.h"
 #include "../../include/dspn_nn.h"
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -19,6 +18,7 @@ using dspn::u32x4_t;
 using dspn::conv::f32x16;
 using dspn::conv::bf16x8;
 using dspn::conv::xcd_remap;
+using dspn::conv::WideLoop;
 using ConvGeom = dspn::conv::ConvGeomT<st_t>;
 #include "conv_wide.h"
 #ifndef DSPN_HALF
@@ -92,44 +92,100 @@ int dspn_tile_minmax_f32(const float *x, long long rows, int C, int tile_rows, f
 namespace dspn {
 namespace conv {
 #ifndef DSPN_HALF
+int launch_stem(const float *x, const float *w, float *y, int N, int H, int W, int Cin, int Cout, int Ho, int Wo,
+                const float *x_absmax, const float *w_absmax, float *stats, float *minmax, hipStream_t s) {
+  return launch_conv_stem(x, w, y, N, H, W, Cin, Cout, Ho, Wo, x_absmax, w_absmax, stats, minmax, s);
+}
+#endif   // !DSPN_HALF
 // dspn_conv_set_wide_tiles(mode): 0 automatic, 1 never, 2 / 3 / 4 always that shape where it is legal (tests, experiments) -- a
 // launch setting: the K order and the accumulation order per output are the same on every tile.
 // Automatic choice, measured on MI355X (scratch/r05/ntw_check.py, profiles/r05_ntw_check_*.txt; plain / fused-epilogue time of
 // the stage-3 3x3 layer: conv_nt_kernel 125 / 148 us, 256 x 128 119 / 118, 128 x 256 110 / 110, 128 x 128 on four waves 111 / 112):
 // the four-wave tile wins or ties on every layer of the headline graph -- two workgroups per CU cover each other's epilogue,
 // which the one-workgroup-per-CU tiles expose -- and is the only one that also pays on the short-K 1x1 layers.
-int wide_tile_choice(long long M, int Cout, int nk, int fused_epilogue) {
+static WideTile wide_tile_choice(long long M, int Cout, int nk, int fused_epilogue) {
+  constexpr WideTile forced[5] = {WideTile::None, WideTile::None, WideTile::P256x128, WideTile::P128x256, WideTile::P128x128};
   const int mode = dspn::wide_tiles_mode();
-  if (mode == 1) return 0;
-  if (mode >= 2) return Cout <= 64 ? 4 : mode - 1;
+  if (mode == 1) return WideTile::None;
+  if (mode >= 2) return Cout <= 64 ? WideTile::P256x64 : forced[mode];
   // one or two k-steps (K = 32 / 64): the kernels are all epilogue -- the wide family's costs less with BatchNorm statistics
   // or BatchNorm-backward sums in it (K = 64: 250 -> 229 us forward, 323 -> 259 us data gradient at 128 x 128 x 32 images),
   // the plain one is a tie
-  if (Cout <= 64) return nk >= 4 ? 4 : 0;      // 64 output columns (stage 1): 256 x 64 on four waves
-  if (nk < 4 && !(fused_epilogue && nk >= 2)) return 0;
+  if (Cout <= 64) return nk >= 4 ? WideTile::P256x64 : WideTile::None;      // 64 output columns (stage 1): 256 x 64 on four waves
+  if (nk < 4 && !(fused_epilogue && nk >= 2)) return WideTile::None;
   // 128 x 256 where it divides the columns, fills the chip and the k-loop is long enough to matter (K >= 256, N = 512: 155 / 172
   // against 179 / 190 us on four waves, plain / fused); the four-wave tile everywhere else
-  if (Cout % 256 == 0 && nk >= 8 && ((M + 127) / 128) * (Cout / 256) >= 256) return 2;
-  return 3;
+  if (Cout % 256 == 0 && nk >= 8 && ((M + 127) / 128) * (Cout / 256) >= 256) return WideTile::P128x256;
+  return WideTile::P128x128;
 }
-int launch_stem(const float *x, const float *w, float *y, int N, int H, int W, int Cin, int Cout, int Ho, int Wo,
-                const float *x_absmax, const float *w_absmax, float *stats, float *minmax, hipStream_t s) {
-  return launch_conv_stem(x, w, y, N, H, W, Cin, Cout, Ho, Wo, x_absmax, w_absmax, stats, minmax, s);
-}
-#endif   // !DSPN_HALF
-int launch_wide(int shape, const st_t *in, const st_t *w_planes, const float *bias, st_t *out, const ConvGeomT<st_t> &g,
-                hipStream_t s, const st_t *residual) {
-  if (shape == 1) return launch_ntw<4, 2, 3>(in, w_planes, bias, out, g, s, residual);
-  if (shape == 2) return launch_ntw<2, 4, 3>(in, w_planes, bias, out, g, s, residual);
-  if (shape == 3) return launch_ntw<2, 2, 2>(in, w_planes, bias, out, g, s, residual);
-  if (shape == 4) return launch_ntw<4, 1, 2, 64>(in, w_planes, bias, out, g, s, residual);      // 256 x 64, 64-row BatchNorm tables
+WideRoute wide_route(const ConvGeomT<st_t> &g, long long M, int nk) {
+  WideRoute r{wide_tile_choice(M, g.Cout, nk, (g.stats || g.bn_sums) ? 1 : 0)};
 #ifndef DSPN_HALF
-  // 10 + shape: the A operand is a float tensor (cut, and optionally affine-transformed, in the loader): conv_ntv_kernel
-  if (shape == 12) return launch_ntv<2, 4>(in, w_planes, bias, out, g, s, residual);
-  if (shape == 13) return launch_ntv<2, 2>(in, w_planes, bias, out, g, s, residual);
-  if (shape == 14) return launch_ntv<4, 1, 64>(in, w_planes, bias, out, g, s, residual);
+  if (!r) return r;
+  // a float A operand (with or without the folded BatchNorm affine) goes through the family's register-staged members; there
+  // is no 256 x 128 one: 128 x 128 on four waves
+  if (!g.a_planes)
+    r.tile = r.tile == WideTile::P128x256 ? WideTile::F128x256 : r.tile == WideTile::P256x64 ? WideTile::F256x64 : WideTile::F128x128;
+  // dspn_conv_set_tile_spanning / DSPN_XT: 0 = every member on the round-5 loop (tests, same-box A/B runs; the results do not
+  // depend on it), 1 = the default, 2 = the float-operand 128 x 128 member on the tile-spanning loop as well
+  const int xt = dspn::tile_spanning();
+  const int bm = (r.tile == WideTile::P256x64 || r.tile == WideTile::F256x64) ? 256 : 128;
+  // the direct epilogue addresses the output (and the tensors of its shape) as one buffer of M rows of ldc elements
+  const bool output_ok = g.dense && (g.flags & 16) && M % bm == 0 && M * g.ldc * (long long)sizeof(st_t) < (1ll << 31);
+  if (xt == 0 || !output_ok) return r;
+  if (r.tile == WideTile::P128x128) {      // a ring of two slots
+    if (nk >= 2) r.loop = WideLoop::Spanning;
+  } else if (r.tile == WideTile::P128x256) {      // ... of three
+    // The eight-wave 128 x 256 member on the tile-spanning loop too: bit-identical (tests/test_wide_tiles_gpu.py) and small on
+    // the step -- its layers have 36+ k-steps and one to four tiles per workgroup, the epilogue is a tenth of a tile: 954.6 ->
+    // 958.8 images/s (+0.2 ... +0.5 % in each of four alternating pairs on one box, beside the float-operand kernels' direct
+    // epilogue).  Default; DSPN_XT8=0 keeps it on the round-5 loop (A/B runs).
+    static const bool wide8 = dspn::env_int("DSPN_XT8", 1) != 0;
+    if (nk >= 3 && wide8) r.loop = WideLoop::Spanning;
+  } else if (bm == 256) {
+    // The 256 x 64 members (<= 64 output columns, 64-row statistics tiles: stage 1 of the ResNets) on the round-6 loops too:
+    // bit-identical stored tensors (tests), +0.2 ... +0.5 % on the step in each of three alternating pairs on one box.
+    // Default; DSPN_XT64=0 keeps them on the round-5 loops (A/B runs).
+    static const bool c64 = dspn::env_int("DSPN_XT64", 1) != 0;
+    if (nk >= 2 && c64) r.loop = r.tile == WideTile::P256x64 ? WideLoop::Spanning : WideLoop::Direct;
+  } else if (r.tile == WideTile::F128x128 && xt >= 2 && nk >= 2 && nk <= 8 && nk % 2 == 0 &&
+             ((M + 127) / 128) * ((g.Cout + 127) / 128) >= 2048) {
+    // Measured (scratch/r06/xt_bench.hip, profiles/r06_xt_*): the float-operand member gains 5 - 15 % in isolation where the
+    // epilogue is a large share of the tile (K <= 256) and a workgroup walks several tiles, and LOSES inside the training step:
+    // its hot calls add a residual (the conv3 of every unit), and with the next tile's rows held in registers across the
+    // epilogue there is room for 2 - 4 residual rows in flight per lane where the staged epilogue keeps 16 (281 -> 305 us on
+    // the stage-1 conv3 layers).  Setting 2 of dspn_conv_set_tile_spanning routes it (experiments); the default does not.
+    r.loop = WideLoop::Spanning;
+  } else if (r.tile == WideTile::F128x128) {
+    // The direct epilogue ALONE (the round-5 loop, nothing held across the epilogue): measured on the step, three
+    // alternating runs on one box: 948.4 -> 953.9 images/s, conv family 27.04 -> 26.66 ms.  Default at setting >= 1;
+    // DSPN_NTV_DIRECT=0 keeps the staged epilogue (A/B runs).
+    static const bool direct = dspn::env_int("DSPN_NTV_DIRECT", 1) != 0;
+    if (nk >= 2 && direct) r.loop = WideLoop::Direct;
+  } else if (r.tile == WideTile::F128x256) {
+    // ... and on the eight-wave 128 x 256 member: 953.9 -> 955.6 images/s (+0.1 ... +0.3 % in each of three alternating pairs);
+    // DSPN_NTV_DIRECT8=0 keeps the staged epilogue
+    static const bool direct8 = dspn::env_int("DSPN_NTV_DIRECT8", 1) != 0;
+    if (nk >= 2 && direct8) r.loop = WideLoop::Direct;
+  }      // (256 x 128: the round-5 loop only)
 #endif
-  return dspn::fail(DSPN_ERR_ARG_, "conv: no wide tile shape %d", shape);
+  return r;
+}
+// (a loop is instantiated only for the members wide_route gives it to: the template flags; bfloat16 tensors have the round-5 loop only)
+int launch_wide(WideRoute r, const st_t *in, const st_t *w_planes, const float *bias, st_t *out, const ConvGeomT<st_t> &g,
+                hipStream_t s, const st_t *residual) {
+  switch (r.tile) {
+    case WideTile::P256x128: return launch_ntw<4, 2, 3>(r.loop, in, w_planes, bias, out, g, s, residual);
+    case WideTile::P128x256: return launch_ntw<2, 4, 3, 128, !kHalf>(r.loop, in, w_planes, bias, out, g, s, residual);
+    case WideTile::P128x128: return launch_ntw<2, 2, 2, 128, !kHalf>(r.loop, in, w_planes, bias, out, g, s, residual);
+    case WideTile::P256x64: return launch_ntw<4, 1, 2, 64, !kHalf>(r.loop, in, w_planes, bias, out, g, s, residual);      // 64-row BatchNorm tables
+#ifndef DSPN_HALF
+    case WideTile::F128x256: return launch_ntv<2, 4>(r.loop, in, w_planes, bias, out, g, s, residual);
+    case WideTile::F128x128: return launch_ntv<2, 2, 128, true>(r.loop, in, w_planes, bias, out, g, s, residual);
+    case WideTile::F256x64: return launch_ntv<4, 1, 64>(r.loop, in, w_planes, bias, out, g, s, residual);
+#endif
+    default: return dspn::fail(DSPN_ERR_ARG_, "conv: no wide tile shape %d", (int)r.tile);
+  }
 }
 }  // namespace conv
 }  // namespace dspn

@@ -1,8 +1,10 @@
 // Shared host-side helpers of the dspnet_amd HIP library (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #define DSPN_OK_ 0
@@ -21,6 +23,9 @@ inline int fail(int code, const char *fmt, ...) {
   va_end(ap);
   return code;
 }
+
+// an integer knob of the environment, `dflt` when unset (a knob read once per process is kept in a static by its reader)
+inline long long env_int(const char *name, long long dflt) { const char *e = getenv(name); return e ? atoll(e) : dflt; }
 
 inline int check_launch(const char *what) {
   hipError_t e = hipGetLastError();
@@ -71,12 +76,8 @@ inline int ensure_dynamic_lds(const void *kern, size_t bytes, KernelDeviceState 
 }
 // occupancy of a persistent kernel on the current device: workgroups per CU and CUs (cached per device in st)
 inline int ensure_persistent_grid(const void *kern, int threads, size_t lds, KernelDeviceState &st, const char *what) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices)
-    return fail(DSPN_ERR_LAUNCH_, "%s: no current device (or an index past %d)", what, kMaxDevices - 1);
-  if (st.slots[dev]) return dev;
-  const int d2 = ensure_dynamic_lds(kern, lds, st, what);
-  if (d2 < 0) return d2;
+  const int dev = ensure_dynamic_lds(kern, lds, st, what);
+  if (dev < 0 || st.slots[dev]) return dev;
   int per_cu = 0, cus = 0;
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -85,6 +86,26 @@ inline int ensure_persistent_grid(const void *kern, int threads, size_t lds, Ker
   st.slots_per_cu[dev] = per_cu; st.cus[dev] = cus > 0 ? cus : 1;
   st.slots[dev] = per_cu * st.cus[dev] / 8 * 8 > 8 ? per_cu * st.cus[dev] / 8 * 8 : 8;
   return dev;
+}
+// The grid width of one launch of the persistent kernel Kern (per-device state of its own) over `tiles` tiles, or a negative
+// status: as many workgroups as the chip holds at once (occupancy x CUs, a multiple of 8 so that a workgroup's tiles t, t + grid,
+// ... stay on its XCD's run of the tile order), at most one per tile; each walks its tiles.  dspn_conv_set_reserved_cus(k): the
+// grid leaves k CUs' worth of workgroup slots free, so that the kernels of another queue (RCCL's all-reduce of the gradient
+// buckets) find room beside a convolution instead of only between two.  name_fmt, name_args: the kernel's name (DSPN_DEBUG_PRINT).
+template <auto Kern, typename... NameArgs>
+int persistent_grid(int threads, size_t lds, long long tiles, const char *what, const char *name_fmt, NameArgs... name_args) {
+  static KernelDeviceState st;
+  const bool first = !st.slots[0] && !st.slots[1];
+  const int dev = ensure_persistent_grid(reinterpret_cast<const void *>(Kern), threads, lds, st, what);
+  if (dev < 0) return dev;
+  if (first && getenv("DSPN_DEBUG_PRINT")) {
+    char name[160];
+    snprintf(name, sizeof(name), name_fmt, name_args...);
+    fprintf(stderr, "[dspn] %s: %zu B LDS, occupancy %d/CU x %d CUs -> grid %d\n", name, lds, st.slots_per_cu[dev], st.cus[dev], st.slots[dev]);
+  }
+  const int reserved = reserved_cus();
+  const int avail = reserved > 0 ? std::max(8, st.slots_per_cu[dev] * std::max(8, st.cus[dev] - reserved) / 8 * 8) : st.slots[dev];
+  return (int)std::min<long long>(tiles, avail);
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

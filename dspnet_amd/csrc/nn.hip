@@ -237,7 +237,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 constexpr int kTileGroup = 32;
 // tables at least this long are pre-reduced (DSPN_TILE_GROUP_MIN: timing experiments)
 static int tile_group_min() {
-  static const int v = [] { const char *e = getenv("DSPN_TILE_GROUP_MIN"); return e ? atoi(e) : 1024; }();
+  static const int v = (int)dspn::env_int("DSPN_TILE_GROUP_MIN", 1024);
   return v;
 }
 // mm / mm_out (MODE 0, optional): the per-tile (min, max) table of the same tiles, merged into one pair per group

@@ -136,6 +136,18 @@ def test_convolution_argument_validation_without_gpu():
     assert wgrad(3 | 0x400, Cin=48) == -1 and b"DSPN_MATH_X_PLANES" in lib.dspn_last_error()
     assert wgrad(3 | 0x400, x_absmax=None) == -1 and b"DSPN_MATH_X_PLANES" in lib.dspn_last_error()
     assert wgrad(3 | 0x400, in_scale=p) == -1 and b"DSPN_MATH_X_PLANES" in lib.dspn_last_error()
+    # the slab-only entry shares those checks: same status, same text as the _bn entry for the same bad call
+    def slabs(math, Cin=64, x_absmax=p, in_scale=None, in_shift=None):
+        return lib.dspn_conv2d_wgrad_slabs_f32(p, in_scale, in_shift, 0, p, p, 1 << 20, 1, 8, 8, Cin, 64, 64, 3, 3, 1, 1, 1, 1, 8, 8, math,
+                                               x_absmax, p, None)
+    for kw in (dict(math=2 | 0x400), dict(math=3 | 0x400, Cin=48), dict(math=3 | 0x400, x_absmax=None),
+               dict(math=3 | 0x400, in_scale=p)):
+        rc, text = wgrad(**kw), lib.dspn_last_error()
+        assert rc == -1 and b"DSPN_MATH_X_PLANES" in text
+        assert slabs(in_shift=kw.get("in_scale"), **kw) == rc and lib.dspn_last_error() == text
+    assert slabs(4) == -1 and b"math is one of DSPN_MATH_*" in lib.dspn_last_error()
+    assert slabs(0, in_scale=p) == -1 and b"in_scale and in_shift go together" in lib.dspn_last_error()
+    assert slabs(0, in_shift=p) == -1 and b"in_scale and in_shift go together" in lib.dspn_last_error()
     assert lib.dspn_bn_apply_planes_f32(p, p, p, p, 64, 48, 1, p, None) == -1 and b"multiple of 32" in lib.dspn_last_error()
     assert lib.dspn_bn_apply_planes_f32(p, p, p, p, 64, 64, 1, None, None) == -1      # the block the planes are cut by
     assert lib.dspn_bn_apply_planes_f32(p, p, p, ctypes.c_void_p(256), 64, 64, 1, p, None) == -1 and b"in place" in lib.dspn_last_error()
@@ -148,6 +160,27 @@ def test_convolution_argument_validation_without_gpu():
     assert lib.dspn_conv2d_weight_transpose_tiles(64, 9, 64, 32) == 0                # Cout_pad < Cout
     assert lib.dspn_conv2d_weight_transpose_batch_f32(None, 1, 4, None) == -1
     assert lib.dspn_conv2d_weight_planes_tiles(64, 9, 64, 64, 1) == 2 * 9 * 2 and lib.dspn_conv2d_weight_planes_tiles(40, 1, 64, 64, 1) == 4
+
+
+def test_convolution_plan_queries_are_pinned(monkeypatch):
+    """tests/golden/conv_plan_queries.json: the five pure queries by which callers size statistics tables, BatchNorm-sum
+    tables, slab buffers and workspaces answer as they did when the fixture was written, for every layer shape of the graphs
+    and the edge cases (tile configuration and the x footprint of the weight-gradient plan feed all of them)"""
+    import importlib.util
+    import json
+    for knob in ("DSPN_WG_TILE", "DSPN_WG_SPLITS"):           # read on every call
+        monkeypatch.delenv(knob, raising=False)
+    assert not any(k in os.environ for k in ("DSPN_NT_MINTILES", "DSPN_NT_CFG64")), "run with the DSPN_* knobs unset"
+    golden = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_conv_plan_queries_golden", os.path.join(golden, "make_conv_plan_queries_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "conv_plan_queries.json")) as f:
+        doc = json.load(f)
+    lib = _lib.lib()
+    assert len(doc["rows"]) >= 200 and [tuple(r["args"]) for r in doc["rows"]] == gen.cases()
+    for row in doc["rows"]:
+        assert gen.query(lib, tuple(row["args"])) == row["results"], row["args"]
 
 
 def test_oracle_is_clean_under_address_and_ub_sanitizers():
