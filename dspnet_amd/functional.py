@@ -142,6 +142,12 @@ _lib.register({
     "dspn_distance_boxes_workspace_bytes": (_sz, [_i]),
     "dspn_distance_boxes_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 })
+# include/dspn_monitor.h
+_lib.register({
+    "dspn_tensor_stats_chunk_elems": (_i, []),
+    "dspn_tensor_stats_workspace_bytes": (_sz, [_i, _ll]),
+    "dspn_tensor_stats": (_i, [_vp, _i, _ll, _vp, _vp, _sz, _vp]),
+})
 
 
 class BnMoving(_c.Structure):
@@ -1237,6 +1243,76 @@ def distance_boxes(det, hh, ww, score_thresh, mode, max_boxes, out=None, sync=Tr
 def check_box_count(count, max_boxes):
     if count > max_boxes:
         raise _lib.DspnError("distance_boxes: %d rows selected, room for max_boxes = %d" % (count, max_boxes))
+
+
+# ------------------------------------------------------------------ per-tensor statistics (training monitor)
+# include/dspn_monitor.h dspn_stats_row (40 bytes) and dspn_stats_out (48 bytes)
+STATS_ROW_FIELDS = [("base", "<u8"), ("rows", "<i8"), ("first_chunk", "<i8"), ("C", "<i4"), ("ld", "<i4"), ("dtype", "<i4"),
+                    ("reserved", "<i4")]
+STATS_OUT_FIELDS = [("sumsq", "<f8"), ("sum", "<f8"), ("n_nan", "<u8"), ("n_posinf", "<u8"), ("n_neginf", "<u8"),
+                    ("absmax", "<f4"), ("reserved", "<i4")]
+_STATS_DTYPES = {torch.float32: (0, 4), torch.bfloat16: (1, 2)}      # DSPN_STATS_F32 / DSPN_STATS_BF16, bytes per element
+
+
+def tensor_stats_chunk_elems():
+    """the fixed chunk length of tensor_stats, in logical elements"""
+    return int(L().dspn_tensor_stats_chunk_elems())
+
+
+def tensor_stats_entry(t, C=None):
+    """the table entry (base, dtype, rows, C, ld) of a contiguous tensor: flat, or -- C given -- rows of t.shape[-1]
+    elements of which the first C count (an NHWC activation whose channels are padded)"""
+    assert t.is_contiguous(), "tensor_stats: contiguous tensors only"
+    ld = int(t.shape[-1]) if t.dim() else 1
+    if C is None or int(C) == ld:
+        return (t.data_ptr(), t.dtype, 1, t.numel(), t.numel())
+    return (t.data_ptr(), t.dtype, t.numel() // ld, int(C), ld)
+
+
+def tensor_stats_table(entries, device):
+    """entries: [(base address, torch.float32 | torch.bfloat16, rows, C, ld)], one per tensor: rows * C logical elements, row r
+    at element r * ld of base, lanes C .. ld - 1 padding that is never counted -> (device table, n_rows, n_chunks) for
+    tensor_stats.  The rows are checked here: the kernel trusts them.  The caller keeps the tensors alive."""
+    if not 0 < len(entries) < (1 << 31):
+        raise ValueError("tensor_stats_table: need at least one row, got %d" % len(entries))
+    chunk = tensor_stats_chunk_elems()
+    tab = np.zeros(len(entries), dtype=STATS_ROW_FIELDS)
+    first = 0
+    for i, (base, dtype, rows, C, ld) in enumerate(entries):
+        if dtype not in _STATS_DTYPES:
+            raise ValueError("tensor_stats_table: row %d: dtype %r (float32 or bfloat16)" % (i, dtype))
+        code, size = _STATS_DTYPES[dtype]
+        base, rows, C, ld = int(base), int(rows), int(C), int(ld)
+        if base <= 0 or base % size:
+            raise ValueError("tensor_stats_table: row %d: base 0x%x is null or not aligned to its %d-byte elements" % (i, base, size))
+        if rows < 1 or C < 1 or ld < C or ld >= (1 << 31):
+            raise ValueError("tensor_stats_table: row %d: need rows >= 1 and 1 <= C <= ld < 2^31, got rows %d, C %d, ld %d"
+                             % (i, rows, C, ld))
+        tab[i] = (base, rows, first, C, ld, code, 0)
+        first += (rows * C + chunk - 1) // chunk
+    if first >= (1 << 31):
+        raise ValueError("tensor_stats_table: %d chunks, the launch takes fewer than 2^31" % first)
+    dev = torch.from_numpy(tab.view(np.uint8).copy()).to(device)
+    return dev, len(entries), first
+
+
+def tensor_stats(table, out=None, workspace=None):
+    """table = tensor_stats_table's (device table, n_rows, n_chunks) -> device bytes of n_rows dspn_stats_out records
+    (stats_records reads them): per tensor sumsq, sum and absmax over its finite elements and the counts of NaN, +Inf, -Inf.
+    Two launches on the current stream, nothing waits.  out / workspace: caller-owned uint8 buffers."""
+    dev, n_rows, n_chunks = table
+    nout = n_rows * np.dtype(STATS_OUT_FIELDS).itemsize
+    out = torch.empty(nout, dtype=torch.uint8, device=dev.device) if out is None else out
+    assert out.dtype == torch.uint8 and out.numel() >= nout and out.is_contiguous()
+    ws = _scratch(L().dspn_tensor_stats_workspace_bytes(n_rows, n_chunks), dev.device, "stats") if workspace is None else workspace
+    check(L().dspn_tensor_stats(ptr(dev), n_rows, n_chunks, ptr(out), ptr(ws), ws.numel(), stream()), "tensor_stats")
+    return out
+
+
+def stats_records(out, n_rows=None):
+    """the records of tensor_stats on the host (one device-to-host copy, which waits for the launch)"""
+    dt = np.dtype(STATS_OUT_FIELDS)
+    return (out if n_rows is None else out[:n_rows * dt.itemsize]).cpu().numpy().view(dt)
 
 
 # ------------------------------------------------------------------ losses / optimizer

@@ -215,6 +215,9 @@ class MultiTaskSolver:
         self._ran_eager = False                         # has forward / backward of this solver run outside a recording?
         self._rerecord = False
         self._replays, self.graph_rerecorded = 0, 0     # replays of the recorded step / recordings dropped by the range guard
+        # a train.monitor.Monitor (fit(monitor=...) installs it): on the iterations it is armed for, the step runs eagerly
+        # with its statistics launches after forward, after backward + all-reduce and after the update
+        self.monitor = None
         g = self.g
         owner = {}                 # parameter -> the first node that holds it
         for idx, n in enumerate(g.nodes):
@@ -352,7 +355,8 @@ class MultiTaskSolver:
 
     def _step(self):
         self._calibrate_guard()
-        if self._graph is not None:
+        mon = self.monitor if (self.monitor is not None and self.monitor.armed) else None
+        if self._graph is not None and mon is None:
             # the recorded SGD launch carries lr / momentum / wd BY VALUE: a schedule that moved them since the recording
             # (the reference's optimizer takes an lr_scheduler, multi_solver.py:221) drops the graph and records a new one
             # ... and so does set_params / load_params on a frozen weight: its derived operands are formed outside the recording
@@ -372,11 +376,25 @@ class MultiTaskSolver:
                 self.graph_rerecorded += 1
                 self._rerecord = True
             return
+        # eager: no recording yet, or an iteration the monitor is armed for -- its three statistics launches sit between the
+        # phases of the step (they only read); a recording is kept and replayed again on the following iterations, unless this
+        # pass moved the range guard's decisions away from the ones it was recorded with
+        risk = self.g.guard["risk"]
         self._train_forward()
+        if mon is not None:
+            mon.after_forward()
         self.backward()
+        if mon is not None:
+            mon.after_backward()
         self.update()
+        if mon is not None:
+            mon.after_update()
         self._ran_eager = True
-        if self._rerecord:
+        if self._graph is not None and self.g.guard["risk"] != risk:
+            self._graph = None
+            self.graph_rerecorded += 1
+            self._rerecord = True
+        elif self._rerecord and self._graph is None:
             self._rerecord = False
             self.capture(warmup=0)
 
@@ -456,7 +474,7 @@ def do_checkpoint(prefix):
 
 def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None, epoch_end_callback=None,
         eval_data=None, class_names=None, seg_class_names=None, logger=None, eval_score_thresh=0.25,
-        check_label_errors=True, eval_cityscapes=False, eval_device_depth=False):
+        check_label_errors=True, eval_cityscapes=False, eval_device_depth=False, monitor=None, check_finite=0):
     """The epoch loop of MultiTaskSolver.fit (multi_solver.py:229-345 + the evaluation pass :353-436): per epoch
     train_data.reset(), metric reset, one solver.step() per batch with the MultiBoxMetric / CustomAccuracyMetric
     read-outs, batch_end_callback(BatchEndParam), epoch_end_callback(epoch, net), the 'Train-<name>' log lines, and
@@ -471,7 +489,11 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
     An evaluation batch may carry its disparity maps as batch.disparity ((B, hh, ww), uint16 or float32, host array or
     device tensor): they go to evaluate_net as 'disparity' and the distance metric ('derror', per-class errors) is scored;
     a batch without the attribute leaves it out, as before.  eval_device_depth: evaluate_net's `device_depth` argument
-    (the box medians of that metric taken on the device; the values are the host metric's)."""
+    (the box medians of that metric taken on the device; the values are the host metric's).
+    monitor: a train.monitor.Monitor (mx.mon.Monitor, train_multitask.py:249 / :317): installed on the net once, tic() before and
+    toc_print() after every step, as Module.fit does.  check_finite=N: every N-th step one statistics pass over the rows of the
+    gradient arena and the loss outputs, read at the metric read-out; a NaN or an infinity raises DspnError naming up to eight
+    tensors with their counts.  0 (default): no launch, no read."""
     import logging
     from .metric import CustomAccuracyMetric, MultiBoxMetric
     logger = logger or logging
@@ -485,6 +507,13 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
     has_seg = getattr(net, "seg_out", None) is not None
     acc_metric = CustomAccuracyMetric(num_classes=net.seg_out.C) if has_seg else None
     history = []
+    if monitor is not None:
+        monitor.install(net)
+        solver.monitor = monitor
+    finite = None
+    if check_finite:
+        from .monitor import FiniteCheck
+        finite = FiniteCheck(net, check_finite)
     for epoch in range(begin_epoch, num_epoch):
         nbatch = 0
         train_data.reset()
@@ -495,10 +524,18 @@ def fit(solver, train_data, begin_epoch=0, num_epoch=1, batch_end_callback=None,
             batch, _ = train_data.next()
             nbatch += 1
             solver.set_batch(batch.data[0], batch.label[0], batch.label[1])
+            if monitor is not None:
+                monitor.tic()
             solver.step()
+            if finite is not None:
+                finite.launch()
             multibox_metric.update(net)
             if acc_metric is not None:
                 acc_metric.update([net.label_seg.data], [net.seg_out.prob.data])
+            if finite is not None:
+                finite.read()
+            if monitor is not None:
+                monitor.toc_print()
             if check_label_errors and getattr(net, "target", None) is not None:
                 net.target.raise_on_errors()
             if batch_end_callback is not None:
