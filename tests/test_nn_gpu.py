@@ -362,7 +362,11 @@ def test_affine_sampler_matches_torch_grid_sample(gpu_device, theta, shapes):
         dth = torch.zeros(6, device="cuda")
         fn.affine_sampler_backward_theta(src, th_dev, dyc, dth)
         # at the identity grid a source of the target's own height or width is sampled exactly ON its pixels, where the
-        # interpolation has a kink (left / right derivative differ): d/d theta is compared off the kinks only
+        # interpolation has a kink (left / right derivative differ): d/d theta is compared off the kinks only.  This 16 x 12
+        # grid is not exact in float32 (-1 + wo * (2 / 11) rounds), so the float32 coordinate can fall into the other floor
+        # cell than the float64 one and the one-sided derivative taken depends on that rounding: no reference is fixed here.
+        # The kinks ARE checked, bit for bit, where the coordinates are exact: test_sampler_edges_gpu.py section a (targets
+        # 17 x 17, 33 x 17, 65 x 65 with dyadic thetas, same-size sources at the identity grid among them)
         kink = tuple(theta) == (1, 0, 0, 0, 1, 0) and any(h == Ho or w == Wo for h, w in shapes)
         if not kink:
             close(dth.cpu().double(), th.grad, 1e-4)
