@@ -4,10 +4,15 @@ detect/multitask_detector.py:99-163 loads the saved TRAINING symbol, binds zero 
 `seg_out_label`, runs forward(is_train=True) per image and reads outputs[3] (det_out) and outputs[4]
 (seg probabilities); rows with id >= 0 are detections (:268-271) and the seg map is the arg-max over
 the class axis (:263).  det_out does not depend on MultiBoxTarget, so this forward-only path runs the
-test graph (`get_multi_symbol`): same det / seg values, no target / loss kernels.  Image decoding,
-resizing and drawing (cv2) are outside the hot path."""
+test graph (`get_multi_symbol`): same det / seg values, no target / loss kernels.  Image decoding (cv2.imread,
+cv2.VideoCapture) stays outside; the demo's picture -- resize, boxes, class colours, legend -- is made on the device
+(`visualize_detection` / `detect_and_visualize`, detect/render.py)."""
+import ctypes
+
+import numpy as np
 import torch
 
+from .. import _lib
 from .. import functional as fn
 from ..symbol.multitask_symbol_factory import get_multi_symbol
 
@@ -37,6 +42,7 @@ class Detector:
         if aux_params is not None:
             self.net.g.set_aux(aux_params, allow_missing=not use_global_stats)
         self.mean = torch.tensor(mean_pixels, dtype=torch.float32, device=self.device).view(1, 3, 1, 1)
+        self.mean_pixels = tuple(float(m) for m in mean_pixels)
 
     def forward(self, data=None):
         """data: (B,3,H,W) float32 device tensor, RGB, mean already subtracted (dataset/iterator.py:570-571)"""
@@ -62,3 +68,66 @@ class Detector:
             rows = det[b]
             out.append(rows[(rows[:, 0] >= 0) & (rows[:, 1] > thresh)])
         return out, fn.nhwc_to_nchw(self.net.seg_out.prob.data, self.net.seg_out.C)
+
+    def visualize_detection(self, img, dets, seg_prob, classes, thresh=0.6):
+        """detect/multitask_detector.py:336-399 on the device -> (B, H + H + 30, W, 3) uint8 RGB: the image with boxes and
+        tags, the class colours at image size, the legend.  img: device uint8 (B, H, W, 3) RGB frames, or the net's input
+        (B, 3, H, W) float32, shown with this detector's mean added back; dets: (B, N, 7) or per-image (k, 7) row tables;
+        seg_prob: (B, h, w, ld) NHWC scores as `forward` returns them.  Nothing is displayed or written (render.save_png)."""
+        from . import render
+        return render.visualize_detection(img, dets, seg_prob, classes, thresh, mean=self.mean_pixels,
+                                          num_classes=self.net.seg_out.C)
+
+    def detect_and_visualize(self, frames, classes, thresh=0.6, nms_thresh=0.95):
+        """the video branch of detect_and_visualize (:433-456) for a batch of decoded frames: uint8 (B, Hs, Ws, 3) BGR,
+        host or device -> (B, H + H + 30, W, 3) uint8 RGB on the device.
+        The reference resizes a frame (`resize(img, 600, 1024)`), crops rows [64:576] unless the aspect is 2, and feeds the
+        result to a net bound to that size.  Here `frame_warp` composes that rule with the scale onto this net's (H, W)
+        -- the identity for the 512 x 1024 model on 16:9 video -- into one affine map, and the existing
+        dspn_augment_batch_u8 applies it as a pure scale warp (the `_get_resized` convention: bilinear, border 0, BGR ->
+        RGB planes, mean subtracted): one interpolation where the reference chains two.  Then forward, the pixel NMS
+        post-filter on [xmin, ymin, xmax, ymax, score] at nms_thresh (:450), and the picture."""
+        from ..dataset import iterator as it
+        from .nms import nms
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+            raise _lib.DspnError("detect_and_visualize: frames are uint8 (B, Hs, Ws, 3)")
+        B, _, H, W = self.net.data.data.shape
+        if frames.shape[0] != B:
+            raise _lib.DspnError("detect_and_visualize: %d frames for a net of batch size %d" % (frames.shape[0], B))
+        Hs, Ws = int(frames.shape[1]), int(frames.shape[2])
+        frames = frames.to(self.device).contiguous()
+        samples = np.zeros(B, it._SAMPLE)
+        samples["img_offset"] = np.arange(B, dtype=np.int64) * (Hs * Ws * 3)
+        samples["seg_offset"] = -1
+        samples["src_h"], samples["src_w"] = Hs, Ws
+        samples["minv"] = it.invert_affine(frame_warp(Hs, Ws, H, W))
+        desc = torch.from_numpy(samples.view(np.uint8).reshape(-1)).to(self.device)
+        data = self.net.data.data
+        _lib.check(it._entry()(frames.data_ptr(), None, desc.data_ptr(), B, H, W, it._CMAP_BGR,
+                               (ctypes.c_double * 3)(*self.mean_pixels), None, data.data_ptr(), None, fn.stream()),
+                   "augment_batch")
+        det, seg_prob = self.forward()
+        det = det.cpu().numpy()
+        rows = []
+        for b in range(B):
+            d = det[b][det[b][:, 0] >= 0]
+            rows.append(d[nms(np.hstack((d[:, 2:6], d[:, 1:2])), nms_thresh)])
+        return self.visualize_detection(data, rows, seg_prob, classes, thresh)
+
+
+def frame_warp(Hs, Ws, H, W, target_size=600, max_size=1024):
+    """forward affine map (2 x 3, row major, source -> net input) of the demo's frame preparation:
+    `resize(img, 600, 1024)` (:45-62: the short side to 600 unless the long side would pass 1024; the new size is
+    cvRound(size * scale)), rows [64:576] unless |width / height - 2| <= .01 (:440-442), then the scale onto (H, W)"""
+    scale = float(target_size) / float(min(Hs, Ws))
+    if np.round(scale * max(Hs, Ws)) > max_size:
+        scale = float(max_size) / float(max(Hs, Ws))
+    rh, rw = int(np.rint(Hs * scale)), int(np.rint(Ws * scale))
+    top, rows = 0, rh
+    if abs(float(rw) / float(rh) - 2.) > .01:
+        top, rows = 64, min(576, rh) - 64
+    if rows <= 0 or rw <= 0:
+        raise _lib.DspnError("frame_warp: a %d x %d frame leaves nothing after the resize and the row crop" % (Hs, Ws))
+    sx, sy = W / float(rw), H / float(rows)
+    return [scale * sx, 0.0, 0.0, 0.0, scale * sy, -top * sy]

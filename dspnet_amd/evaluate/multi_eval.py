@@ -9,7 +9,11 @@ What the reference does per batch, and where it runs here:
   DistanceAccuracyMetric against the disparity maps (:379-384)             -> host, as in the reference; with
       device_depth=True the box medians come from the device (evaluate.distance_eval, dspn_box_rank_select_*)
   (offline, on the PNGs the script writes) Cityscapes IoU / iIoU           -> evaluate.cityscapes_eval (device counts)
-The image display / file writing of the script (cv2) is not part of the numerics contract and is not built."""
+  result images (:344-368): the labelId map at full resolution and the 2 x 2 display mosaic, per image
+                                                                           -> results_dir=...: label_ids(prob_upsampling)
+      and detect.render.display_results (device), written as PNG files; no window is opened"""
+import os
+
 import numpy as np
 import torch
 
@@ -55,7 +59,8 @@ def filter_detections(det, score_thresh=0.1):
 
 
 def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use_difficult=False,
-                 voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False, device_depth=False):
+                 voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False, device_depth=False,
+                 results_dir=None):
     """net: training graph (symbol.multitask_symbol_factory.get_multi_symbol_train); batches: iterable of dicts with
     'data' (B,3,H,W), 'label_det' (B,L,6), 'label_seg' (B,H/4,W/4) and optionally 'disparity' (B,hh,ww) host maps.
     -> dict name -> value, plus 'class_maps' (list of uint8 device tensors) when full_res=(H, W) is given.
@@ -67,7 +72,18 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
     device_depth=True: the distance metric reads the device's unfiltered detections and takes every box median on the
     device (distance_eval.DeviceDistanceAccuracyMetric; 'disparity' may then be a device tensor, uint16 or float32);
     the box table is sized from det_out, B * N rows, so no batch the host path scores can overflow it; the values are
-    those of the host metric, which stays the default."""
+    those of the host metric, which stays the default.
+    results_dir: a directory; per image the script's two files (multi_eval.py:355, :366) are written below it:
+    results/<name>, the labelId map at full_res (default 1024 x 2048), and output/<name with labelTrainIds -> output>, the
+    display_results mosaic.  <name> is the base name of batch['fnames'][i] (the label image's path, as the iterator gives
+    it), or '%06d_gtFine_labelTrainIds.png' of the running image index.  None (the default) launches nothing, imports
+    nothing and writes nothing."""
+    render = image_index = None
+    if results_dir is not None:
+        from ..detect import render
+        image_index = 0
+        for sub in ("results", "output"):
+            os.makedirs(os.path.join(results_dir, sub), exist_ok=True)
     multibox_metric = MultiBoxMetric()
     acc_metric = CustomAccuracyMetric(num_classes=len(seg_class_names))
     if device_depth:
@@ -96,6 +112,17 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
         det_metric.update([batch["label_det"][:, :, :5]], [pred_det[:, :, :6]])
         if full_res is not None:
             class_maps.append(prob_upsampling(seg_prob, full_res, len(seg_class_names)))
+        if render is not None:
+            ids = label_ids(class_maps[-1] if full_res is not None else
+                            prob_upsampling(seg_prob, (1024, 2048), len(seg_class_names)))
+            mosaic = render.display_results(net.data.data, net.label_seg.data, seg_prob, list(pred_det), net.label_det.data,
+                                            list(class_names), num_classes=len(seg_class_names))
+            for i in range(mosaic.shape[0]):
+                name = (os.path.basename(batch["fnames"][i]) if batch.get("fnames") else
+                        "%06d_gtFine_labelTrainIds.png" % image_index)
+                render.save_png(os.path.join(results_dir, "results", name), ids[i])
+                render.save_png(os.path.join(results_dir, "output", name.replace("labelTrainIds", "output")), mosaic[i])
+                image_index += 1
         if city_metric is not None:
             gt_ids = batch["gt_label_ids"]
             if full_res is not None and tuple(gt_ids.shape[-2:]) != tuple(int(v) for v in full_res):

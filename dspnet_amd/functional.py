@@ -148,6 +148,15 @@ _lib.register({
     "dspn_tensor_stats_workspace_bytes": (_sz, [_i, _ll]),
     "dspn_tensor_stats": (_i, [_vp, _i, _ll, _vp, _vp, _sz, _vp]),
 })
+# include/dspn_render.h
+_lib.register({
+    "dspn_render_chunk_rows": (_i, []),
+    "dspn_render_classmap_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "dspn_render_labels_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "dspn_render_data_f32": (_i, [_vp, _i, _i, _i, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _vp, _i, _i, _i, _i, _vp]),
+    "dspn_render_check_draw_rows": (_i, [_vp, _i, _vp, _i]),
+    "dspn_render_draw_list_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+})
 
 
 class BnMoving(_c.Structure):
@@ -1243,6 +1252,101 @@ def distance_boxes(det, hh, ww, score_thresh, mode, max_boxes, out=None, sync=Tr
 def check_box_count(count, max_boxes):
     if count > max_boxes:
         raise _lib.DspnError("distance_boxes: %d rows selected, room for max_boxes = %d" % (count, max_boxes))
+
+
+# ------------------------------------------------------------------ display images (include/dspn_render.h)
+# dspn_draw_row: nine int32
+DRAW_ROW_FIELDS = [("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("r", "<i4"), ("g", "<i4"),
+                   ("b", "<i4"), ("arg", "<i4")]
+DRAW_OUTLINE, DRAW_FILL, DRAW_GLYPH = 0, 1, 2      # DSPN_DRAW_*
+RENDER_FONT_BYTES = 665                            # DSPN_RENDER_FONT_BYTES
+
+
+def render_chunk_rows():
+    """DSPN_RENDER_CHUNK_ROWS: draw rows of one image staged in LDS at a time"""
+    return int(L().dspn_render_chunk_rows())
+
+
+def _canvas_args(canvas, B):
+    assert canvas.dim() == 4 and canvas.shape[3] == 3 and canvas.dtype == torch.uint8 and canvas.is_contiguous(), \
+        (canvas.dtype, tuple(canvas.shape))
+    assert canvas.shape[0] == B, (canvas.shape[0], B)
+    return int(canvas.shape[1]), int(canvas.shape[2])
+
+
+def _index_table(t, n):
+    assert t.dtype == torch.int32 and t.numel() == n and t.is_contiguous(), (t.dtype, t.numel(), n)
+    return ptr(t)
+
+
+def _palette_arg(palette):
+    assert palette.dtype == torch.uint8 and palette.numel() == 768 and palette.is_contiguous(), (palette.dtype, palette.numel())
+    return ptr(palette)
+
+
+def render_classmap(scores, C, palette, ysrc, xsrc, canvas, y0=0, x0=0):
+    """scores (B, h, w, ld >= C) NHWC float32 -> the (len(ysrc), len(xsrc)) panel at (y0, x0) of canvas (B, CH, CW, 3) uint8:
+    palette[first argmax over channels 0..C-1 of scores[b, ysrc[y], xsrc[x]]]; palette (256, 3) uint8, ysrc / xsrc int32,
+    all on the device (dspn_render_classmap_f32)"""
+    assert scores.dim() == 4 and scores.dtype == torch.float32 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape))
+    B, h, w, ld = scores.shape
+    CH, CW = _canvas_args(canvas, B)
+    Hd, Wd = ysrc.numel(), xsrc.numel()
+    check(L().dspn_render_classmap_f32(ptr(scores), B, h, w, int(C), ld, _palette_arg(palette), _index_table(ysrc, Hd),
+                                       _index_table(xsrc, Wd), Hd, Wd, ptr(canvas), CH, CW, int(y0), int(x0), stream()),
+          "render_classmap")
+    return canvas
+
+
+def render_labels(labels, palette, ysrc, xsrc, canvas, y0=0, x0=0):
+    """labels (B, h, w) float32 holding 0..255 -> panel of palette[uint8(label)] (dspn_render_labels_f32)"""
+    assert labels.dim() == 3 and labels.dtype == torch.float32 and labels.is_contiguous(), (labels.dtype, tuple(labels.shape))
+    B, h, w = labels.shape
+    CH, CW = _canvas_args(canvas, B)
+    Hd, Wd = ysrc.numel(), xsrc.numel()
+    check(L().dspn_render_labels_f32(ptr(labels), B, h, w, _palette_arg(palette), _index_table(ysrc, Hd), _index_table(xsrc, Wd),
+                                     Hd, Wd, ptr(canvas), CH, CW, int(y0), int(x0), stream()), "render_labels")
+    return canvas
+
+
+def render_data(data, channel_map, mean, canvas, y0=0, x0=0):
+    """data (B, 3, H, W) float32 planes -> the H x W panel: sat_u8(trunc(double(data[channel_map[c]]) + mean[c]))
+    (dspn_render_data_f32)"""
+    assert data.dim() == 4 and data.shape[1] == 3 and data.dtype == torch.float32 and data.is_contiguous(), (data.dtype, tuple(data.shape))
+    B, _, H, W = data.shape
+    CH, CW = _canvas_args(canvas, B)
+    check(L().dspn_render_data_f32(ptr(data), B, H, W, (_c.c_int * 3)(*[int(v) for v in channel_map]),
+                                   (_c.c_double * 3)(*[float(v) for v in mean]), ptr(canvas), CH, CW, int(y0), int(x0), stream()),
+          "render_data")
+    return canvas
+
+
+def draw_table(rows_per_image, device):
+    """rows_per_image: for every image a sequence of (kind, x0, y0, x1, y1, r, g, b, arg) -> (rows, row_start, R): the device
+    table of dspn_draw_row and the (B + 1,) int32 row_start; the host table is checked first (dspn_render_check_draw_rows)"""
+    counts = [len(r) for r in rows_per_image]
+    row_start = np.zeros(len(counts) + 1, np.int32)
+    row_start[1:] = np.cumsum(counts)
+    R = int(row_start[-1])
+    flat = np.zeros(max(R, 1), DRAW_ROW_FIELDS)
+    if R:
+        flat[:R] = np.array([tuple(int(v) for v in row) for rows in rows_per_image for row in rows], DRAW_ROW_FIELDS)
+    check(L().dspn_render_check_draw_rows(flat.ctypes.data, R, row_start.ctypes.data, len(counts)), "draw_table")
+    return (torch.from_numpy(flat.view(np.int32).reshape(-1, 9)).to(device), torch.from_numpy(row_start).to(device), R)
+
+
+def render_draw_list(canvas, table, font, y0=0, x0=0, Hd=None, Wd=None):
+    """paints table = (rows, row_start, R) (draw_table) into the (Hd, Wd) panel at (y0, x0) of canvas -- the whole canvas by
+    default -- in painter's order; font: RENDER_FONT_BYTES device bytes (dspn_render_draw_list_u8)"""
+    rows, row_start, R = table
+    B = row_start.numel() - 1
+    CH, CW = _canvas_args(canvas, B)
+    Hd, Wd = CH - int(y0) if Hd is None else int(Hd), CW - int(x0) if Wd is None else int(Wd)
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= 9 * R and row_start.dtype == torch.int32
+    assert font.dtype == torch.uint8 and font.numel() == RENDER_FONT_BYTES and font.is_contiguous()
+    check(L().dspn_render_draw_list_u8(ptr(canvas), B, CH, CW, int(y0), int(x0), Hd, Wd, ptr(rows), R, ptr(row_start), ptr(font),
+                                       stream()), "render_draw_list")
+    return canvas
 
 
 # ------------------------------------------------------------------ per-tensor statistics (training monitor)
