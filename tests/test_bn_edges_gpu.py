@@ -51,6 +51,7 @@ import torch
 
 from dspnet_amd import functional as fn
 from bf16_twins import BF
+from fp_bars import ulp32, bf16_of, within, bf16_within
 
 pytestmark = pytest.mark.gpu
 
@@ -70,47 +71,6 @@ def slab_rows_for(rows):
 def slabs_of(rows, C):
     """the slab count the library uses, read back from its workspace size: 4 * (slabs * 2 * C + 4 * C) bytes"""
     return (fn.L().dspn_bn_workspace_bytes(rows, C) // 4 - 4 * C) // (2 * C)
-
-
-def ulp32(v):
-    """spacing of float32 at |v| (float64 tensor; 0 at 0)"""
-    v = v.abs().float().double()
-    _, e = torch.frexp(v)
-    return torch.where(v == 0, torch.zeros_like(v), torch.ldexp(torch.ones_like(v), e - 24))
-
-
-def bf16_of(v):
-    """round-to-nearest-even bfloat16 of a float64 tensor, straight from the float64 bits (8 of the 53 significant bits stay)"""
-    b = v.contiguous().view(torch.int64)
-    return ((b + ((1 << 44) - 1) + ((b >> 45) & 1)) & ~((1 << 45) - 1)).view(F64)
-
-
-def within(got, exp, bound, what):
-    """element-wise derived bound on float64 tensors of one shape; nothing is excluded"""
-    err = (got - exp).abs()
-    print(f"    {what}: worst err {float(err.max()):.3e}, largest bar {float(torch.as_tensor(bound).max()):.3e}")
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite result"
-    over = err - bound
-    assert not bool((over > 0).any()), f"{what}: {int((over > 0).sum())} over the bar, worst by {float(over.max()):.3e}"
-
-
-def bf16_within(got, exp, bound, emul32, what):
-    """rule 4 of the docstring for a bfloat16 result; emul32: a float32 CPU evaluation of the same quantity"""
-    assert got.dtype == BF
-    r, n = bf16_of(exp), exp.numel()
-    pre = int((emul32.to(BF).double() != r).sum())
-    assert pre < 1e-3 * n or pre <= 1, f"{what}: the inputs are unfit, float32 and float64 references differ in {pre} of {n} bf16 results"
-    g = got.cpu().double()
-    assert bool(torch.isfinite(g).all()), f"{what}: non-finite result"
-    lo, hi = bf16_of(exp - bound), bf16_of(exp + bound)
-    out = int(((g < lo) | (g > hi)).sum())
-    step = ulp32(r) * 65536.0
-    # (where the float bar itself exceeds half a bf16 step -- a dx that cancels to almost nothing -- [lo, hi] above is the bar)
-    far = int((((g - r).abs() > step) & (bound <= 0.5 * step)).sum())
-    diff = int((g != r).sum())
-    print(f"    {what}: {diff} of {n} differ from bf16(reference) (CPU float32 evaluation: {pre}), {out} outside the bar, "
-          f"{far} further than one bf16 step; worst err {float((g - exp).abs().max()):.3e}")
-    assert out == 0 and far == 0 and (diff < 1e-3 * n or diff <= 1), what
 
 
 def h64(t):
