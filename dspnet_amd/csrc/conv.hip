@@ -1976,8 +1976,30 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
   if (kHalf) wide_ok = wide_ok && !g.in_scale && g.Cin % 64 == 0 && dspn::wide_tiles_mode() >= 2;
   else wide_ok = wide_ok && pre && g.bf16 == 3;       // (pre: whole 32-channel blocks, the weights as piece planes)
   // (whole channel blocks per tap there: nk is the family's k-step count)
-  if (const dspn::conv::WideRoute route = wide_ok ? dspn::conv::wide_route(g, M, nk) : dspn::conv::WideRoute{})
-    return dspn::conv::launch_wide(route, in, w, bias, out, g, s, residual);
+  const dspn::conv::WideRoute route = wide_ok ? dspn::conv::wide_route(g, M, nk) : dspn::conv::WideRoute{};
+  if (g.sadd) {
+    // The strided addend (ConvGeom::sadd) exists in the direct epilogue of the plane-fed 128-row members on the tile-spanning
+    // loop, with BatchNorm-backward sums: the calls the conv1 data gradients of the projection units are.  Everything else is
+    // refused HERE, by name -- there is no second implementation to fall back to; the caller keeps the accumulate path.
+    constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd);
+    if (kHalf) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend takes float tensors only", who);
+    if (g.bf16 != 3) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs DSPN_MATH_F32_F16X2", who);
+    if (splits > 1) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend cannot be combined with split-K (%d splits)", who, splits);
+    if (!g.bn_sums) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs the BatchNorm-backward sums (bn_sums)", who);
+    if (!g.dense || g.ldc != g.Cout || (g.flags & (1 | 2 | 4 | 8)) || residual)
+      return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs a dense dx written by this call alone (no accumulate)", who);
+    // (W % 4 == 0, W >= 8: a group of four rows of the epilogue lies inside one image row and starts at an even column)
+    if (g.sadd_h != (g.Hg + 1) / 2 || g.sadd_w != (g.Wg + 1) / 2 || g.Wg < 8 || g.Wg % 4 != 0)
+      return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend is (N, ceil(H / 2), ceil(W / 2), Cin) with W >= 8 and W %% 4 == 0, got %d x %d for %d x %d", who,
+                        g.sadd_h, g.sadd_w, g.Hg, g.Wg);
+    if (!((route.tile == dspn::conv::WideTile::P128x128 || route.tile == dspn::conv::WideTile::P128x256) &&
+          route.loop == dspn::conv::WideLoop::Spanning))
+      return dspn::fail(DSPN_ERR_ARG_, "%s: no kernel takes the strided addend on this route (it needs dy as piece planes, N H W %% 128 == 0 "
+                        "and the plane-fed 128-row tiles on the tile-spanning loop)", who);
+    g.sadd_bytes = (unsigned)((long long)sizeof(st_t) * g.N * g.sadd_h * g.sadd_w * g.Cout);      // (a quarter of dx, which the route bounds below 2 GiB)
+    if (g.probe) return 0;
+  }
+  if (route) return dspn::conv::launch_wide(route, in, w, bias, out, g, s, residual);
   const int rc = cfg == 0 && eight ? launch_nt<4, 2, 1, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
                  : cfg == 0        ? launch_nt<2, 2, 2, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
                  : cfg == 1        ? launch_nt<2, 2, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
@@ -2349,6 +2371,8 @@ int dspn_conv2d_weight_prepare_batch_bf16(const void *table, int n, long long to
 // dx (N,H,W,Cin_x) from dy (N,Ho,Wo,ldy) and wt = transposed weights [Cin_x][R*S][ldy].
 // Also the forward of a transposed convolution (x := dy).
 struct BnBwd { const st_t *x; const float *scale, *shift, *mean, *rstd; int relu; float *sums; float *dy_absmax; };
+// the strided addend of a dense data gradient (ConvGeom::sadd); probe: ask dispatch_nt for its verdict only
+struct StridedAddend { const st_t *p; int h, w, probe; };
 
 // row tiles of the launches of one data gradient, in launch order (stride 2: up to 4 parity classes)
 static int dgrad_tiles(int N, int H, int W, int Cin, int stride, int *per_class /* [4] or NULL */) {
@@ -2367,7 +2391,7 @@ static int dgrad_tiles(int N, int H, int W, int Cin, int stride, int *per_class 
 static int conv2d_dgrad_one(int math, OpScales scales, const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
                           int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                           int Wo, int dx_ldc, int accumulate, BnBwd bn, void *workspace, size_t workspace_bytes,
-                          void *stream) {
+                          void *stream, StridedAddend sa = StridedAddend{nullptr, 0, 0, 0}) {
   DSPN_REQUIRE(dy && (wt || wt_planes) && dx, "conv2d_dgrad: null pointer");
   DSPN_REQUIRE(ldy % kEPC == 0, "conv2d_dgrad: dy channel stride must be a multiple of %d", kEPC);
   DSPN_REQUIRE(stride == 1 || (stride == 2 && dil == 1), "conv2d_dgrad: stride 1, or stride 2 with dilation 1");
@@ -2387,6 +2411,7 @@ static int conv2d_dgrad_one(int math, OpScales scales, const st_t *dy, const st_
   g.bn_relu = bn.relu; g.bn_sums = bn.sums; g.bn_tile_base = 0;
   g.bn_dy_absmax = (bn.sums && !kHalf && math == DSPN_MATH_F32_F16X2) ? reinterpret_cast<unsigned *>(bn.dy_absmax) : nullptr;
   g.a_planes = scales.a_planes;
+  g.sadd = sa.p; g.sadd_h = sa.h; g.sadd_w = sa.w; g.probe = sa.probe;
   int class_tiles[4] = {0, 0, 0, 0};
   if (bn.sums) dgrad_tiles(N, H, W, Cin, stride, class_tiles);
   hipStream_t s = (hipStream_t)stream;
@@ -2428,14 +2453,21 @@ static int dgrad_bn_tiles(int N, int H, int W, int Cin, int stride) {
 int dspn_conv2d_dgrad_bn_tiles(int N, int H, int W, int Cin, int stride) { return dgrad_bn_tiles(N, H, W, Cin, stride); }
 #endif
 
-int DSPN_FN(dspn_conv2d_dgrad_bn)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
+}  // extern "C"
+static int conv2d_dgrad_bn_impl(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
                              int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                              int Wo, int dx_ldc, int accumulate,
                              const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
                              const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
                              int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
-                             void *stream) {
+                             void *stream, StridedAddend sa) {
   DSPN_REQUIRE(N > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_dgrad: bad geometry");
+  if (sa.p) {      // (what the arguments alone decide; the route is dispatch_nt's)
+    constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd);
+    DSPN_REQUIRE(stride == 1 && !accumulate, "%s: the strided addend goes with a stride-1 data gradient that is the only writer of dx (no accumulate)", who);
+    DSPN_REQUIRE((dx_ldc <= 0 || dx_ldc == Cin), "%s: the strided addend needs a dense dx (dx_ldc %d, Cin %d)", who, dx_ldc, Cin);
+    DSPN_REQUIRE(batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy) == N, "%s: dy of 2 GiB or more", who);
+  }
   const int flags = split_math(&math, DSPN_MATH_DY_PLANES), dy_planes = (flags & DSPN_MATH_DY_PLANES) ? 1 : 0;
   DSPN_REQUIRE(!dy_planes || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && ldy % 32 == 0 && dy_absmax),
                "conv2d_dgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy %% 32 == 0 and the block the planes were cut by (dy_absmax)");
@@ -2455,11 +2487,49 @@ int DSPN_FN(dspn_conv2d_dgrad_bn)(const st_t *dy, const st_t *wt, const void *wt
     const int rc = conv2d_dgrad_one(math, OpScales{dy_absmax, w_absmax, dy_planes}, dy + (long long)n0 * Ho * Wo * ldy, wt, wt_planes, dx + (long long)n0 * H * W * ldc, n, H,
                                     W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
                                     BnBwd{bn_x, bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_dy_absmax}, workspace,
-                                    workspace_bytes, stream);
+                                    workspace_bytes, stream, sa);
     if (rc) return rc;
   }
   return 0;
 }
+extern "C" {
+int DSPN_FN(dspn_conv2d_dgrad_bn)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
+                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
+                             int Wo, int dx_ldc, int accumulate,
+                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
+                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
+                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
+                             void *stream) {
+  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate, bn_x,
+                              bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_sums_bytes, bn_dy_absmax, math, dy_absmax,
+                              w_absmax, workspace, workspace_bytes, stream, StridedAddend{nullptr, 0, 0, 0});
+}
+// ... with the strided addend (include/dspn_nn.h): dx = conv + (h, w both even ? addend[n, h / 2, w / 2, :] : +0.0f)
+int DSPN_FN(dspn_conv2d_dgrad_bn_sadd)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
+                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
+                             int Wo, int dx_ldc, int accumulate,
+                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
+                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
+                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
+                             const st_t *strided_addend, int addend_h, int addend_w, void *stream) {
+  DSPN_REQUIRE(strided_addend && addend_h > 0 && addend_w > 0, "%s: no strided addend (dspn_conv2d_dgrad_bn is the call without one)",
+               DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd));
+  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate, bn_x,
+                              bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_sums_bytes, bn_dy_absmax, math, dy_absmax,
+                              w_absmax, workspace, workspace_bytes, stream, StridedAddend{strided_addend, addend_h, addend_w, 0});
+}
+#ifndef DSPN_HALF
+int dspn_conv2d_dgrad_bn_sadd_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes) {
+  // the verdict of dispatch_nt for the 1 x 1 / stride-1 call of that shape in the two-piece math, without a launch: the
+  // pointers only stand for "given" (16-byte aligned, never dereferenced on the host)
+  float *const q = reinterpret_cast<float *>(uintptr_t(256));
+  const int tiles = dgrad_bn_tiles(N, H, W, Cin, 1);
+  if (tiles <= 0 || N <= 0 || ldy <= 0) return 0;
+  return conv2d_dgrad_bn_impl(q, nullptr, q, q, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 0, q, q, q, q, q, 1, q,
+                              sizeof(float) * 2 * (size_t)tiles * Cin, q, DSPN_MATH_F32_F16X2 | (dy_planes ? DSPN_MATH_DY_PLANES : 0), q, q,
+                              nullptr, 0, nullptr, StridedAddend{q, (H + 1) / 2, (W + 1) / 2, 1}) == 0 ? 1 : 0;
+}
+#endif
 
 #ifndef DSPN_HALF
 int dspn_conv2d_dgrad_f32(const float *dy, const float *wt, float *dx, int N, int H, int W,

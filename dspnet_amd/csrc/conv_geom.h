@@ -54,6 +54,15 @@ struct ConvGeomT {
   // host side only: the weight operand as three bf16 piece planes [Cout][WTAPS][Cin / 32][3][32] (split mode, Cin % 32 == 0:
   // dspn_conv2d_weight_planes_f32); the kernel then receives this pointer in place of the float weights
   const void *w_planes;
+  // optional, with bn_sums (a dense stride-1 data gradient that is the ONLY writer of its output): a compact tensor
+  // (N, sadd_h, sadd_w, Cout) with sadd_h = ceil(Hg / 2), sadd_w = ceil(Wg / 2) -- the data gradient of a 1 x 1 / stride-2
+  // convolution of the same input -- added at the even positions: out[n,h,w,:] = conv + (h, w both even ? sadd[n,h/2,w/2,:] : +0.0f),
+  // where the accumulate addend would be added.  Only the plane-fed 128-row members on the tile-spanning loop take it
+  // (dispatch_nt refuses every other route).
+  const st_t *sadd;
+  int sadd_h, sadd_w;
+  unsigned sadd_bytes;             // its size (buffer bound)
+  int probe;                       // host side only: dispatch_nt returns its verdict without launching (dspn_conv2d_dgrad_bn_sadd_route_f32)
 };
 
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

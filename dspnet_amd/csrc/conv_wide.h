@@ -278,7 +278,11 @@ __device__ __forceinline__ void wide_epilogue(const ConvGeom &g, char *wsm, cons
 // fixed order -- another summation order than the staged epilogue's, i.e. tables equal within rounding, deterministic.
 // SR: rows of a statistics tile (128, or 64 on the <= 64-column layers: one wave row each); CLOSE: end with a barrier (the exchange
 // lies in a ring slot the next tile's first requests are aimed at)
-template <int WAVES_M, int WAVES_N, int EPI, int RB = 16, int SR = 128, bool CLOSE = false>       // RB: rows of a 32 x 32 block whose operand rows are in flight together
+// SADD (EPI 2 only): the strided addend g.sadd -- a compact (N, ceil(Hg / 2), ceil(Wg / 2), Cout) tensor added at the positions
+// with even h and w, +0.0f elsewhere -- takes the place of the accumulate addend: same place in the order of additions, so the
+// stored bits are those of "first writer scatters the compact tensor over zeros, this call accumulates".  A template flag, not a
+// kernel-uniform branch: the launches without the operand keep their instruction stream and register count as they were.
+template <int WAVES_M, int WAVES_N, int EPI, int RB = 16, int SR = 128, bool CLOSE = false, bool SADD = false>       // RB: rows of a 32 x 32 block whose operand rows are in flight together
 __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f32x16 (&acc)[2][2], const float inv_a, const float inv_b, const int m0,
                                                 const int n0, const int M, const int tid, const int wave,
                                                 const float *__restrict__ bias, float *__restrict__ out,
@@ -332,8 +336,41 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
     // (one row at a time: the packed form below needs register pairs for the BatchNorm-input rows as well, which 256 registers
     // do not hold beside the accumulators and the next tile's rows)
     float rq[2][RB][TN], xq[2][RB][TN], oq[2][RB][TN];
+    // SADD: a batch is ONE group of four consecutive rows (RB = 4) that starts at a multiple of four, and the host routes
+    // Wg % 4 == 0, Wg >= 8 only: the group lies inside one image row and starts at an even column, so which of its rows have an
+    // addend is known here -- the first and the third, when the image row is even; the second and the fourth add the constant
+    // +0.0f and request nothing.  (image, row, column) of the group: decoded once per tile (row0), then stepped by the eight
+    // rows between consecutive groups of a lane (the batches are requested in ascending order, each once) -- at most one
+    // image row per step.  A tile may span image rows and images.
+    int sa_n = 0, sa_h = 0, sa_w = 0;
+    __amdgpu_buffer_rsrc_t rs_s = rs_a;
+    if constexpr (SADD) {
+      static_assert(!SADD || RB == 4, "one group of four rows per batch");
+      rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.sadd), 0, g.sadd_bytes, 0x00020000);
+      const int hw = g.Hg * g.Wg;
+      sa_n = row0 / hw;
+      const int rem = row0 - sa_n * hw;
+      sa_h = rem / g.Wg; sa_w = rem - sa_h * g.Wg;
+    }
     auto request = [&](const int bb, const int s_) __attribute__((always_inline)) {
       const int i = bb / (16 / RB), r0 = (bb % (16 / RB)) * RB;
+      // the compact row of the group's first row, or -- odd image row -- an out-of-range offset: the hardware returns the
+      // +0.0f the accumulate path adds there and moves no bytes
+      unsigned sa_off[TN];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) sa_off[j] = kOOB;
+      if constexpr (SADD) {
+        const unsigned sa_rb = (unsigned)((sa_n * g.sadd_h + (sa_h >> 1)) * g.sadd_w + (sa_w >> 1)) * pitch;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) sa_off[j] = ((sa_h & 1) || !cv[j]) ? kOOB : sa_rb + cbyte[j];
+        sa_w += 8;
+        const bool wrap = sa_w >= g.Wg;
+        sa_w -= wrap ? g.Wg : 0;
+        sa_h += wrap ? 1 : 0;
+        const bool wrap2 = sa_h >= g.Hg;
+        sa_h = wrap2 ? 0 : sa_h;
+        sa_n += wrap2 ? 1 : 0;
+      }
 #pragma unroll
       for (int rr = 0; rr < RB; ++rr) {
         const int r = r0 + rr;
@@ -341,6 +378,9 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           const unsigned off = rb + cbyte[j];
+          if constexpr (SADD)      // (an out-of-range offset stays out of range: a row pitch is far below 2^31)
+            rq[s_][rr][j] = (rr & 1) ? 0.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_s, (int)(sa_off[j] + (unsigned)(rr >> 1) * pitch), 0, 0));
+          else
           rq[s_][rr][j] = addsrc ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_a, (int)off, 0, 0)) : 0.f;
           xq[s_][rr][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_x, (int)off, 0, 0));
           oq[s_][rr][j] = both ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_o, (int)off, 0, 0)) : 0.f;
@@ -526,7 +566,8 @@ __device__ __forceinline__ void wide_publish_absmax(const ConvGeom &g, char *wsm
 // the last k-step" (out of range, zeros) are here the LIVE requests of the next tile's first k-steps -- and the epilogue works
 // from the accumulators (direct_epilogue), so the next tile's images are on their way while the current tile is written out.
 // Same K order, same epilogue arithmetic per element: the bits of the plain loop.
-template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR = 128, bool XT = false>
+// SADD: the strided addend of direct_epilogue (XT, EPI 2)
+template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR = 128, bool XT = false, bool SADD = false>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
     const st_t *__restrict__ in, const st_t *__restrict__ wgt, const float *__restrict__ bias,
     st_t *__restrict__ out, const ConvGeom g, const int m_tiles, const int n_tiles,
@@ -545,6 +586,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
   static_assert(STAGES >= 2 && STAGES <= 4, "ring depth");
   static_assert(BM % SR == 0, "BatchNorm tables are per SR rows");
   static_assert(!XT || !kHalf, "the tile-spanning loop: float build");
+  static_assert(!SADD || (XT && EPI == 2 && SR == 128), "the strided addend: tile-spanning loop, BatchNorm-backward sums, 128-row tables");
   extern __shared__ __attribute__((aligned(1024))) char wsm[];
 
 #ifdef DSPN_ABLATE
@@ -768,7 +810,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
         exch = wsm + last_slot * STG;
         if constexpr (EPI != 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }   // every wave has read its last fragments
       }
-      if constexpr (!kHalf) direct_epilogue<WAVES_M, WAVES_N, EPI, (EPI == 2 ? 4 : 8), SR>(g, exch, acc, inv_a, inv_b, m0, n0, M, tid, wave, bias, out, residual, gmx_all);
+      if constexpr (!kHalf) direct_epilogue<WAVES_M, WAVES_N, EPI, (EPI == 2 ? 4 : 8), SR, false, SADD>(g, exch, acc, inv_a, inv_b, m0, n0, M, tid, wave, bias, out, residual, gmx_all);
       DSPN_STAMP(5);
     }
     DSPN_STAMP_FLUSH;
@@ -1258,7 +1300,7 @@ int launch_ntv(WideLoop loop, const float *in, const float *w, const float *bias
 #endif   // !DSPN_HALF
 
 // host side: one launch of the wide family.  Persistent grid as conv_nt_kernel's (dspn::persistent_grid).
-template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR, bool XT>
+template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR, bool XT, bool SADD = false>
 int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s,
                     const st_t *residual) {
   constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64;
@@ -1268,9 +1310,10 @@ int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out,
   // eight waves keep it in the ring slot of the tile's last k-step)
   const size_t lds = XT ? (size_t)STAGES * (BM + BN) * 128 + ((WAVES_M * WAVES_N == 8 || BM == 256) ? 0 : sizeof(float) * 4 * BN * 6)
                         : std::max<size_t>((size_t)STAGES * (BM + BN) * 128, sizeof(float) * BM * (BN + 4));
-  constexpr auto kern = conv_ntw_kernel<WAVES_M, WAVES_N, STAGES, EPI, SR, XT>;
+  constexpr auto kern = conv_ntw_kernel<WAVES_M, WAVES_N, STAGES, EPI, SR, XT, SADD>;
   const int grid_x = dspn::persistent_grid<kern>(WAVES_M * WAVES_N * 64, lds, (long long)mt * nt, "conv_ntw",
-                                                 "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d>", WAVES_M, WAVES_N, STAGES, EPI, (int)XT);
+                                                 SADD ? "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d,sadd>" : "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d>",
+                                                 WAVES_M, WAVES_N, STAGES, EPI, (int)XT);
   if (grid_x < 0) return grid_x;
   {
     dspn::ProfScope prof(0, s);
@@ -1281,6 +1324,10 @@ int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out,
 // one member on the round-5 loop or (SPANS: the member has it; wide_route chose it) the tile-spanning one: the epilogue
 template <int WAVES_M, int WAVES_N, int STAGES, int SR, bool XT>
 int launch_ntw_on(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s, const st_t *residual) {
+  if constexpr (XT && SR == 128 && WAVES_M == 2 && !kHalf) {      // (the members dispatch_nt lets the strided addend through to)
+    if (g.bn_sums && g.sadd) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT, true>(in, w, bias, out, g, s, residual);
+  }
+  if (g.sadd) return dspn::fail(DSPN_ERR_ARG_, "conv: this kernel does not take a strided addend");
   if (g.bn_sums) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT>(in, w, bias, out, g, s, residual);
   if (g.stats) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 1, SR, XT>(in, w, bias, out, g, s, residual);
   return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 0, SR, XT>(in, w, bias, out, g, s, residual);

@@ -125,6 +125,7 @@ class Tensor:
         self.am_slot = None
         self.alias_of = None
         self.grad_planes = False   # this backward pass: .grad holds fp16 piece planes, not floats (BatchNorm.dx_planes)
+        self.sc_compact = None     # this backward pass: the projection shortcut's share of .grad, compact (Conv._compact_shortcut)
         self.channels = None       # logical channel count when the last axis is padded (19 -> 20, 3 -> 4)
         self.data = None if virtual else (data if data is not None else fn.zeros(*self.shape, device=device, dtype=self.dtype))
         self.grad = None
@@ -254,6 +255,9 @@ class Graph:
         self.side_fwd_events, self.side_fwd_waits = {}, {}   # graph_plan.side_sync
         self.side_plan = None      # what the builder asked for (any device) and what graph_plan.side_sync made of it
         self.slab_tables = {}      # key -> (conv nodes, device table) of deferred split-K slab reductions
+        # the compact data gradient of a projection shortcut between its two calls (graph_plan.shortcut_compaction): ONE flat
+        # buffer sized for the largest pair -- a pair's two calls are neighbours on the step's stream, so only one is live
+        self.sc_compact_buf = None
         self.wt_table = None       # descriptor table of every Conv's (weight, transposed weight) pair
         self.wt_batched = False    # True while backward() runs after one batched transpose launch
         self.arena = self.grad_arena = self.mom_arena = None
@@ -787,6 +791,7 @@ class Graph:
             t._gw = False
             t.grad = None
             t.grad_planes = False
+            t.sc_compact = None
         if self.side_bwd is not None:
             assert not self.side_bwd["dirty"], "the previous backward pass left side-stream work unjoined"
             self.side_bwd["forked"] = False
@@ -1196,6 +1201,12 @@ FINALIZE_BESIDE = os.environ.get("DSPN_FINALIZE_BESIDE", "1") != "0"
 # (the ReLU-backward / bias-gradient pass) as by-products; DSPN_CONV_MAGNITUDES=0 keeps the stand-alone passes (same-box A/B)
 FUSE_CONV_MAGNITUDES = os.environ.get("DSPN_CONV_MAGNITUDES", "1") != "0"
 
+# the projection units (conv1 and the 1 x 1 / stride-2 shortcut read one BatchNorm output): the shortcut's data gradient stays a
+# compact (N, H/2, W/2, C) tensor and conv1's data gradient, the only writer of the full-resolution gradient, adds it at the
+# even positions (graph_plan.shortcut_compaction); DSPN_SC_COMPACT=0: the shortcut writes the full tensor -- three quarters of
+# it zeros -- and conv1 accumulates (same-box A/B; same bits either way)
+SC_COMPACT = os.environ.get("DSPN_SC_COMPACT", "1") != "0"
+
 
 def xa_unavailable(conv):
     """the output-magnitude epilogue needs a dense output of whole float4 rows (every Conv output of the engine is one)"""
@@ -1274,6 +1285,7 @@ class Conv(Node):
         self.bn_bwd_node = None      # the BatchNorm whose backward sums this node's data gradient gathers (graph_plan.bn_backward_fusion)
         self._wg_worth = None        # _wgrad_worth_a_stream, once estimated
         self.guard_fb = False        # range guard (Graph._update_guard): this pass's calls run in the three-piece bf16 math
+        self.sc_pair = None          # the other convolution of a (conv1, projection shortcut) pair (graph_plan.shortcut_compaction)
         self.wp = self.wtp = None
         if g.device.type == "cuda":
             npc = fn.plane_pieces(g.math)
@@ -1524,7 +1536,11 @@ class Conv(Node):
                              w_absmax=wa)
         elif self.wtp is None and not (g.wt_frozen is not None if self.w.fixed else g.wt_batched):
             fn.weight_transpose(self.w.data, out=self.wt, copy=self.wh)
+        if self.sc_pair is not None and self.stride == 2 and self._compact_shortcut(dy, planes, dya, wa):
+            return
         dx, acc = self.x.grad_target()
+        sa = self.x.sc_compact   # left by the pair's shortcut in this pass: this call is then the first and only writer of dx
+        assert sa is None or (not acc and not self.guard_fb and self.bn_bwd_node is not None)
         bn = self.bn_bwd_node   # set by Graph.finalize on the LAST writer of a deferred BN's gradient
         bn_bwd, bn_dya = None, None
         if bn is not None:
@@ -1543,7 +1559,28 @@ class Conv(Node):
             return
         fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, out=dx, accumulate=acc,
                         bn_bwd=bn_bwd, wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa,
-                        bn_dy_absmax=bn_dya, dy_planes=planes, wt_shape=self.wt_shape)
+                        bn_dy_absmax=bn_dya, dy_planes=planes, wt_shape=self.wt_shape, strided_addend=sa)
+
+    def _compact_shortcut(self, dy, planes, dya, wa):
+        """The data gradient of a projection shortcut (1 x 1, stride 2, pad 0) as the stride-1 1 x 1 data gradient on the
+        subsampled grid, into the graph's compact buffer, left on the input tensor for the pair's conv1 (which runs next among
+        the writers of that gradient and adds it in its epilogue).  Decided per pass: False -- the full-resolution call as
+        first writer, conv1 accumulates -- when the knob is off, either node is on the range guard's fallback, conv1 has no
+        gradient to propagate, or no kernel takes the addend for conv1's call (its dy not piece planes, launch settings).
+        A frozen shortcut weight changes nothing here: the operand planes are prepared the same way for either call.
+        The weight gradient of this node beside the chain (_wg_before_write / WgradSide.reads) is unaffected: it reads dy,
+        never the compact buffer, which is written and read on the step's stream only."""
+        conv1, x, g = self.sc_pair, self.x, self._g
+        if (not SC_COMPACT or self.guard_fb or conv1.guard_fb or planes or x._gw or not conv1.out._gw or g.sc_compact_buf is None
+                or not fn.conv2d_dgrad_addend_route(x.shape, conv1.out.shape[3], conv1.out.grad_planes)):
+            return False
+        N, H, W, C = x.shape
+        Ho, Wo = dy.shape[1], dy.shape[2]
+        dxc = g.sc_compact_buf[:N * Ho * Wo * C].view(N, Ho, Wo, C)
+        fn.conv2d_dgrad(dy, self.wt, dxc.shape, 1, 0, 1, out=dxc, wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa,
+                        wt_shape=self.wt_shape)
+        x.sc_compact = dxc
+        return True
 
 
 class BilinearConcatConv(Node):

@@ -47,6 +47,9 @@ _lib.register({
     "dspn_conv2d_dgrad_bn_tiles": (_i, [_i, _i, _i, _i, _i]),
     "dspn_conv2d_dgrad_bn_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                                       _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dspn_conv2d_dgrad_bn_sadd_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                           _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp, _i, _i, _vp]),
+    "dspn_conv2d_dgrad_bn_sadd_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
     "dspn_bn_backward_from_sums_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _i, _i, _i,
                                             _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "dspn_bn_discard_parked": (_i, [_vp]),
@@ -120,7 +123,7 @@ _lib.register({
 
 
 # the bfloat16-tensor twins (include/dspn_nn.h): same argument lists as the *_f32 entries
-for _name in ("dspn_conv2d_forward_bn", "dspn_conv2d_dgrad_bn", "dspn_conv2d_wgrad_bn", "dspn_conv2d_wgrad_slabs",
+for _name in ("dspn_conv2d_forward_bn", "dspn_conv2d_dgrad_bn", "dspn_conv2d_dgrad_bn_sadd", "dspn_conv2d_wgrad_bn", "dspn_conv2d_wgrad_slabs",
               "dspn_conv2d_input_sum_grad", "dspn_bn_stats", "dspn_bn_apply", "dspn_bn_backward",
               "dspn_bn_backward_from_sums", "dspn_add", "dspn_relu_backward", "dspn_relu_backward_colsum", "dspn_colsum",
               "dspn_nchw_to_nhwc", "dspn_copy_block", "dspn_tap_sum", "dspn_tap_spread", "dspn_maxpool_forward", "dspn_maxpool_forward_bn",
@@ -563,9 +566,20 @@ MATH_X_PLANES = 0x400        # include/dspn_nn.h DSPN_MATH_X_PLANES
 BN_SUMS_PLANES, BN_SUMS_FINALIZE_ONLY, BN_SUMS_APPLY_ONLY, BN_SUMS_PARKED = 1, 2, 4, 8
 
 
+def conv2d_dgrad_addend_route(x_shape, ldy, dy_planes):
+    """True when the 1 x 1 / stride-1 data gradient dy (N,H,W,ldy) -> dx x_shape, "f16x2" math with BatchNorm sums, takes a
+    strided addend under the current launch settings (a host-side query: no launch)"""
+    N, H, W, C = x_shape
+    return bool(L().dspn_conv2d_dgrad_bn_sadd_route_f32(N, H, W, C, ldy, int(bool(dy_planes))))
+
+
 def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=False, bn_bwd=None, wt_planes=None,
-                 math=None, dy_absmax=None, w_absmax=None, bn_dy_absmax=None, dy_planes=False, wt_shape=None):
+                 math=None, dy_absmax=None, w_absmax=None, bn_dy_absmax=None, dy_planes=False, wt_shape=None,
+                 strided_addend=None):
     """dy (N,Ho,Wo,ldy), wt (Cin,R,S,ldy) -> dx (N,H,W,ldc>=Cin).
+    strided_addend: a compact (N, ceil(H/2), ceil(W/2), Cin) tensor -- the data gradient of a 1 x 1 / stride-2 convolution of
+    the same input -- added at the positions with even h and w (+0.0 elsewhere) where `accumulate` would add dx's old value;
+    this call is then the only writer of dx (include/dspn_nn.h dspn_conv2d_dgrad_bn_sadd_f32: refused where no kernel takes it).
     bn_bwd = (bn_x, scale, shift, mean, rstd, relu, sums): dx is the complete gradient of a BatchNorm(+ReLU) output
     whose input was bn_x; the two reductions of its backward pass are written to sums (tiles, 2, Cin).
     wt_planes: the piece planes of wt (weight_planes(w, transposed=True, cols=ldy)), used in the split math when
@@ -595,11 +609,17 @@ def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=F
     ws = workspace(L().dspn_conv2d_split_workspace_bytes(N * H * W, Cin), dy.device, "split")
     ph, pw = _hw(pad)
     bx, bsc, bsh, bmu, brs, brelu, bsums = bn_bwd if bn_bwd is not None else (None, None, None, None, None, False, None)
-    check(_f("dspn_conv2d_dgrad_bn", dy)(ptr(dy), ptr(wt), ptr(wt_planes), ptr(out), N, H, W, Cin, ldy, R, S, stride, ph, pw,
-                                       dil, Ho, Wo, out.shape[3], int(accumulate), ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu),
-                                       ptr(brs), int(brelu), ptr(bsums), 0 if bsums is None else bsums.numel() * 4,
-                                       ptr(bn_dy_absmax), math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax),
-                                       ptr(w_absmax), ptr(ws), ws.numel(), stream()), "conv2d_dgrad")
+    args = (ptr(dy), ptr(wt), ptr(wt_planes), ptr(out), N, H, W, Cin, ldy, R, S, stride, ph, pw,
+            dil, Ho, Wo, out.shape[3], int(accumulate), ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu),
+            ptr(brs), int(brelu), ptr(bsums), 0 if bsums is None else bsums.numel() * 4,
+            ptr(bn_dy_absmax), math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax),
+            ptr(w_absmax), ptr(ws), ws.numel())
+    if strided_addend is not None:
+        sa = strided_addend
+        assert sa.dtype == out.dtype and sa.is_contiguous() and sa.shape == (N, (H + 1) // 2, (W + 1) // 2, Cin), (sa.shape, x_shape)
+        check(_f("dspn_conv2d_dgrad_bn_sadd", dy)(*args, ptr(sa), sa.shape[1], sa.shape[2], stream()), "conv2d_dgrad")
+    else:
+        check(_f("dspn_conv2d_dgrad_bn", dy)(*args, stream()), "conv2d_dgrad")
     return out
 
 

@@ -43,6 +43,7 @@ def plan(g):      # (the passes in the order their decisions build on each other
     gradient_magnitudes(g, index)
     if os.environ.get("DSPN_DY_PLANES", "1") != "0":      # (A/B switch)
         gradient_planes(g, index)
+    shortcut_compaction(g, index)
 
 
 def resolve_auto_deferred(g, index):
@@ -133,6 +134,35 @@ def gradient_planes(g, index):
         n.dx_planes = True
         n.x_ext = fn.zeros(2, x.shape[3], device=g.device)
         n.am_dyin = g.new_scalar(backward=True)
+
+
+def shortcut_compaction(g, index):
+    """The projection units of the ResNets: act1 feeds conv1 (1 x 1, stride 1) and the shortcut (1 x 1, stride 2, pad 0), and
+    conv1 -- built first -- is the last writer of act1's gradient and gathers bn1's backward sums.  The shortcut's data
+    gradient is the stride-1 1 x 1 data gradient on the subsampled grid; written at full resolution it is three quarters
+    zeros that conv1's accumulate reads back.  Marked pairs keep it compact (Conv._compact_shortcut) and conv1's data gradient
+    adds it at the even positions (include/dspn_nn.h dspn_conv2d_dgrad_bn_sadd_f32).  A pair: the BatchNorm output's gradient
+    has exactly these two writers, "f16x2" math, float tensors; whether a given pass takes the path is the nodes' decision."""
+    if g.math != "f16x2" or g.device.type != "cuda":
+        return
+    largest = 0
+    for n in g.nodes:
+        if not isinstance(n, E.BatchNorm) or not n.out.requires_grad or n.out.dtype != torch.float32:
+            continue
+        readers = sorted(index.reader_nodes(n.out))
+        if len(readers) != 2 or not all(isinstance(g.nodes[i], E.Conv) and g.nodes[i].x is n.out for i in readers):
+            continue
+        conv1, sc = g.nodes[readers[0]], g.nodes[readers[1]]
+        one_by_one = lambda c: c.w.shape[1:3] == (1, 1) and c.pad == (0, 0) and c.dil == 1 and not c.tap_expand  # noqa: E731
+        if not (one_by_one(conv1) and conv1.stride == 1 and conv1.bn_bwd_node is n and conv1.math == "f16x2"
+                and one_by_one(sc) and sc.stride == 2 and sc.math == "f16x2" and sc.input_sum_grad is None
+                and conv1.input_sum_grad is None and n.out.shape[3] == conv1.w.shape[3]):
+            continue
+        conv1.sc_pair, sc.sc_pair = sc, conv1
+        N, H, W, C = n.out.shape
+        largest = max(largest, N * ((H + 1) // 2) * ((W + 1) // 2) * C)
+    if largest:
+        g.sc_compact_buf = fn.zeros(largest, device=g.device)
 
 
 def input_planes(g):

@@ -192,6 +192,26 @@ int dspn_conv2d_dgrad_bn_f32(const float *dy, const float *wt, const void *wt_pl
 /* bn_dy_absmax (optional, with bn_sums, DSPN_MATH_F32_F16X2; round 4): DSPN_ABSMAX_SLOTS floats (zeroed by the caller) that
  * receive the partial maxima of |dx| as stored -- the `dy_absmax` of the dspn_bn_backward_from_sums_f32 call that finishes
  * this BatchNorm's backward pass with dx_planes. */
+/* The same call with a STRIDED ADDEND: strided_addend is a compact tensor (N, addend_h, addend_w, Cin) with addend_h =
+ * ceil(H / 2), addend_w = ceil(W / 2) -- the data gradient of a 1 x 1 / stride-2 / pad-0 convolution of the same input, which
+ * is the stride-1 1 x 1 data gradient on the subsampled grid -- and
+ *     dx[n,h,w,:] = conv + (h, w both even ? strided_addend[n, h/2, w/2, :] : +0.0f),
+ * the addend applied where `accumulate` applies its own: the stored bits, the sum tables and the bn_dy_absmax block are those
+ * of "the stride-2 data gradient writes dx first, this call accumulates", without the full-resolution tensor of three
+ * quarters zeros being written and read back.  This call is the only writer of dx (accumulate must be 0).  Taken by the
+ * plane-fed 128-row tiles of DSPN_MATH_F32_F16X2 on the tile-spanning loop, with bn_sums (stride 1, dense dx, dy as piece
+ * planes, N H W % 128 == 0, W % 4 == 0, W >= 8); every other call -- another math mode, bfloat16 tensors, split-K, a strided dx -- returns
+ * non-zero with dspn_last_error() naming this entry, and the caller keeps the accumulate path.
+ * dspn_conv2d_dgrad_bn_sadd_route_f32: 1 when the 1 x 1 call of that shape would be taken under the current launch settings
+ * (no launch, no device access), else 0. */
+int dspn_conv2d_dgrad_bn_sadd_f32(const float *dy, const float *wt, const void *wt_planes, float *dx, int N, int H, int W, int Cin, int ldy,
+                                  int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo, int dx_ldc,
+                                  int accumulate, const float *bn_x, const float *bn_scale, const float *bn_shift,
+                                  const float *bn_mean, const float *bn_rstd, int bn_relu, float *bn_sums,
+                                  size_t bn_sums_bytes, float *bn_dy_absmax, int math, const float *dy_absmax, const float *w_absmax,
+                                  void *workspace, size_t workspace_bytes, const float *strided_addend, int addend_h, int addend_w,
+                                  void *stream);
+int dspn_conv2d_dgrad_bn_sadd_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes);
 
 /* out[c] = sum over every input pixel of the data gradient of the convolution, c < Cin <= 8, computed
  * from per-tap sums of dy without forming the gradient (the first convolution's input only feeds the
@@ -287,6 +307,15 @@ int dspn_conv2d_dgrad_bn_bf16(const dspn_bf16 *dy, const dspn_bf16 *wt, const vo
                               float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax_unused, int math,
                               const float *absmax_unused_a, const float *absmax_unused_b, void *workspace,
                               size_t workspace_bytes, void *stream);
+/* (always refused: the strided addend exists for float tensors) */
+int dspn_conv2d_dgrad_bn_sadd_bf16(const dspn_bf16 *dy, const dspn_bf16 *wt, const void *wt_planes_unused, dspn_bf16 *dx, int N, int H, int W,
+                                   int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo,
+                                   int dx_ldc, int accumulate, const dspn_bf16 *bn_x, const float *bn_scale,
+                                   const float *bn_shift, const float *bn_mean, const float *bn_rstd, int bn_relu,
+                                   float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax_unused, int math,
+                                   const float *absmax_unused_a, const float *absmax_unused_b, void *workspace,
+                                   size_t workspace_bytes, const dspn_bf16 *strided_addend, int addend_h, int addend_w,
+                                   void *stream);
 int dspn_conv2d_wgrad_bn_bf16(const dspn_bf16 *x, const float *in_scale, const float *in_shift, int in_relu,
                               const dspn_bf16 *dy, float *dw, int N, int H, int W, int Cin, int Cout, int ldy,
                               int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo,

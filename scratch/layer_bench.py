@@ -58,6 +58,7 @@ for n in net.g.nodes:
         tw = timeit(lambda: fn.conv2d_wgrad(n.x_raw.data, dy, n.w.shape, n.stride, n.pad, n.dil, out=n.w.grad, in_affine=n.in_affine, math=n.math, x_absmax=xa, dy_absmax=dya, dy_planes=dyp))
     td = None
     fused_d = 0
+    sc_mark = ""
     if n.x.requires_grad:
         dx = n.x.own_grad()
         # round 6: the data gradient as the GRAPH calls it -- with the BatchNorm-backward sums of the layer in front in its
@@ -68,7 +69,21 @@ for n in net.g.nodes:
             bn_bwd = (bn.x.data, bn.scale, bn.shift, bn.mean, bn.rstd, bn.relu, bn.bwd_sums[0])
             bn_dya = net.g.scalar(bn.am_dyin) if getattr(bn, "dx_planes", False) else None
             fused_d = 1
-        td = timeit(lambda: fn.conv2d_dgrad(dy, n.wt, n.x.shape, n.stride, n.pad, n.dil, out=dx, wt_planes=n.wtp, math=n.math, dy_absmax=dya, w_absmax=wa, wt_shape=n.wt_shape, dy_planes=dyp, bn_bwd=bn_bwd, bn_dy_absmax=bn_dya))
+        # the projection units (graph_plan.shortcut_compaction), as the graph calls them: the shortcut's data gradient is the
+        # stride-1 call on the subsampled grid into the compact buffer ("c"), conv1's adds that buffer at the even positions ("a")
+        pair = getattr(n, "sc_pair", None)
+        conv1 = None if pair is None else (pair if n.stride == 2 else n)
+        compact = (pair is not None and E.SC_COMPACT and f16
+                   and fn.conv2d_dgrad_addend_route(n.x.shape, conv1.out.shape[3], bool(planes_dy.get(id(conv1.out)))))
+        dxc = None
+        if compact:
+            dxc = net.g.sc_compact_buf[:N_ * ((H + 1) // 2) * ((W + 1) // 2) * Cin].view(N_, (H + 1) // 2, (W + 1) // 2, Cin)
+        if compact and n.stride == 2:
+            td = timeit(lambda: fn.conv2d_dgrad(dy, n.wt, dxc.shape, 1, 0, 1, out=dxc, wt_planes=n.wtp, math=n.math, dy_absmax=dya, w_absmax=wa, wt_shape=n.wt_shape))
+            sc_mark = "c"
+        else:
+            td = timeit(lambda: fn.conv2d_dgrad(dy, n.wt, n.x.shape, n.stride, n.pad, n.dil, out=dx, wt_planes=n.wtp, math=n.math, dy_absmax=dya, w_absmax=wa, wt_shape=n.wt_shape, dy_planes=dyp, bn_bwd=bn_bwd, bn_dy_absmax=bn_dya, strided_addend=dxc))
+            sc_mark = "a" if compact else ""
     tot[0] += tf; tot[2] += tw; totf[0] += fl; totf[2] += fl
     if td: tot[1] += td; totf[1] += fl
     xin = N_ * H * W * Cin * 4 // (n.stride * n.stride if R * S == 1 else 1)          # (a strided 1x1 reads every stride-th pixel)
@@ -77,12 +92,16 @@ for n in net.g.nodes:
     # of the BatchNorm input its epilogue reads for the backward sums
     byt_f = byt + (M * Cout * 4 if n.residual is not None else 0)
     byt_d = byt + (xin if fused_d else 0)
+    if sc_mark == "c":        # dy read, the compact gradient written: a quarter of the full-resolution tensor
+        byt_d = M * Cout * 4 + M * Cin * 4 + Cout * Cin * 4
+    elif sc_mark == "a":      # + the compact rows the epilogue adds
+        byt_d += xin // 4
     key = key + (n.residual is not None, fused_d)
     cnt[key] = cnt.get(key, 0) + 1
-    rows.setdefault(key, (n.w.name[:-7] + ("*" if dyp else "") + ("+" if xp is not None else "") + ("r" if n.residual is not None else "") + ("^" if fused_d else ""),
+    rows.setdefault(key, (n.w.name[:-7] + ("*" if dyp else "") + ("+" if xp is not None else "") + ("r" if n.residual is not None else "") + ("^" if fused_d else "") + sc_mark,
                           M, Cout, R * S * Cin, tf, fl, td, tw, byt, byt_f, byt_d))
 print("(* dy as piece planes in dgrad / wgrad, + x as piece planes in forward / wgrad, r forward adds a residual in its epilogue, ^ data gradient with the")
-print(" BatchNorm-backward sums in its epilogue; TB/s = bytes the call moves / time, of 8: operand + output + weights, + the residual rows (r), + the BatchNorm input rows (^))")
+print(" BatchNorm-backward sums in its epilogue, c the projection shortcut's data gradient as the compact stride-1 call, a conv1's with that compact tensor as strided addend; TB/s = bytes the call moves / time, of 8: operand + output + weights, + the residual rows (r), + the BatchNorm input rows (^))")
 for key, (name, M, Cout, K, tf, fl, td, tw, byt, byt_f, byt_d) in rows.items():
     print("%-32s x%-2d %8d %5d %6d | %7.3f %6.1f %4.2f %4.1f | %7s %6s %4s %4s | %7.3f %6.1f %4.2f %4.1f" % (
         name, cnt[key], M, Cout, K, tf, fl / tf / 1e9, fl / tf / 1e9 / PEAK, byt_f / tf / 1e9,
