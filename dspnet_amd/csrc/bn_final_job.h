@@ -34,6 +34,8 @@ struct BnFinalJob {
 // host side (capi.hip): one parked job per stream
 void bn_job_defer(hipStream_t s, const BnFinalJob &job);
 bool bn_job_take(hipStream_t s, BnFinalJob *job);
+// (nn.hip) the jobs of this stream that no weight gradient took, each as a launch of its own: what every apply half does first
+void bn_jobs_run(hipStream_t s);
 
 // what bn_bwd_final_kernel does with a channel's two sums (shared with that kernel: one arithmetic)
 __device__ __forceinline__ void bn_final_channel(const int c, const int C, const double S, const double SS, const double inv_rows,
@@ -64,6 +66,16 @@ __device__ __forceinline__ void bn_final_channel(const int c, const int C, const
     // magnitudes the planes are cut over (one word, the caller presets it to +inf; min of positive floats = min of their bits)
     if (dx_bound_min && bf > 0.f && bf < INFINITY) atomicMin(dx_bound_min, __float_as_uint(bf));
   }
+}
+
+// The apply half's element, dx = a dy' + c1 x + c0, in the instruction sequence hipcc forms for bn_bwd_apply_kernel's
+// `a * g + c1 * x + c0` under that file's contraction setting (read from its ISA: v_pk_mul a g, v_pk_fma c1 x onto it,
+// v_pk_add c0): the product a dy' rounded, c1 x fused onto it, c0 added.  Written out -- this header is compiled without
+// contraction wherever it is included -- for the kernels that form the same element elsewhere (conv_wide.h, the apply form
+// of the direct epilogue): the bits bn_bwd_apply_kernel stores.
+__device__ __forceinline__ float bn_apply_element(const float a, const float g, const float c1, const float x, const float c0) {
+  const float ag = a * g;
+  return fmaf(c1, x, ag) + c0;
 }
 
 // one job workgroup: channels 16 b .. 16 b + 15 on threads 0 .. 255 (lane pair (channel, virtual slab lane 0 .. 15)); every

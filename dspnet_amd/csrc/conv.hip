@@ -1999,6 +1999,31 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
     g.sadd_bytes = (unsigned)((long long)sizeof(st_t) * g.N * g.sadd_h * g.sadd_w * g.Cout);      // (a quarter of dx, which the route bounds below 2 GiB)
     if (g.probe) return 0;
   }
+  if (g.bn_recompute) {
+    // The data gradient whose output is never stored (ConvGeom::bn_recompute: the sums pass, the apply pass) exists where the
+    // strided addend does -- the direct epilogue of the plane-fed 128-row members on the tile-spanning loop -- and nowhere
+    // else: refused HERE, by name; the caller keeps the data gradient + BatchNorm backward pair.
+    const char *who = g.bn_recompute == 1 ? DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums) : DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply);
+    if (kHalf) return dspn::fail(DSPN_ERR_ARG_, "%s: float tensors only", who);
+    if (g.bf16 != 3) return dspn::fail(DSPN_ERR_ARG_, "%s: needs DSPN_MATH_F32_F16X2", who);
+    // (the sums pass carries tables and the apply pass no split workspace: neither is ever split -- a shape that a plain data
+    // gradient splits over K is named as such)
+    if (splits > 1 || (g.dense && nblk < 192 && nk >= 16))
+      return dspn::fail(DSPN_ERR_ARG_, "%s: cannot be combined with split-K (%lld workgroups, %d k-steps: a shape that is split)", who, nblk, nk);
+    if (!g.a_planes) return dspn::fail(DSPN_ERR_ARG_, "%s: needs dy as piece planes (DSPN_MATH_DY_PLANES)", who);
+    if (g.sadd || g.stats || g.in_scale || residual || (g.flags & (1 | 2 | 8)))
+      return dspn::fail(DSPN_ERR_ARG_, "%s: a plain data gradient only (no strided addend, statistics, input affine, bias, ReLU or residual)", who);
+    if (!g.dense || g.ldc != g.Cout) return dspn::fail(DSPN_ERR_ARG_, "%s: needs a dense dx (dx_ldc %d, Cin %d)", who, g.ldc, g.Cout);
+    if (g.TR * g.TS != 1 || g.ish != 1 || g.isw != 1 || g.ioh != 0 || g.iow != 0)
+      return dspn::fail(DSPN_ERR_ARG_, "%s: a 1 x 1 / stride-1 / pad-0 convolution only", who);
+    if ((g.bn_recompute == 1) != (g.bn_sums != nullptr) || (g.bn_recompute == 1 && (g.flags & 4)))
+      return dspn::fail(DSPN_ERR_ARG_, "%s: the sums pass writes the tables and adds to nothing; the apply pass reads the coefficients", who);
+    if (!((route.tile == dspn::conv::WideTile::P128x128 || route.tile == dspn::conv::WideTile::P128x256) &&
+          route.loop == dspn::conv::WideLoop::Spanning))
+      return dspn::fail(DSPN_ERR_ARG_, "%s: no kernel on this route (it needs N H W %% 128 == 0 and the plane-fed 128-row tiles on the "
+                        "tile-spanning loop)", who);
+    if (g.probe) return 0;
+  }
   if (route) return dspn::conv::launch_wide(route, in, w, bias, out, g, s, residual);
   const int rc = cfg == 0 && eight ? launch_nt<4, 2, 1, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
                  : cfg == 0        ? launch_nt<2, 2, 2, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
@@ -2373,6 +2398,9 @@ int dspn_conv2d_weight_prepare_batch_bf16(const void *table, int n, long long to
 struct BnBwd { const st_t *x; const float *scale, *shift, *mean, *rstd; int relu; float *sums; float *dy_absmax; };
 // the strided addend of a dense data gradient (ConvGeom::sadd); probe: ask dispatch_nt for its verdict only
 struct StridedAddend { const st_t *p; int h, w, probe; };
+// the passes of a data gradient that is never stored (ConvGeom::bn_recompute): mode 1 sums, 2 apply (coef: the finalize's
+// 3 Cin floats; dx_absmax: the optional magnitude block of the dx it stores); probe as above
+struct BnRecompute { int mode; const float *coef; float *dx_absmax; int probe; };
 
 // row tiles of the launches of one data gradient, in launch order (stride 2: up to 4 parity classes)
 static int dgrad_tiles(int N, int H, int W, int Cin, int stride, int *per_class /* [4] or NULL */) {
@@ -2391,8 +2419,8 @@ static int dgrad_tiles(int N, int H, int W, int Cin, int stride, int *per_class 
 static int conv2d_dgrad_one(int math, OpScales scales, const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
                           int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                           int Wo, int dx_ldc, int accumulate, BnBwd bn, void *workspace, size_t workspace_bytes,
-                          void *stream, StridedAddend sa = StridedAddend{nullptr, 0, 0, 0}) {
-  DSPN_REQUIRE(dy && (wt || wt_planes) && dx, "conv2d_dgrad: null pointer");
+                          void *stream, StridedAddend sa = StridedAddend{nullptr, 0, 0, 0}, BnRecompute rc2 = BnRecompute{0, nullptr, nullptr, 0}) {
+  DSPN_REQUIRE(dy && (wt || wt_planes) && (dx || rc2.mode == 1), "conv2d_dgrad: null pointer");
   DSPN_REQUIRE(ldy % kEPC == 0, "conv2d_dgrad: dy channel stride must be a multiple of %d", kEPC);
   DSPN_REQUIRE(stride == 1 || (stride == 2 && dil == 1), "conv2d_dgrad: stride 1, or stride 2 with dilation 1");
   DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && R > 0 && S > 0, "conv2d_dgrad: bad geometry");
@@ -2411,7 +2439,10 @@ static int conv2d_dgrad_one(int math, OpScales scales, const st_t *dy, const st_
   g.bn_relu = bn.relu; g.bn_sums = bn.sums; g.bn_tile_base = 0;
   g.bn_dy_absmax = (bn.sums && !kHalf && math == DSPN_MATH_F32_F16X2) ? reinterpret_cast<unsigned *>(bn.dy_absmax) : nullptr;
   g.a_planes = scales.a_planes;
-  g.sadd = sa.p; g.sadd_h = sa.h; g.sadd_w = sa.w; g.probe = sa.probe;
+  g.sadd = sa.p; g.sadd_h = sa.h; g.sadd_w = sa.w; g.probe = sa.probe | rc2.probe;
+  g.bn_recompute = rc2.mode; g.bn_coef = rc2.coef;
+  if (rc2.mode == 2) g.bn_dy_absmax = reinterpret_cast<unsigned *>(rc2.dx_absmax);
+  if (rc2.mode == 1) g.bn_dy_absmax = nullptr;
   int class_tiles[4] = {0, 0, 0, 0};
   if (bn.sums) dgrad_tiles(N, H, W, Cin, stride, class_tiles);
   hipStream_t s = (hipStream_t)stream;
@@ -2460,8 +2491,17 @@ static int conv2d_dgrad_bn_impl(const st_t *dy, const st_t *wt, const void *wt_p
                              const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
                              const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
                              int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
-                             void *stream, StridedAddend sa) {
+                             void *stream, StridedAddend sa, BnRecompute rc2 = BnRecompute{0, nullptr, nullptr, 0}) {
   DSPN_REQUIRE(N > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_dgrad: bad geometry");
+  if (rc2.mode) {      // (what the arguments alone decide; the route is dispatch_nt's)
+    const char *who = rc2.mode == 1 ? DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums) : DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply);
+    DSPN_REQUIRE(!dspn::kHalf, "%s: float tensors only (the bfloat16 build has no such kernel)", who);
+    DSPN_REQUIRE(R == 1 && S == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && Ho == H && Wo == W,
+                 "%s: a 1 x 1 / stride-1 / pad-0 convolution only", who);
+    DSPN_REQUIRE((dx_ldc <= 0 || dx_ldc == Cin), "%s: needs a dense dx (dx_ldc %d, Cin %d)", who, dx_ldc, Cin);
+    DSPN_REQUIRE(Cin > 0 && Cin % 4 == 0, "%s: Cin %% 4 == 0", who);
+    DSPN_REQUIRE(batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy) == N, "%s: dy of 2 GiB or more", who);
+  }
   if (sa.p) {      // (what the arguments alone decide; the route is dispatch_nt's)
     constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd);
     DSPN_REQUIRE(stride == 1 && !accumulate, "%s: the strided addend goes with a stride-1 data gradient that is the only writer of dx (no accumulate)", who);
@@ -2487,12 +2527,50 @@ static int conv2d_dgrad_bn_impl(const st_t *dy, const st_t *wt, const void *wt_p
     const int rc = conv2d_dgrad_one(math, OpScales{dy_absmax, w_absmax, dy_planes}, dy + (long long)n0 * Ho * Wo * ldy, wt, wt_planes, dx + (long long)n0 * H * W * ldc, n, H,
                                     W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
                                     BnBwd{bn_x, bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_dy_absmax}, workspace,
-                                    workspace_bytes, stream, sa);
+                                    workspace_bytes, stream, sa, rc2);
     if (rc) return rc;
   }
   return 0;
 }
 extern "C" {
+// The data gradient of a BatchNorm(+ReLU) output that is never stored (include/dspn_nn.h): the sums pass ...
+int DSPN_FN(dspn_conv2d_dgrad_bn_sums)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
+                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
+                             int Wo, int dx_ldc, int accumulate,
+                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
+                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
+                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
+                             void *stream) {
+  constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums);
+  DSPN_REQUIRE(!dx && !accumulate && !bn_dy_absmax, "%s: stores no dx (dx == NULL, accumulate 0, no bn_dy_absmax); dspn_conv2d_dgrad_bn is the call that does", who);
+  DSPN_REQUIRE(bn_sums, "%s: bn_sums missing", who);
+  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, nullptr, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, 0, bn_x,
+                              bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_sums_bytes, nullptr, math, dy_absmax,
+                              w_absmax, workspace, workspace_bytes, stream, StridedAddend{nullptr, 0, 0, 0}, BnRecompute{1, nullptr, nullptr, 0});
+}
+// ... and the apply pass, in the place of the DSPN_BN_SUMS_APPLY_ONLY call of dspn_bn_backward_from_sums
+int DSPN_FN(dspn_conv2d_dgrad_bn_apply)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
+                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
+                             int Wo, int dx_ldc, int accumulate,
+                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, int bn_relu, float *dx_absmax,
+                             int math, const float *dy_absmax, const float *w_absmax, const void *bn_workspace,
+                             size_t bn_workspace_bytes, void *stream) {
+  constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply);
+  DSPN_REQUIRE(dx && bn_x && bn_workspace && (!bn_relu || (bn_scale && bn_shift)), "%s: null pointer", who);
+  if (Cin > 0 && bn_workspace_bytes < sizeof(float) * 3 * (size_t)Cin)
+    return dspn::fail(DSPN_ERR_WORKSPACE_, "%s: the BatchNorm workspace holds 3 * Cin coefficients", who);
+  // (the probe of the route query launches nothing: it leaves a parked finalize where it is)
+  const int rc = conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
+                                      bn_x, bn_scale, bn_shift, nullptr, nullptr, bn_relu, nullptr, 0, nullptr, math, dy_absmax, w_absmax,
+                                      nullptr, 0, stream, StridedAddend{nullptr, 0, 0, 0},
+                                      BnRecompute{2, static_cast<const float *>(bn_workspace), dx_absmax, 1});
+  if (rc) return rc;
+  dspn::bn_jobs_run((hipStream_t)stream);      // a finalize of this stream that no weight gradient took: now, as the apply half does
+  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
+                              bn_x, bn_scale, bn_shift, nullptr, nullptr, bn_relu, nullptr, 0, nullptr, math, dy_absmax, w_absmax,
+                              nullptr, 0, stream, StridedAddend{nullptr, 0, 0, 0},
+                              BnRecompute{2, static_cast<const float *>(bn_workspace), dx_absmax, 0});
+}
 int DSPN_FN(dspn_conv2d_dgrad_bn)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
                              int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                              int Wo, int dx_ldc, int accumulate,
@@ -2528,6 +2606,22 @@ int dspn_conv2d_dgrad_bn_sadd_route_f32(int N, int H, int W, int Cin, int ldy, i
   return conv2d_dgrad_bn_impl(q, nullptr, q, q, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 0, q, q, q, q, q, 1, q,
                               sizeof(float) * 2 * (size_t)tiles * Cin, q, DSPN_MATH_F32_F16X2 | (dy_planes ? DSPN_MATH_DY_PLANES : 0), q, q,
                               nullptr, 0, nullptr, StridedAddend{q, (H + 1) / 2, (W + 1) / 2, 1}) == 0 ? 1 : 0;
+}
+#endif
+
+#ifndef DSPN_HALF
+int dspn_conv2d_dgrad_bn_recompute_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes) {
+  // the verdict of dispatch_nt for BOTH passes of the 1 x 1 / stride-1 call of that shape, without a launch (pointers as above)
+  float *const q = reinterpret_cast<float *>(uintptr_t(256));
+  const int tiles = dgrad_bn_tiles(N, H, W, Cin, 1);
+  if (tiles <= 0 || N <= 0 || ldy <= 0) return 0;
+  const int math = DSPN_MATH_F32_F16X2 | (dy_planes ? DSPN_MATH_DY_PLANES : 0);
+  const StridedAddend none{nullptr, 0, 0, 0};
+  return conv2d_dgrad_bn_impl(q, nullptr, q, nullptr, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 0, q, q, q, q, q, 1, q,
+                              sizeof(float) * 2 * (size_t)tiles * Cin, nullptr, math, q, q, nullptr, 0, nullptr, none,
+                              BnRecompute{1, nullptr, nullptr, 1}) == 0 &&
+         conv2d_dgrad_bn_impl(q, nullptr, q, q, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 1, q, q, q, nullptr, nullptr, 1, nullptr,
+                              0, nullptr, math, q, q, nullptr, 0, nullptr, none, BnRecompute{2, q, q, 1}) == 0 ? 1 : 0;
 }
 #endif
 

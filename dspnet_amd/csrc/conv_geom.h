@@ -62,7 +62,13 @@ struct ConvGeomT {
   const st_t *sadd;
   int sadd_h, sadd_w;
   unsigned sadd_bytes;             // its size (buffer bound)
-  int probe;                       // host side only: dispatch_nt returns its verdict without launching (dspn_conv2d_dgrad_bn_sadd_route_f32)
+  int probe;                       // host side only: dispatch_nt returns its verdict without launching (the *_route_f32 queries)
+  // The data gradient of a BatchNorm(+ReLU) output that is never stored (dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32 / _apply_f32),
+  // on the routes of the strided addend: 1 = the sums pass (bn_sums as ever, out == NULL: no store, no addend, no magnitude
+  // block), 2 = the apply pass -- out (+)= a g' + c1 bn_x + c0 with the finalize's coefficients bn_coef = [a | c1 | c0], 3 Cout
+  // floats; bn_mean / bn_rstd / bn_sums unused, bn_dy_absmax receives the partial maxima of |out| as stored.
+  int bn_recompute;
+  const float *bn_coef;
 };
 
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

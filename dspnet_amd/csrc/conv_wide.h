@@ -282,7 +282,17 @@ __device__ __forceinline__ void wide_epilogue(const ConvGeom &g, char *wsm, cons
 // with even h and w, +0.0f elsewhere -- takes the place of the accumulate addend: same place in the order of additions, so the
 // stored bits are those of "first writer scatters the compact tensor over zeros, this call accumulates".  A template flag, not a
 // kernel-uniform branch: the launches without the operand keep their instruction stream and register count as they were.
-template <int WAVES_M, int WAVES_N, int EPI, int RB = 16, int SR = 128, bool CLOSE = false, bool SADD = false>       // RB: rows of a 32 x 32 block whose operand rows are in flight together
+// SUMS_ONLY / APPLY (EPI 2 only, template flags for the same reason): the two passes of a data gradient whose output -- the
+// gradient g of a BatchNorm(+ReLU) output -- is never stored, because the BatchNorm backward that would read it back runs in
+// the epilogue of a SECOND pass over the same short-K product (include/dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32 / _apply_f32).
+// SUMS_ONLY: the element arithmetic, the mask, the two sums, the exchange and the table writes of the plain form -- the tables
+// are its bits -- with no store, no addend request and no magnitude block.  APPLY: per column the coefficients (a, c1, c0) the
+// finalize left at g.bn_coef, per element out = a g' + c1 x + c0 (+ out's old value when accumulating) by bn_apply_element
+// (bn_final_job.h: the arithmetic of bn_bwd_apply_kernel, whose stored bits these are); the largest |out| goes where the plain
+// form puts the largest |g| (g.bn_dy_absmax, here the magnitude block of the BatchNorm's dx); no sums, no exchange, no
+// tables.  In place: every element is read and then written by the same lane.
+template <int WAVES_M, int WAVES_N, int EPI, int RB = 16, int SR = 128, bool CLOSE = false, bool SADD = false,
+          bool SUMS_ONLY = false, bool APPLY = false>       // RB: rows of a 32 x 32 block whose operand rows are in flight together
 __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f32x16 (&acc)[2][2], const float inv_a, const float inv_b, const int m0,
                                                 const int n0, const int M, const int tid, const int wave,
                                                 const float *__restrict__ bias, float *__restrict__ out,
@@ -304,7 +314,9 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
   int col[TN];
   unsigned cbyte[TN];
   bool cv[TN];
+  static_assert(!(SUMS_ONLY || APPLY) || (EPI == 2 && !SADD && !(SUMS_ONLY && APPLY)), "the two passes of the recomputed data gradient: BatchNorm-backward epilogue, one at a time");
   float bv[TN], bsc[TN], bsh[TN], bmu[TN], brs[TN];
+  float ka[TN], kc1[TN], kc0[TN];      // APPLY: the finalize's coefficients of this lane's columns
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     col[j] = n0 + wn + j * 32 + lc;
@@ -312,8 +324,10 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
     cbyte[j] = cv[j] ? (unsigned)col[j] * 4u : kOOB;
     bv[j] = (has_bias && cv[j]) ? bias[col[j]] : 0.f;
     bsc[j] = bsh[j] = bmu[j] = brs[j] = 0.f;
+    ka[j] = kc1[j] = kc0[j] = 0.f;
     if (EPI == 2 && cv[j]) {
-      bmu[j] = g.bn_mean[col[j]]; brs[j] = g.bn_rstd[col[j]];
+      if constexpr (APPLY) { ka[j] = g.bn_coef[col[j]]; kc1[j] = g.bn_coef[g.Cout + col[j]]; kc0[j] = g.bn_coef[2 * g.Cout + col[j]]; }
+      else { bmu[j] = g.bn_mean[col[j]]; brs[j] = g.bn_rstd[col[j]]; }
       if (g.bn_relu) { bsc[j] = g.bn_scale[col[j]]; bsh[j] = g.bn_shift[col[j]]; }
     }
   }
@@ -380,10 +394,12 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
           const unsigned off = rb + cbyte[j];
           if constexpr (SADD)      // (an out-of-range offset stays out of range: a row pitch is far below 2^31)
             rq[s_][rr][j] = (rr & 1) ? 0.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_s, (int)(sa_off[j] + (unsigned)(rr >> 1) * pitch), 0, 0));
+          else if constexpr (SUMS_ONLY)      // (nothing is stored: nothing to add to)
+            rq[s_][rr][j] = 0.f;
           else
           rq[s_][rr][j] = addsrc ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_a, (int)off, 0, 0)) : 0.f;
           xq[s_][rr][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_x, (int)off, 0, 0));
-          oq[s_][rr][j] = both ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_o, (int)off, 0, 0)) : 0.f;
+          oq[s_][rr][j] = (both && !SUMS_ONLY && !APPLY) ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_o, (int)off, 0, 0)) : 0.f;
         }
       }
     };
@@ -399,15 +415,27 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           float v = acc[i][j][r] * inv_a * inv_b + bv[j];
+          if constexpr (APPLY) {
+            // g as the sums pass formed it (no addend there: + 0.0f), then the BatchNorm backward's element; the row requested
+            // from `out` is the old value of the gradient this call accumulates into
+            v += 0.f;
+            const float xv = xq[s_][rr][j];
+            const float gd = (!g.bn_relu || fmaf(xv, bsc[j], bsh[j]) > 0.f) ? v : 0.f;
+            float o = dspn::bn_apply_element(ka[j], gd, kc1[j], xv, kc0[j]);
+            if (accum) o += rq[s_][rr][j];
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rs_o, (int)(rb + cbyte[j]), 0, 0);
+            gmx = fmaxf(gmx, fabsf(o));
+          } else {
           v += rq[s_][rr][j];
           if (both) v += oq[s_][rr][j];
           if (relu) v = v > 0.f ? v : 0.f;
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_o, (int)(rb + cbyte[j]), 0, 0);
+          if constexpr (!SUMS_ONLY) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_o, (int)(rb + cbyte[j]), 0, 0);
           const float xv = xq[s_][rr][j];
           const float gd = (!g.bn_relu || fmaf(xv, bsc[j], bsh[j]) > 0.f) ? v : 0.f;
           gs[j] += gd;
           gss[j] += gd * ((xv - bmu[j]) * brs[j]);
-          gmx = fmaxf(gmx, fabsf(v));
+          if constexpr (!SUMS_ONLY) gmx = fmaxf(gmx, fabsf(v));
+          }
         }
       }
     }
@@ -478,7 +506,7 @@ __device__ __forceinline__ void direct_epilogue(const ConvGeom &g, char *exch, f
   }
   if constexpr (EPI == 0) gmx_all = fmaxf(gmx_all, gmx);
   if constexpr (EPI == 2) gmx_all = fmaxf(gmx_all, gmx);
-  if constexpr (EPI != 0) {
+  if constexpr (EPI != 0 && !APPLY) {
     // partial p = 2 (wave row) + half-wave of column c at red[(p * BN + c) * 4 ..]: EPI 1 (count, mean, M2) and, at red2, (min, max);
     // EPI 2 (sum, sum x-hat).  The previous tile's exchange was read before the k-loop barriers every wave has passed since.
     float *red = reinterpret_cast<float *>(exch);
@@ -566,8 +594,8 @@ __device__ __forceinline__ void wide_publish_absmax(const ConvGeom &g, char *wsm
 // the last k-step" (out of range, zeros) are here the LIVE requests of the next tile's first k-steps -- and the epilogue works
 // from the accumulators (direct_epilogue), so the next tile's images are on their way while the current tile is written out.
 // Same K order, same epilogue arithmetic per element: the bits of the plain loop.
-// SADD: the strided addend of direct_epilogue (XT, EPI 2)
-template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR = 128, bool XT = false, bool SADD = false>
+// SADD: the strided addend of direct_epilogue (XT, EPI 2); BNR: 1 / 2 = its SUMS_ONLY / APPLY form (XT, EPI 2)
+template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR = 128, bool XT = false, bool SADD = false, int BNR = 0>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
     const st_t *__restrict__ in, const st_t *__restrict__ wgt, const float *__restrict__ bias,
     st_t *__restrict__ out, const ConvGeom g, const int m_tiles, const int n_tiles,
@@ -587,6 +615,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
   static_assert(BM % SR == 0, "BatchNorm tables are per SR rows");
   static_assert(!XT || !kHalf, "the tile-spanning loop: float build");
   static_assert(!SADD || (XT && EPI == 2 && SR == 128), "the strided addend: tile-spanning loop, BatchNorm-backward sums, 128-row tables");
+  static_assert(BNR == 0 || (XT && EPI == 2 && SR == 128 && !SADD && BNR <= 2), "the recomputed data gradient: tile-spanning loop, BatchNorm-backward epilogue, 128-row tables");
   extern __shared__ __attribute__((aligned(1024))) char wsm[];
 
 #ifdef DSPN_ABLATE
@@ -789,8 +818,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
         // the images of this k-step have landed (this wave's pieces: the wait; the other waves': the barrier).  A tile's first D
         // k-steps were requested BEFORE the previous tile's epilogue, whose 64 stores per wave (always issued: out-of-range
         // lanes are dropped by the hardware) are younger, as are the D - 1 requests behind them: "at most 63 younger
-        // operations outstanding" says they have landed without asking for those stores to be acknowledged
-        if (!first && kt < D) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
+        // operations outstanding" says they have landed without asking for those stores to be acknowledged.  (BNR 1 stores
+        // nothing, and the epilogue's row loads have been waited for where their values were used: the plain count holds.)
+        if (BNR != 1 && !first && kt < D) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NI) : "memory");
         __builtin_amdgcn_s_barrier();
         if (kt + D < nk) {
@@ -808,14 +838,14 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_ntw_kernel(
       char *exch = wsm + STAGES * STG;
       if constexpr (EXCH_IN_RING) {
         exch = wsm + last_slot * STG;
-        if constexpr (EPI != 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }   // every wave has read its last fragments
+        if constexpr (EPI != 0 && BNR != 2) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }   // every wave has read its last fragments (BNR 2: no exchange)
       }
-      if constexpr (!kHalf) direct_epilogue<WAVES_M, WAVES_N, EPI, (EPI == 2 ? 4 : 8), SR, false, SADD>(g, exch, acc, inv_a, inv_b, m0, n0, M, tid, wave, bias, out, residual, gmx_all);
+      if constexpr (!kHalf) direct_epilogue<WAVES_M, WAVES_N, EPI, (EPI == 2 ? 4 : 8), SR, false, SADD, BNR == 1, BNR == 2>(g, exch, acc, inv_a, inv_b, m0, n0, M, tid, wave, bias, out, residual, gmx_all);
       DSPN_STAMP(5);
     }
     DSPN_STAMP_FLUSH;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the last, out-of-range requests)
-    if constexpr (EPI != 1) {
+    if constexpr (EPI != 1 && BNR != 1) {                // (BNR 1 stores nothing: no magnitude to publish)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                      // (the exchange of the last tile has been read)
       wide_publish_absmax<NWV>(g, wsm, gmx_all, tid);
@@ -1300,7 +1330,7 @@ int launch_ntv(WideLoop loop, const float *in, const float *w, const float *bias
 #endif   // !DSPN_HALF
 
 // host side: one launch of the wide family.  Persistent grid as conv_nt_kernel's (dspn::persistent_grid).
-template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR, bool XT, bool SADD = false>
+template <int WAVES_M, int WAVES_N, int STAGES, int EPI, int SR, bool XT, bool SADD = false, int BNR = 0>
 int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s,
                     const st_t *residual) {
   constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64;
@@ -1310,9 +1340,10 @@ int launch_ntw_impl(const st_t *in, const st_t *w, const float *bias, st_t *out,
   // eight waves keep it in the ring slot of the tile's last k-step)
   const size_t lds = XT ? (size_t)STAGES * (BM + BN) * 128 + ((WAVES_M * WAVES_N == 8 || BM == 256) ? 0 : sizeof(float) * 4 * BN * 6)
                         : std::max<size_t>((size_t)STAGES * (BM + BN) * 128, sizeof(float) * BM * (BN + 4));
-  constexpr auto kern = conv_ntw_kernel<WAVES_M, WAVES_N, STAGES, EPI, SR, XT, SADD>;
+  constexpr auto kern = conv_ntw_kernel<WAVES_M, WAVES_N, STAGES, EPI, SR, XT, SADD, BNR>;
   const int grid_x = dspn::persistent_grid<kern>(WAVES_M * WAVES_N * 64, lds, (long long)mt * nt, "conv_ntw",
-                                                 SADD ? "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d,sadd>" : "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d>",
+                                                 SADD ? "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d,sadd>" : BNR == 1 ? "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d,sums>"
+                                                 : BNR == 2 ? "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d,apply>" : "conv_ntw<%d,%d,stages=%d,epi=%d,xt=%d>",
                                                  WAVES_M, WAVES_N, STAGES, EPI, (int)XT);
   if (grid_x < 0) return grid_x;
   {
@@ -1326,8 +1357,11 @@ template <int WAVES_M, int WAVES_N, int STAGES, int SR, bool XT>
 int launch_ntw_on(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s, const st_t *residual) {
   if constexpr (XT && SR == 128 && WAVES_M == 2 && !kHalf) {      // (the members dispatch_nt lets the strided addend through to)
     if (g.bn_sums && g.sadd) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT, true>(in, w, bias, out, g, s, residual);
+    if (g.bn_recompute == 1) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT, false, 1>(in, w, bias, out, g, s, residual);
+    if (g.bn_recompute == 2) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT, false, 2>(in, w, bias, out, g, s, residual);
   }
   if (g.sadd) return dspn::fail(DSPN_ERR_ARG_, "conv: this kernel does not take a strided addend");
+  if (g.bn_recompute) return dspn::fail(DSPN_ERR_ARG_, "conv: this kernel has no sums-only / apply form");
   if (g.bn_sums) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 2, SR, XT>(in, w, bias, out, g, s, residual);
   if (g.stats) return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 1, SR, XT>(in, w, bias, out, g, s, residual);
   return launch_ntw_impl<WAVES_M, WAVES_N, STAGES, 0, SR, XT>(in, w, bias, out, g, s, residual);

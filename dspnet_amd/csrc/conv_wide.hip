@@ -6,6 +6,7 @@
 #include "dspn_store.h"
 #include "dspn_pieces.h"
 #include "conv_geom.h"
+#include "bn_final_job.h"
 #include "../../include/dspn_nn.h"
 #include <algorithm>
 #include <type_traits>
@@ -119,7 +120,7 @@ static WideTile wide_tile_choice(long long M, int Cout, int nk, int fused_epilog
   return WideTile::P128x128;
 }
 WideRoute wide_route(const ConvGeomT<st_t> &g, long long M, int nk) {
-  WideRoute r{wide_tile_choice(M, g.Cout, nk, (g.stats || g.bn_sums) ? 1 : 0)};
+  WideRoute r{wide_tile_choice(M, g.Cout, nk, (g.stats || g.bn_sums || g.bn_recompute) ? 1 : 0)};      // (the apply pass of a recomputed data gradient takes its sums pass's route)
 #ifndef DSPN_HALF
   if (!r) return r;
   // a float A operand (with or without the folded BatchNorm affine) goes through the family's register-staged members; there

@@ -2022,6 +2022,13 @@ static int bn_bwd_apply_launch(hipStream_t s, const st_t *x, const float *scale,
   return dspn::check_launch(what);
 }
 
+#ifndef DSPN_HALF
+void dspn::bn_jobs_run(hipStream_t s) {
+  for (dspn::BnFinalJob job; dspn::bn_job_take(s, &job);)
+    hipLaunchKernelGGL(bn_final_job_kernel, dim3(job.blocks), dim3(256), 0, s, job);
+}
+#endif
+
 extern "C" {
 
 #ifndef DSPN_HALF
@@ -2230,7 +2237,8 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
   DSPN_REQUIRE((flags & ~(DSPN_BN_SUMS_PLANES | DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY | DSPN_BN_SUMS_PARKED)) == 0 &&
                    half != (DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY) && (!parked || half == DSPN_BN_SUMS_FINALIZE_ONLY),
                "bn_backward_from_sums: flag word = dx_planes | 2 (finalize only, | 8: parked for the next weight gradient) | 4 (apply only)");
-  DSPN_REQUIRE(x && dy && mean && rstd && workspace && tile_sums && tiles > 0, "bn_backward_from_sums: null pointer");
+  // (the finalize reads no dy: a caller whose data gradient stored none -- dspn_conv2d_dgrad_bn_sums -- passes NULL with flag 2)
+  DSPN_REQUIRE(x && (dy || half == DSPN_BN_SUMS_FINALIZE_ONLY) && mean && rstd && workspace && tile_sums && tiles > 0, "bn_backward_from_sums: null pointer");
   // dx == NULL (parameters only): the finalize alone, nothing parked -- no apply half follows
   DSPN_REQUIRE(dx || flags == DSPN_BN_SUMS_FINALIZE_ONLY, "bn_backward_from_sums: dx == NULL needs the finalize-only flag word 2");
   DSPN_REQUIRE(!planes || (!dspn::kHalf && !accumulate && C % 32 == 0 && dx_absmax && dy_absmax && x_chan_minmax &&
@@ -2244,8 +2252,7 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
     return dspn::fail(DSPN_ERR_WORKSPACE_, "bn_backward_from_sums: workspace too small (3*C floats)");
   float *coef = static_cast<float *>(workspace);      // the finalize hands the apply pass its coefficients here
   if (half == DSPN_BN_SUMS_APPLY_ONLY) {      // jobs of this stream no weight gradient took: here, before the apply pass
-    for (dspn::BnFinalJob job; dspn::bn_job_take(S_(stream), &job);)
-      hipLaunchKernelGGL(bn_final_job_kernel, dim3(job.blocks), dim3(256), 0, S_(stream), job);
+    dspn::bn_jobs_run(S_(stream));
   } else {
     // a long table is grouped by a launch of its own, now, also where the rest is parked (that level needs hundreds of workgroups)
     BnTiles t{tile_sums, tiles, 1, tiles, nullptr};

@@ -258,6 +258,7 @@ class Graph:
         # the compact data gradient of a projection shortcut between its two calls (graph_plan.shortcut_compaction): ONE flat
         # buffer sized for the largest pair -- a pair's two calls are neighbours on the step's stream, so only one is live
         self.sc_compact_buf = None
+        self.bn1_recompute_calls = 0   # apply passes run inside a recomputed data gradient so far (Conv._recompute_route)
         self.wt_table = None       # descriptor table of every Conv's (weight, transposed weight) pair
         self.wt_batched = False    # True while backward() runs after one batched transpose launch
         self.arena = self.grad_arena = self.mom_arena = None
@@ -821,7 +822,7 @@ class Graph:
             if isinstance(n, BatchNorm):
                 if n._pending is not None:
                     streams.add(n._pending[2])
-                n._pending, n.bwd_sums_ready = None, False
+                n._pending, n.bwd_sums_ready, n._recompute = None, False, None
         for s in streams:      # (a job no apply half has run belongs to a node that is still pending)
             fn.bn_discard_parked(s)
 
@@ -1056,6 +1057,9 @@ class BatchNorm(Node):
         # whose data gradient gathered the sums: (args, kwargs, stream handle) of the apply half, or None.  The coefficients
         # wait in bwd_ws, which no other node writes (Graph.abandon_backward drops a pass that never gets to the apply half)
         self._pending = None
+        # this backward pass: the data gradient that gathered the sums stored no dy for this node (Conv._recompute_route):
+        # (conv, dy, planes, dy magnitude, weight magnitude) of the apply pass that forms it again
+        self._recompute = None
 
     def _moving(self):
         """the dspn_bn_moving block of this forward's finalize, or None (batch statistics, nothing tracked)"""
@@ -1119,17 +1123,33 @@ class BatchNorm(Node):
 
     def _from_sums(self, beside, args, kw):
         kw["workspace"] = self.bwd_ws
-        if not beside:
+        if beside:
+            fn.bn_backward_from_sums(*args, phase=1, park=True, **kw)
+            self._pending = (args, kw, fn.stream())
+        elif self._recompute is None:
             fn.bn_backward_from_sums(*args, **kw)
+        else:      # (the gradient was never stored: the finalize now, the apply pass in the data gradient that forms it again)
+            fn.bn_backward_from_sums(*args, phase=1, **kw)
+            self._apply(args, kw)
+
+    def _apply(self, args, kw):
+        """the apply half from the coefficients the finalize left in bwd_ws: the apply kernel over the stored gradient, or --
+        the data gradient stored none (Conv._recompute_route) -- that data gradient again, with the apply in its epilogue"""
+        rc, self._recompute = self._recompute, None
+        if rc is None:
+            fn.bn_backward_from_sums(*args, phase=2, **kw)
             return
-        fn.bn_backward_from_sums(*args, phase=1, park=True, **kw)
-        self._pending = (args, kw, fn.stream())
+        conv, dy, planes, dya, wa = rc
+        fn.conv2d_dgrad_bn_apply(dy, conv.wt, self.x.data, self.scale, self.shift, self.relu, self.bwd_ws, kw["dx"],
+                                 accumulate=kw["accumulate"], dx_absmax=kw["dx_absmax"], wt_planes=conv.wtp, math=conv.math,
+                                 dy_absmax=dya, w_absmax=wa, dy_planes=planes, wt_shape=conv.wt_shape)
+        self._g.bn1_recompute_calls += 1
 
     def backward(self, beside=False):
         if self._pending is not None:
             args, kw, _ = self._pending
             self._pending = None
-            fn.bn_backward_from_sums(*args, phase=2, **kw)
+            self._apply(args, kw)
             return
         if not self.out._gw:
             return
@@ -1206,6 +1226,24 @@ FUSE_CONV_MAGNITUDES = os.environ.get("DSPN_CONV_MAGNITUDES", "1") != "0"
 # even positions (graph_plan.shortcut_compaction); DSPN_SC_COMPACT=0: the shortcut writes the full tensor -- three quarters of
 # it zeros -- and conv1 accumulates (same-box A/B; same bits either way)
 SC_COMPACT = os.environ.get("DSPN_SC_COMPACT", "1") != "0"
+
+# The bn1 of the dim-match residual units reads the residual stream; the gradient of its output has one writer (conv1's data
+# gradient, a 1 x 1 product over C / 4 channels) and one reader (bn1's backward).  On marked pairs (graph_plan.bn1_recompute)
+# that gradient is never stored: conv1's data gradient runs for the sums alone, and again with the apply pass in its epilogue
+# (include/dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32 / _apply_f32) -- four passes over the M x C tensor instead of six.
+# DSPN_BN1_RECOMPUTE: 0 the data gradient + apply kernel pair everywhere, 1 the layers bn1_recompute_pays() names (default),
+# 2 every layer that has the route (measurements).
+BN1_RECOMPUTE = int(os.environ.get("DSPN_BN1_RECOMPUTE", "1"))
+
+
+def bn1_recompute_pays(M, C, K):
+    """The layers that take the route by default, by shape (M rows of C channels, K = channels of the product): the ONE place
+    that decides.  Measured per stage of the resnet-50 step at 32 x 512 x 512 (profiles/bn1_recompute_last_step_by_kernel.txt,
+    DESIGN.md section 7; data gradient + apply kernel -> sums pass + apply pass, ms per unit): stage 1 (524288, 256, 64) 0.607 ->
+    0.495, stage 2 (131072, 512, 128) 0.317 -> 0.281, stage 3 (32768, 1024, 256) 0.188 -> 0.186 (inside the 0.008 spread of its
+    launches), stage 4 (8192, 2048, 512) 0.136 -> 0.143.  The route pays where the second product is short beside the two passes
+    it saves (K <= 128) and the M x C tensor does not fit the 256 MiB Infinity Cache, i.e. the saved passes are HBM traffic."""
+    return K <= 128 and 4 * M * C >= 256 << 20
 
 
 def xa_unavailable(conv):
@@ -1285,6 +1323,7 @@ class Conv(Node):
         self.bn_bwd_node = None      # the BatchNorm whose backward sums this node's data gradient gathers (graph_plan.bn_backward_fusion)
         self._wg_worth = None        # _wgrad_worth_a_stream, once estimated
         self.guard_fb = False        # range guard (Graph._update_guard): this pass's calls run in the three-piece bf16 math
+        self.bn1_recompute = False   # its data gradient may run sums-only, and again in bn_bwd_node's backward (graph_plan.bn1_recompute)
         self.sc_pair = None          # the other convolution of a (conv1, projection shortcut) pair (graph_plan.shortcut_compaction)
         self.wp = self.wtp = None
         if g.device.type == "cuda":
@@ -1548,6 +1587,13 @@ class Conv(Node):
             bn.bwd_sums_ready = True
             if bn.dx_planes:         # that BatchNorm's backward bounds its dx from the largest gradient stored here
                 bn_dya = self._g.scalar(bn.am_dyin)
+            if self._recompute_route(bn, planes, acc):
+                # the sums alone: dx stays unwritten; bn's backward runs this product again (BatchNorm._apply)
+                fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, bn_bwd=bn_bwd, wt_planes=self.wtp,
+                                math=self.math, dy_absmax=dya, w_absmax=wa, dy_planes=planes, wt_shape=self.wt_shape,
+                                sums_only=True)
+                bn._recompute = (self, dy, planes, dya, wa)
+                return
         if self.guard_fb:
             w3 = self._w3(True)
             fn.conv2d_dgrad(dy, self.wt if w3 is None else None, self.x.shape, self.stride, self.pad, self.dil, out=dx,
@@ -1560,6 +1606,20 @@ class Conv(Node):
         fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, out=dx, accumulate=acc,
                         bn_bwd=bn_bwd, wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa,
                         bn_dy_absmax=bn_dya, dy_planes=planes, wt_shape=self.wt_shape, strided_addend=sa)
+
+    def _recompute_route(self, bn, planes, acc):
+        """This pass, for a pair graph_plan.bn1_recompute marked: does the data gradient run for the sums alone, and again in
+        bn's backward?  No -- the pair of today -- with the knob off, on a layer the predicate leaves out, where either node
+        is on the range guard's fallback, where bn has no dx to write (its input needs no gradient) or folds a pooling
+        backward, where another writer got to the gradient first, or where the library has no kernel for the call."""
+        if (not self.bn1_recompute or not BN1_RECOMPUTE or acc or self.guard_fb or not planes or self._g.device.type != "cuda"
+                or not bn.x.requires_grad or bn.pool_grad is not None or bn.dx_planes or bn._pending is not None):
+            return False
+        N, H, W, C = self.x.shape
+        K = self.wt_shape[3]
+        if BN1_RECOMPUTE < 2 and not bn1_recompute_pays(N * H * W, C, K):
+            return False
+        return fn.conv2d_dgrad_recompute_route(self.x.shape, K, planes)
 
     def _compact_shortcut(self, dy, planes, dya, wa):
         """The data gradient of a projection shortcut (1 x 1, stride 2, pad 0) as the stride-1 1 x 1 data gradient on the

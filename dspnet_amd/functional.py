@@ -50,6 +50,11 @@ _lib.register({
     "dspn_conv2d_dgrad_bn_sadd_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                                            _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp, _i, _i, _vp]),
     "dspn_conv2d_dgrad_bn_sadd_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
+    "dspn_conv2d_dgrad_bn_sums_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                           _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dspn_conv2d_dgrad_bn_apply_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                            _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dspn_conv2d_dgrad_bn_recompute_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
     "dspn_bn_backward_from_sums_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _i, _i, _i,
                                             _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "dspn_bn_discard_parked": (_i, [_vp]),
@@ -123,7 +128,8 @@ _lib.register({
 
 
 # the bfloat16-tensor twins (include/dspn_nn.h): same argument lists as the *_f32 entries
-for _name in ("dspn_conv2d_forward_bn", "dspn_conv2d_dgrad_bn", "dspn_conv2d_dgrad_bn_sadd", "dspn_conv2d_wgrad_bn", "dspn_conv2d_wgrad_slabs",
+for _name in ("dspn_conv2d_forward_bn", "dspn_conv2d_dgrad_bn", "dspn_conv2d_dgrad_bn_sadd", "dspn_conv2d_dgrad_bn_sums",
+              "dspn_conv2d_dgrad_bn_apply", "dspn_conv2d_wgrad_bn", "dspn_conv2d_wgrad_slabs",
               "dspn_conv2d_input_sum_grad", "dspn_bn_stats", "dspn_bn_apply", "dspn_bn_backward",
               "dspn_bn_backward_from_sums", "dspn_add", "dspn_relu_backward", "dspn_relu_backward_colsum", "dspn_colsum",
               "dspn_nchw_to_nhwc", "dspn_copy_block", "dspn_tap_sum", "dspn_tap_spread", "dspn_maxpool_forward", "dspn_maxpool_forward_bn",
@@ -573,9 +579,36 @@ def conv2d_dgrad_addend_route(x_shape, ldy, dy_planes):
     return bool(L().dspn_conv2d_dgrad_bn_sadd_route_f32(N, H, W, C, ldy, int(bool(dy_planes))))
 
 
+def conv2d_dgrad_recompute_route(x_shape, ldy, dy_planes):
+    """True when the 1 x 1 / stride-1 data gradient dy (N,H,W,ldy) -> dx x_shape, "f16x2" math, has the sums-only and the
+    apply form under the current launch settings (conv2d_dgrad(sums_only=True) / conv2d_dgrad_bn_apply; a host-side query)"""
+    N, H, W, C = x_shape
+    return bool(L().dspn_conv2d_dgrad_bn_recompute_route_f32(N, H, W, C, ldy, int(bool(dy_planes))))
+
+
+def conv2d_dgrad_bn_apply(dy, wt, bn_x, scale, shift, relu, bn_workspace, dx, accumulate=False, dx_absmax=None, wt_planes=None,
+                          math=None, dy_absmax=None, w_absmax=None, dy_planes=False, wt_shape=None):
+    """The second pass of a data gradient that is never stored (include/dspn_nn.h dspn_conv2d_dgrad_bn_apply_f32): the 1 x 1
+    product of conv2d_dgrad(..., sums_only=True) again, and dx (+)= a g' + c1 bn_x + c0 from its accumulators, with the
+    coefficients the finalize (bn_backward_from_sums(phase=1, workspace=bn_workspace)) left in bn_workspace.  In the place of
+    bn_backward_from_sums(phase=2): the same dx and dx_absmax.  Refused (RuntimeError naming the entry) where no kernel takes it."""
+    N, H, W, C = bn_x.shape
+    Cin, R, S, ldy = wt.shape if wt is not None else wt_shape
+    assert dx.shape == bn_x.shape and dy.shape == (N, H, W, ldy) and Cin == C, (dx.shape, dy.shape, Cin)
+    math = _math_code(math)
+    if not (math == 3 and dy.dtype == torch.float32):
+        dy_absmax = w_absmax = None
+    check(_f("dspn_conv2d_dgrad_bn_apply", dy)(ptr(dy), ptr(wt), ptr(wt_planes), ptr(dx), N, H, W, Cin, ldy, R, S, 1, 0, 0, 1, H, W,
+                                              dx.shape[3], int(accumulate), ptr(bn_x), ptr(scale), ptr(shift), int(relu),
+                                              ptr(dx_absmax), math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax),
+                                              ptr(w_absmax), ptr(bn_workspace), bn_workspace.numel() * bn_workspace.element_size(),
+                                              stream()), "conv2d_dgrad_bn_apply")
+    return dx
+
+
 def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=False, bn_bwd=None, wt_planes=None,
                  math=None, dy_absmax=None, w_absmax=None, bn_dy_absmax=None, dy_planes=False, wt_shape=None,
-                 strided_addend=None):
+                 strided_addend=None, sums_only=False):
     """dy (N,Ho,Wo,ldy), wt (Cin,R,S,ldy) -> dx (N,H,W,ldc>=Cin).
     strided_addend: a compact (N, ceil(H/2), ceil(W/2), Cin) tensor -- the data gradient of a 1 x 1 / stride-2 convolution of
     the same input -- added at the positions with even h and w (+0.0 elsewhere) where `accumulate` would add dx's old value;
@@ -583,7 +616,9 @@ def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=F
     bn_bwd = (bn_x, scale, shift, mean, rstd, relu, sums): dx is the complete gradient of a BatchNorm(+ReLU) output
     whose input was bn_x; the two reductions of its backward pass are written to sums (tiles, 2, Cin).
     wt_planes: the piece planes of wt (weight_planes(w, transposed=True, cols=ldy)), used in the split math when
-    ldy % 32 == 0 (made here from wt when the caller keeps none)."""
+    ldy % 32 == 0 (made here from wt when the caller keeps none).
+    sums_only (with bn_bwd): the sums tables alone -- dx is not stored and None comes back; conv2d_dgrad_bn_apply forms the
+    product again (include/dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32: refused where no kernel takes it)."""
     N, H, W, Cx = x_shape
     # wt may be None when the call reads piece planes (wt_planes, split math with ldy % 32 == 0): wt_shape = (Cin, R, S, ldy)
     Cin, R, S, ldy = wt.shape if wt is not None else wt_shape
@@ -603,14 +638,16 @@ def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=F
     else:
         wt_planes = None
     Ho, Wo = dy.shape[1], dy.shape[2]
-    if out is None:
+    if sums_only:
+        assert out is None and bn_bwd is not None and not accumulate and bn_dy_absmax is None and strided_addend is None
+    elif out is None:
         out = (zeros if Cx != Cin else empty)(N, H, W, Cx, device=dy.device, dtype=dy.dtype)
-    assert (wt is None or wt.dtype == dy.dtype) and dy.dtype == out.dtype, (dy.dtype, out.dtype)
+    assert (wt is None or wt.dtype == dy.dtype) and (sums_only or dy.dtype == out.dtype), (dy.dtype, out)
     ws = workspace(L().dspn_conv2d_split_workspace_bytes(N * H * W, Cin), dy.device, "split")
     ph, pw = _hw(pad)
     bx, bsc, bsh, bmu, brs, brelu, bsums = bn_bwd if bn_bwd is not None else (None, None, None, None, None, False, None)
     args = (ptr(dy), ptr(wt), ptr(wt_planes), ptr(out), N, H, W, Cin, ldy, R, S, stride, ph, pw,
-            dil, Ho, Wo, out.shape[3], int(accumulate), ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu),
+            dil, Ho, Wo, Cx if sums_only else out.shape[3], int(accumulate), ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu),
             ptr(brs), int(brelu), ptr(bsums), 0 if bsums is None else bsums.numel() * 4,
             ptr(bn_dy_absmax), math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax),
             ptr(w_absmax), ptr(ws), ws.numel())
@@ -618,6 +655,8 @@ def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=F
         sa = strided_addend
         assert sa.dtype == out.dtype and sa.is_contiguous() and sa.shape == (N, (H + 1) // 2, (W + 1) // 2, Cin), (sa.shape, x_shape)
         check(_f("dspn_conv2d_dgrad_bn_sadd", dy)(*args, ptr(sa), sa.shape[1], sa.shape[2], stream()), "conv2d_dgrad")
+    elif sums_only:
+        check(_f("dspn_conv2d_dgrad_bn_sums", dy)(*args, stream()), "conv2d_dgrad")
     else:
         check(_f("dspn_conv2d_dgrad_bn", dy)(*args, stream()), "conv2d_dgrad")
     return out
@@ -854,7 +893,7 @@ def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, r
              (BN_SUMS_PARKED if park else 0))
     if workspace is None:
         workspace = _scratch(12 * C + L().dspn_bn_tiles_workspace_bytes(tiles, C), x.device, "bn_from_sums")
-    assert dy.dtype == x.dtype
+    assert (dy is None and phase == 1) or dy.dtype == x.dtype      # (the finalize alone reads no dy)
     check(_f("dspn_bn_backward_from_sums", x)(ptr(x), ptr(scale), ptr(shift), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma),
                                              ptr(sums), tiles, ptr(dx), ptr(dgamma), ptr(dbeta), rows, C, int(relu),
                                              int(accumulate), ptr(dx_absmax), ptr(dx_absmin), ptr(dy_absmax), ptr(x_chan_minmax),

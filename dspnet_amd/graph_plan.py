@@ -44,6 +44,7 @@ def plan(g):      # (the passes in the order their decisions build on each other
     if os.environ.get("DSPN_DY_PLANES", "1") != "0":      # (A/B switch)
         gradient_planes(g, index)
     shortcut_compaction(g, index)
+    bn1_recompute(g, index)
 
 
 def resolve_auto_deferred(g, index):
@@ -163,6 +164,27 @@ def shortcut_compaction(g, index):
         largest = max(largest, N * ((H + 1) // 2) * ((W + 1) // 2) * C)
     if largest:
         g.sc_compact_buf = fn.zeros(largest, device=g.device)
+
+
+def bn1_recompute(g, index):
+    """The dim-match residual units: bn1 reads the residual stream and conv1 (1 x 1, stride 1, C -> C / 4) alone reads bn1's
+    output, so the gradient of that output has ONE writer -- conv1's data gradient, which gathers bn1's backward sums -- and ONE
+    reader, bn1's backward.  Marked pairs may leave it unwritten: the data gradient runs for the sums alone and again with the
+    apply pass in its epilogue (include/dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32 / _apply_f32).  A pair: "f16x2" math, float
+    tensors, bn1's dx a float tensor (not piece planes) that is wanted, no projection shortcut beside conv1 (that is an
+    sc_pair); whether a given pass takes the route is the nodes' decision (Conv._recompute_route)."""
+    if g.math != "f16x2" or g.device.type != "cuda":
+        return
+    for idx, c in enumerate(g.nodes):
+        n = c.bn_bwd_node if isinstance(c, E.Conv) else None
+        if n is None or c.sc_pair is not None or c.math != "f16x2" or n.out.dtype != torch.float32:
+            continue
+        if not (c.w.shape[1:3] == (1, 1) and c.stride == 1 and c.pad == (0, 0) and c.dil == 1 and not c.tap_expand
+                and c.input_sum_grad is None and c.x is n.out and n.out.shape[3] == c.w.shape[3]):
+            continue
+        if index.reader_nodes(n.out) != {idx} or n.dx_planes or not n.x.requires_grad:
+            continue
+        c.bn1_recompute = True
 
 
 def input_planes(g):

@@ -212,6 +212,41 @@ int dspn_conv2d_dgrad_bn_sadd_f32(const float *dy, const float *wt, const void *
                                   void *workspace, size_t workspace_bytes, const float *strided_addend, int addend_h, int addend_w,
                                   void *stream);
 int dspn_conv2d_dgrad_bn_sadd_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes);
+/* The data gradient of a BatchNorm(+ReLU) output that is NEVER STORED: where the product is short (a 1 x 1 convolution with few
+ * output channels) and its result g (N,H,W,Cin) is read once, by that BatchNorm's backward, writing g and reading it back costs
+ * more than forming it twice.  Two passes over the same operands take the place of dspn_conv2d_dgrad_bn_f32 followed by the
+ * apply half of dspn_bn_backward_from_sums_f32:
+ *   dspn_conv2d_dgrad_bn_sums_f32    the arguments of dspn_conv2d_dgrad_bn_f32 with dx == NULL, accumulate == 0 and
+ *                                    bn_dy_absmax == NULL: the row-tile tables bn_sums of that call -- the same bits -- and
+ *                                    nothing else: no store, no addend read.
+ *   (the finalize: dspn_bn_backward_from_sums_f32 with DSPN_BN_SUMS_FINALIZE_ONLY, launched or parked as ever; it leaves the
+ *    coefficients [a | c1 | c0], 3 Cin floats, at the start of that BatchNorm's workspace)
+ *   dspn_conv2d_dgrad_bn_apply_f32   the same product again, and from the accumulators
+ *                                        dx = a g' + c1 bn_x + c0 (+ dx when accumulate != 0),   g' = g under the ReLU mask
+ *                                    (bn_scale bn_x + bn_shift > 0, when bn_relu) -- the element arithmetic and the stored bits
+ *                                    of the DSPN_BN_SUMS_APPLY_ONLY call it replaces.  In place on dx; bn_workspace is the
+ *                                    workspace the finalize wrote (>= 3 Cin floats); dx_absmax (optional): DSPN_ABSMAX_SLOTS
+ *                                    partial maxima of |dx| as stored, as that call leaves them (which slot holds which
+ *                                    partial follows the launch grid; their maximum is the same).  A finalize still parked
+ *                                    on the stream is run first, as that call does.
+ * Taken where the strided addend is: DSPN_MATH_F32_F16X2 with dy as piece planes, float tensors, 1 x 1 / stride 1 / pad 0, a
+ * dense dx, N H W % 128 == 0, the plane-fed 128-row tiles on the tile-spanning loop.  Every other call -- another math mode, a
+ * float dy, bfloat16 tensors, split-K, a strided dx -- returns non-zero with dspn_last_error() naming the entry and launches
+ * nothing (a parked finalize stays parked); the caller keeps the pair.
+ * dspn_conv2d_dgrad_bn_recompute_route_f32: 1 when both passes of that shape would be taken under the current launch settings
+ * (no launch, no device access), else 0. */
+int dspn_conv2d_dgrad_bn_sums_f32(const float *dy, const float *wt, const void *wt_planes, float *dx, int N, int H, int W, int Cin, int ldy,
+                                  int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo, int dx_ldc,
+                                  int accumulate, const float *bn_x, const float *bn_scale, const float *bn_shift,
+                                  const float *bn_mean, const float *bn_rstd, int bn_relu, float *bn_sums,
+                                  size_t bn_sums_bytes, float *bn_dy_absmax, int math, const float *dy_absmax, const float *w_absmax,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int dspn_conv2d_dgrad_bn_apply_f32(const float *dy, const float *wt, const void *wt_planes, float *dx, int N, int H, int W, int Cin, int ldy,
+                                   int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo, int dx_ldc,
+                                   int accumulate, const float *bn_x, const float *bn_scale, const float *bn_shift, int bn_relu,
+                                   float *dx_absmax, int math, const float *dy_absmax, const float *w_absmax,
+                                   const void *bn_workspace, size_t bn_workspace_bytes, void *stream);
+int dspn_conv2d_dgrad_bn_recompute_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes);
 
 /* out[c] = sum over every input pixel of the data gradient of the convolution, c < Cin <= 8, computed
  * from per-tap sums of dy without forming the gradient (the first convolution's input only feeds the
@@ -316,6 +351,20 @@ int dspn_conv2d_dgrad_bn_sadd_bf16(const dspn_bf16 *dy, const dspn_bf16 *wt, con
                                    const float *absmax_unused_a, const float *absmax_unused_b, void *workspace,
                                    size_t workspace_bytes, const dspn_bf16 *strided_addend, int addend_h, int addend_w,
                                    void *stream);
+/* (always refused: the sums / apply passes of a data gradient that is never stored exist for float tensors) */
+int dspn_conv2d_dgrad_bn_sums_bf16(const dspn_bf16 *dy, const dspn_bf16 *wt, const void *wt_planes_unused, dspn_bf16 *dx, int N, int H, int W,
+                                   int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo,
+                                   int dx_ldc, int accumulate, const dspn_bf16 *bn_x, const float *bn_scale,
+                                   const float *bn_shift, const float *bn_mean, const float *bn_rstd, int bn_relu,
+                                   float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax_unused, int math,
+                                   const float *absmax_unused_a, const float *absmax_unused_b, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int dspn_conv2d_dgrad_bn_apply_bf16(const dspn_bf16 *dy, const dspn_bf16 *wt, const void *wt_planes_unused, dspn_bf16 *dx, int N, int H, int W,
+                                    int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo,
+                                    int dx_ldc, int accumulate, const dspn_bf16 *bn_x, const float *bn_scale,
+                                    const float *bn_shift, int bn_relu, float *dx_absmax_unused, int math,
+                                    const float *absmax_unused_a, const float *absmax_unused_b, const void *bn_workspace,
+                                    size_t bn_workspace_bytes, void *stream);
 int dspn_conv2d_wgrad_bn_bf16(const dspn_bf16 *x, const float *in_scale, const float *in_shift, int in_relu,
                               const dspn_bf16 *dy, float *dw, int N, int H, int W, int Cin, int Cout, int ldy,
                               int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo,
@@ -446,7 +495,8 @@ int dspn_bn_backward_from_sums_f32(const float *x, const float *scale, const flo
  * alone, from the coefficients an earlier FINALIZE_ONLY call (same arguments, same workspace) left there; | PARKED (with
  * FINALIZE_ONLY) = the finalize is not launched but parked for the next weight-gradient launch on this stream, and the
  * APPLY_ONLY call runs it if none took it.  The finalize is a chain of one or two latency-bound launches on 1 - 64
- * workgroups: a caller keeps it off the critical path this way (dspnet_amd/engine.py, Conv.backward).  0 / 1: both halves. */
+ * workgroups: a caller keeps it off the critical path this way (dspnet_amd/engine.py, Conv.backward).  0 / 1: both halves.
+ * The finalize reads no dy: with FINALIZE_ONLY dy may be NULL (a data gradient that stored none: dspn_conv2d_dgrad_bn_sums_f32). */
 #define DSPN_BN_SUMS_PLANES 1
 #define DSPN_BN_SUMS_FINALIZE_ONLY 2
 #define DSPN_BN_SUMS_APPLY_ONLY 4
