@@ -1905,11 +1905,53 @@ int output_absmax_pass(const st_t *out, const ConvGeom &g, hipStream_t s) {
 #endif
   return 0;
 }
-// one convolution launch: the checks every kernel shares, then the wide family where it is legal and dspn::conv::wide_route
-// names a member, conv_nt_kernel on the tile of nt_config everywhere else
-int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g_in,
-                hipStream_t s, SplitWs ws, const st_t *residual = nullptr) {
-  ConvGeom g = g_in;
+// The forms of a data gradient, in the order of ConvGeom::bn_recompute: Store = dx as ever (with StoreAddend: plus ConvGeom::sadd);
+// SumsOnly / Apply = the two passes of a data gradient that is never stored.  variant_entry: the entry that takes each.
+enum class DgradVariant { Store, SumsOnly, Apply, StoreAddend };
+constexpr const char *variant_entry[4] = {DSPN_FN_NAME(dspn_conv2d_dgrad_bn), DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums),
+                                          DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply), DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd)};
+// What plan_nt decides: a member of the wide family (route), or conv_nt_kernel on the tile `cfg` of nt_config, on eight waves or
+// four, in `splits` parts of `per` of the nk k-steps; w_planes: the weights are read as piece planes; empty: no output point
+struct NtPlan {
+  int cfg = 0, splits = 1, per = 0, nk = 0; long long nblk = 0; bool eight = false, w_planes = false, empty = false;
+  dspn::conv::WideRoute route;
+};
+// What the ROUTE decides about the variants, each rule once (what the arguments alone decide: dgrad_variant_args).  They exist in
+// the direct epilogue of the plane-fed 128-row members on the tile-spanning loop and nowhere else: every other route is refused HERE,
+// by the entry's name -- no second implementation to fall back to; the caller keeps the accumulate path / the dgrad + BatchNorm pair.
+int variant_route_refusal(DgradVariant v, const ConvGeom &g, const NtPlan &p) {
+  const char *who = variant_entry[(int)v];
+  const bool member = (p.route.tile == dspn::conv::WideTile::P128x128 || p.route.tile == dspn::conv::WideTile::P128x256) &&
+                      p.route.loop == dspn::conv::WideLoop::Spanning;
+  if (v == DgradVariant::StoreAddend) {
+    if (kHalf) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend takes float tensors only", who);
+    if (g.bf16 != 3) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs DSPN_MATH_F32_F16X2", who);
+    if (p.splits > 1) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend cannot be combined with split-K (%d splits)", who, p.splits);
+    if (!g.bn_sums) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs the BatchNorm-backward sums (bn_sums)", who);
+    // (W % 4 == 0, W >= 8: a group of four rows of the epilogue lies inside one image row and starts at an even column)
+    if (g.sadd_h != (g.Hg + 1) / 2 || g.sadd_w != (g.Wg + 1) / 2 || g.Wg < 8 || g.Wg % 4 != 0)
+      return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend is (N, ceil(H / 2), ceil(W / 2), Cin) with W >= 8 and W %% 4 == 0, got %d x %d for %d x %d", who,
+                        g.sadd_h, g.sadd_w, g.Hg, g.Wg);
+    if (!member)
+      return dspn::fail(DSPN_ERR_ARG_, "%s: no kernel takes the strided addend on this route (it needs dy as piece planes, N H W %% 128 == 0 "
+                        "and the plane-fed 128-row tiles on the tile-spanning loop)", who);
+    return 0;
+  }
+  if (g.bf16 != 3) return dspn::fail(DSPN_ERR_ARG_, "%s: needs DSPN_MATH_F32_F16X2", who);
+  // (the sums pass carries tables and the apply pass no split workspace: neither is ever split -- a shape that a plain data
+  // gradient splits over K is named as such)
+  if (p.splits > 1 || (g.dense && p.nblk < 192 && p.nk >= 16))
+    return dspn::fail(DSPN_ERR_ARG_, "%s: cannot be combined with split-K (%lld workgroups, %d k-steps: a shape that is split)", who, p.nblk, p.nk);
+  if (!g.a_planes) return dspn::fail(DSPN_ERR_ARG_, "%s: needs dy as piece planes (DSPN_MATH_DY_PLANES)", who);
+  if (!member)
+    return dspn::fail(DSPN_ERR_ARG_, "%s: no kernel on this route (it needs N H W %% 128 == 0 and the plane-fed 128-row tiles on the "
+                      "tile-spanning loop)", who);
+  return 0;
+}
+// The decision for one convolution launch and nothing else (no launch, no device access): completes the geometry (in_bytes,
+// w_bytes, sadd_bytes, flag 16), runs the checks every kernel shares, and names the wide family's member where the family is
+// legal and dspn::conv::wide_route has one, the tile of nt_config everywhere else -- or refuses
+int plan_nt(ConvGeom &g, const st_t *out, const st_t *residual, SplitWs ws, NtPlan &p) {
   g.dbg = g_debug_bits;
   // the 4-element-vector epilogue needs aligned rows (16 bytes float, 8 bytes bf16) in every operand it touches
   constexpr uintptr_t amask = 4 * sizeof(st_t) - 1;
@@ -1924,19 +1966,19 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
     g.in_bytes = (unsigned)ib; g.w_bytes = (unsigned)wb;
   }
   const long long M = (long long)g.N * g.Hg * g.Wg;
-  if (M <= 0) return output_absmax_pass(out, g, s);
+  if (M <= 0) { p.empty = true; return 0; }
   // split mode with whole 32-channel blocks per tap: the kernels read the weights as piece planes
   const bool pre = !kHalf && g.bf16 >= 2 && ((g.Cin / kEPC) & 7) == 0;
   if (pre) {
     if (!g.w_planes)
       return dspn::fail(DSPN_ERR_ARG_, "conv: the split math modes with a multiple of 32 input channels (%d) need the weight operand as piece planes (dspn_conv2d_weight_planes_f32)", g.Cin);
-    w = static_cast<const st_t *>(g.w_planes);
+    p.w_planes = true;
     g.w_bytes = (unsigned)((g.bf16 == 3 ? 4ll : 6ll) * g.Cout * g.WTAPS * g.Cin);
   }
-  const int cfg = nt_config(M, g.Cout);
-  const long long nblk = ((M + kNtBm[cfg] - 1) / kNtBm[cfg]) * ((g.Cout + kNtBn[cfg] - 1) / kNtBn[cfg]);
-  const int nk = (g.TR * g.TS * (g.Cin / kEPC) + 7) >> 3;
-  int splits = 1, per = nk;
+  p.cfg = nt_config(M, g.Cout);
+  p.nblk = ((M + kNtBm[p.cfg] - 1) / kNtBm[p.cfg]) * ((g.Cout + kNtBn[p.cfg] - 1) / kNtBn[p.cfg]);
+  p.nk = (g.TR * g.TS * (g.Cin / kEPC) + 7) >> 3;
+  p.per = p.nk;
   if (g.a_planes && !(pre && g.bf16 == 3 && !g.in_scale))
     return dspn::fail(DSPN_ERR_ARG_, "conv: a piece-plane operand needs DSPN_MATH_F32_F16X2, a multiple of 32 channels (%d) and no input affine", g.Cin);
   if (g.stats && (!g.dense || !(g.flags & 16) || g.Cout % 4 != 0))
@@ -1945,12 +1987,12 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
     return dspn::fail(DSPN_ERR_ARG_, "conv: BatchNorm-backward sums cannot be combined with an input affine or output statistics");
   if (g.bn_sums && (!(g.flags & 16) || g.Cout % 4 != 0))
     return dspn::fail(DSPN_ERR_ARG_, "conv2d_dgrad: BatchNorm sums need a 16-byte aligned dx with Cin %% 4 == 0");
-  if (g.dense && nblk < 192 && nk >= 16 && ws.ptr && !g.stats && !g.bn_sums) {
-    splits = (int)std::min<long long>((384 + nblk - 1) / nblk, nk / 8);
+  if (g.dense && p.nblk < 192 && p.nk >= 16 && ws.ptr && !g.stats && !g.bn_sums) {
+    int splits = (int)std::min<long long>((384 + p.nblk - 1) / p.nblk, p.nk / 8);
     splits = std::max(1, std::min(splits, 32));
     while (splits > 1 && sizeof(float) * (size_t)splits * M * g.Cout > ws.bytes) --splits;
-    per = (nk + splits - 1) / splits;
-    splits = (nk + per - 1) / per;
+    p.per = (p.nk + splits - 1) / splits;
+    p.splits = (p.nk + p.per - 1) / p.per;
   }
   // The 128x128 tile on 8 waves (4 x 2 of 32 x 64; two workgroups put 4 waves on every SIMD instead of 2): one wave
   // per SIMD reaches 67 % of the MFMA rate in this loop, two 81 %, four 93 % on a plain 1x1 layer (in-kernel stamps,
@@ -1961,14 +2003,14 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
   // bf16 tensors: the main loop is ~3x shorter, the fused epilogues cost relatively more, and the 8-wave form wins for
   // every epilogue (measured on the resnet-50 step: 28.6 -> 26.1 ms)
   // the split mode's kernels all fit the 128-register budget of the 8-wave form without scratch, fused epilogues included
-  const bool eight = eight_mode == 0 ? false : eight_mode == 1 ? true : (kHalf || g.bf16 >= 2) ? true
-                     : ((!g.stats && !g.bn_sums) || (eight_mode == 2 && one_tap && g.bn_sums) || (eight_mode == 3 && one_tap));
+  p.eight = eight_mode == 0 ? false : eight_mode == 1 ? true : (kHalf || g.bf16 >= 2) ? true
+            : ((!g.stats && !g.bn_sums) || (eight_mode == 2 && one_tap && g.bn_sums) || (eight_mode == 3 && one_tap));
   // The wide family (conv_wide.h): both operands pure copies, 64 x 64 outputs per wave.  Legal when the vector epilogue applies,
   // there is at least one tap, no split-K, and the BatchNorm tables are per 128 rows (cfg 0), or per 64 rows with at most 64 output
   // columns (cfg 2) -- the layouts the wide epilogue writes -- and the A operand is a pure copy: fp16 piece planes in the float
   // build (=> two-piece math, whole 32-channel blocks, no input affine), the bf16 tensor itself in the bf16 build (whole
   // 64-channel blocks, no input affine).
-  bool wide_ok = splits == 1 && (cfg == 0 || (cfg == 2 && g.Cout > 32 && g.Cout <= 64)) && (g.flags & 16) && g.Cout % 4 == 0 &&
+  bool wide_ok = p.splits == 1 && (p.cfg == 0 || (p.cfg == 2 && g.Cout > 32 && g.Cout <= 64)) && (g.flags & 16) && g.Cout % 4 == 0 &&
                  g.TR * g.TS > 0;
   // bf16 tensors: legal, bit-identical (tests/test_wide_tiles_gpu.py) and NOT faster -- the training step measured 1340 - 1343
   // images/s with the family against 1345 - 1347 without, every forced shape lower still (profiles/r05_bf16_wide_ab.txt): those
@@ -1976,61 +2018,32 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
   if (kHalf) wide_ok = wide_ok && !g.in_scale && g.Cin % 64 == 0 && dspn::wide_tiles_mode() >= 2;
   else wide_ok = wide_ok && pre && g.bf16 == 3;       // (pre: whole 32-channel blocks, the weights as piece planes)
   // (whole channel blocks per tap there: nk is the family's k-step count)
-  const dspn::conv::WideRoute route = wide_ok ? dspn::conv::wide_route(g, M, nk) : dspn::conv::WideRoute{};
-  if (g.sadd) {
-    // The strided addend (ConvGeom::sadd) exists in the direct epilogue of the plane-fed 128-row members on the tile-spanning
-    // loop, with BatchNorm-backward sums: the calls the conv1 data gradients of the projection units are.  Everything else is
-    // refused HERE, by name -- there is no second implementation to fall back to; the caller keeps the accumulate path.
-    constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd);
-    if (kHalf) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend takes float tensors only", who);
-    if (g.bf16 != 3) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs DSPN_MATH_F32_F16X2", who);
-    if (splits > 1) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend cannot be combined with split-K (%d splits)", who, splits);
-    if (!g.bn_sums) return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs the BatchNorm-backward sums (bn_sums)", who);
-    if (!g.dense || g.ldc != g.Cout || (g.flags & (1 | 2 | 4 | 8)) || residual)
-      return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend needs a dense dx written by this call alone (no accumulate)", who);
-    // (W % 4 == 0, W >= 8: a group of four rows of the epilogue lies inside one image row and starts at an even column)
-    if (g.sadd_h != (g.Hg + 1) / 2 || g.sadd_w != (g.Wg + 1) / 2 || g.Wg < 8 || g.Wg % 4 != 0)
-      return dspn::fail(DSPN_ERR_ARG_, "%s: the strided addend is (N, ceil(H / 2), ceil(W / 2), Cin) with W >= 8 and W %% 4 == 0, got %d x %d for %d x %d", who,
-                        g.sadd_h, g.sadd_w, g.Hg, g.Wg);
-    if (!((route.tile == dspn::conv::WideTile::P128x128 || route.tile == dspn::conv::WideTile::P128x256) &&
-          route.loop == dspn::conv::WideLoop::Spanning))
-      return dspn::fail(DSPN_ERR_ARG_, "%s: no kernel takes the strided addend on this route (it needs dy as piece planes, N H W %% 128 == 0 "
-                        "and the plane-fed 128-row tiles on the tile-spanning loop)", who);
-    g.sadd_bytes = (unsigned)((long long)sizeof(st_t) * g.N * g.sadd_h * g.sadd_w * g.Cout);      // (a quarter of dx, which the route bounds below 2 GiB)
-    if (g.probe) return 0;
-  }
-  if (g.bn_recompute) {
-    // The data gradient whose output is never stored (ConvGeom::bn_recompute: the sums pass, the apply pass) exists where the
-    // strided addend does -- the direct epilogue of the plane-fed 128-row members on the tile-spanning loop -- and nowhere
-    // else: refused HERE, by name; the caller keeps the data gradient + BatchNorm backward pair.
-    const char *who = g.bn_recompute == 1 ? DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums) : DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply);
-    if (kHalf) return dspn::fail(DSPN_ERR_ARG_, "%s: float tensors only", who);
-    if (g.bf16 != 3) return dspn::fail(DSPN_ERR_ARG_, "%s: needs DSPN_MATH_F32_F16X2", who);
-    // (the sums pass carries tables and the apply pass no split workspace: neither is ever split -- a shape that a plain data
-    // gradient splits over K is named as such)
-    if (splits > 1 || (g.dense && nblk < 192 && nk >= 16))
-      return dspn::fail(DSPN_ERR_ARG_, "%s: cannot be combined with split-K (%lld workgroups, %d k-steps: a shape that is split)", who, nblk, nk);
-    if (!g.a_planes) return dspn::fail(DSPN_ERR_ARG_, "%s: needs dy as piece planes (DSPN_MATH_DY_PLANES)", who);
-    if (g.sadd || g.stats || g.in_scale || residual || (g.flags & (1 | 2 | 8)))
-      return dspn::fail(DSPN_ERR_ARG_, "%s: a plain data gradient only (no strided addend, statistics, input affine, bias, ReLU or residual)", who);
-    if (!g.dense || g.ldc != g.Cout) return dspn::fail(DSPN_ERR_ARG_, "%s: needs a dense dx (dx_ldc %d, Cin %d)", who, g.ldc, g.Cout);
-    if (g.TR * g.TS != 1 || g.ish != 1 || g.isw != 1 || g.ioh != 0 || g.iow != 0)
-      return dspn::fail(DSPN_ERR_ARG_, "%s: a 1 x 1 / stride-1 / pad-0 convolution only", who);
-    if ((g.bn_recompute == 1) != (g.bn_sums != nullptr) || (g.bn_recompute == 1 && (g.flags & 4)))
-      return dspn::fail(DSPN_ERR_ARG_, "%s: the sums pass writes the tables and adds to nothing; the apply pass reads the coefficients", who);
-    if (!((route.tile == dspn::conv::WideTile::P128x128 || route.tile == dspn::conv::WideTile::P128x256) &&
-          route.loop == dspn::conv::WideLoop::Spanning))
-      return dspn::fail(DSPN_ERR_ARG_, "%s: no kernel on this route (it needs N H W %% 128 == 0 and the plane-fed 128-row tiles on the "
-                        "tile-spanning loop)", who);
-    if (g.probe) return 0;
-  }
-  if (route) return dspn::conv::launch_wide(route, in, w, bias, out, g, s, residual);
-  const int rc = cfg == 0 && eight ? launch_nt<4, 2, 1, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
-                 : cfg == 0        ? launch_nt<2, 2, 2, 2>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
-                 : cfg == 1        ? launch_nt<2, 2, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
-                 : cfg == 2        ? launch_nt<2, 2, 1, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual)
-                                   : launch_nt<4, 1, 2, 1>(in, w, bias, out, g, s, splits, per, ws.ptr, residual);
+  if (wide_ok) p.route = dspn::conv::wide_route(g, M, p.nk);
+  if (g.bn_recompute || g.sadd)
+    if (const int rc = variant_route_refusal(g.bn_recompute ? DgradVariant(g.bn_recompute) : DgradVariant::StoreAddend, g, p)) return rc;
+  if (g.sadd) g.sadd_bytes = (unsigned)((long long)sizeof(st_t) * g.N * g.sadd_h * g.sadd_w * g.Cout);      // (a quarter of dx, which the route bounds below 2 GiB)
+  return 0;
+}
+// the launch plan_nt decided on, for the geometry it completed
+int launch_nt_plan(const NtPlan &p, const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g, hipStream_t s,
+                   SplitWs ws, const st_t *residual) {
+  if (p.empty) return output_absmax_pass(out, g, s);
+  if (p.w_planes) w = static_cast<const st_t *>(g.w_planes);
+  if (p.route) return dspn::conv::launch_wide(p.route, in, w, bias, out, g, s, residual);
+  const int rc = p.cfg == 0 && p.eight ? launch_nt<4, 2, 1, 2>(in, w, bias, out, g, s, p.splits, p.per, ws.ptr, residual)
+                 : p.cfg == 0          ? launch_nt<2, 2, 2, 2>(in, w, bias, out, g, s, p.splits, p.per, ws.ptr, residual)
+                 : p.cfg == 1          ? launch_nt<2, 2, 2, 1>(in, w, bias, out, g, s, p.splits, p.per, ws.ptr, residual)
+                 : p.cfg == 2          ? launch_nt<2, 2, 1, 1>(in, w, bias, out, g, s, p.splits, p.per, ws.ptr, residual)
+                                       : launch_nt<4, 1, 2, 1>(in, w, bias, out, g, s, p.splits, p.per, ws.ptr, residual);
   return rc ? rc : output_absmax_pass(out, g, s);
+}
+// one convolution launch: the decision, then the launch
+int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, const ConvGeom &g_in,
+                hipStream_t s, SplitWs ws, const st_t *residual = nullptr) {
+  ConvGeom g = g_in;
+  NtPlan p;
+  if (const int rc = plan_nt(g, out, residual, ws, p)) return rc;
+  return launch_nt_plan(p, in, w, bias, out, g, s, ws, residual);
 }
 
 struct WgradPlan { int bm; int bn; int splits; int pps; };
@@ -2395,13 +2408,6 @@ int dspn_conv2d_weight_prepare_batch_bf16(const void *table, int n, long long to
 
 // dx (N,H,W,Cin_x) from dy (N,Ho,Wo,ldy) and wt = transposed weights [Cin_x][R*S][ldy].
 // Also the forward of a transposed convolution (x := dy).
-struct BnBwd { const st_t *x; const float *scale, *shift, *mean, *rstd; int relu; float *sums; float *dy_absmax; };
-// the strided addend of a dense data gradient (ConvGeom::sadd); probe: ask dispatch_nt for its verdict only
-struct StridedAddend { const st_t *p; int h, w, probe; };
-// the passes of a data gradient that is never stored (ConvGeom::bn_recompute): mode 1 sums, 2 apply (coef: the finalize's
-// 3 Cin floats; dx_absmax: the optional magnitude block of the dx it stores); probe as above
-struct BnRecompute { int mode; const float *coef; float *dx_absmax; int probe; };
-
 // row tiles of the launches of one data gradient, in launch order (stride 2: up to 4 parity classes)
 static int dgrad_tiles(int N, int H, int W, int Cin, int stride, int *per_class /* [4] or NULL */) {
   int total = 0;
@@ -2415,67 +2421,6 @@ static int dgrad_tiles(int N, int H, int W, int Cin, int stride, int *per_class 
     }
   return total;
 }
-
-static int conv2d_dgrad_one(int math, OpScales scales, const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
-                          int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                          int Wo, int dx_ldc, int accumulate, BnBwd bn, void *workspace, size_t workspace_bytes,
-                          void *stream, StridedAddend sa = StridedAddend{nullptr, 0, 0, 0}, BnRecompute rc2 = BnRecompute{0, nullptr, nullptr, 0}) {
-  DSPN_REQUIRE(dy && (wt || wt_planes) && (dx || rc2.mode == 1), "conv2d_dgrad: null pointer");
-  DSPN_REQUIRE(ldy % kEPC == 0, "conv2d_dgrad: dy channel stride must be a multiple of %d", kEPC);
-  DSPN_REQUIRE(stride == 1 || (stride == 2 && dil == 1), "conv2d_dgrad: stride 1, or stride 2 with dilation 1");
-  DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && R > 0 && S > 0, "conv2d_dgrad: bad geometry");
-  ConvGeom g;
-  memset(&g, 0, sizeof(g));
-  g.N = N; g.Hin = Ho; g.Win = Wo; g.Cin = ldy; g.Cout = Cin;
-  g.WTAPS = R * S; g.WS = S;
-  g.ldc = dx_ldc > 0 ? dx_ldc : Cin;
-  g.obs = (long long)H * W * g.ldc;
-  g.OW = W;
-  g.flags = accumulate ? 4 : 0;
-  g.bf16 = kHalf ? 1 : math;
-  g.w_planes = wt_planes;
-  g.a_absmax = scales.a; g.b_absmax = scales.b;
-  g.bn_x = bn.x; g.bn_scale = bn.scale; g.bn_shift = bn.shift; g.bn_mean = bn.mean; g.bn_rstd = bn.rstd;
-  g.bn_relu = bn.relu; g.bn_sums = bn.sums; g.bn_tile_base = 0;
-  g.bn_dy_absmax = (bn.sums && !kHalf && math == DSPN_MATH_F32_F16X2) ? reinterpret_cast<unsigned *>(bn.dy_absmax) : nullptr;
-  g.a_planes = scales.a_planes;
-  g.sadd = sa.p; g.sadd_h = sa.h; g.sadd_w = sa.w; g.probe = sa.probe | rc2.probe;
-  g.bn_recompute = rc2.mode; g.bn_coef = rc2.coef;
-  if (rc2.mode == 2) g.bn_dy_absmax = reinterpret_cast<unsigned *>(rc2.dx_absmax);
-  if (rc2.mode == 1) g.bn_dy_absmax = nullptr;
-  int class_tiles[4] = {0, 0, 0, 0};
-  if (bn.sums) dgrad_tiles(N, H, W, Cin, stride, class_tiles);
-  hipStream_t s = (hipStream_t)stream;
-  const SplitWs sws{static_cast<float *>(workspace), workspace ? workspace_bytes : 0};
-  if (stride == 1) {
-    g.Hg = H; g.Wg = W; g.ish = 1; g.isw = 1; g.ioh = pad_h; g.iow = pad_w; g.idh = -dil; g.idw = -dil;
-    g.TR = R; g.TS = S; g.wr0 = 0; g.wrs = 1; g.ws0 = 0; g.wss = 1;
-    g.osh = 1; g.osw = 1; g.dense = 1;
-    return dispatch_nt(dy, wt, nullptr, dx, g, s, sws);
-  }
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      ConvGeom c = g;
-      c.Hg = (H - ph + 1) / 2; c.Wg = (W - pw + 1) / 2;
-      for (int q = 0; q < ph * 2 + pw; ++q) c.bn_tile_base += class_tiles[q];
-      if (c.Hg <= 0 || c.Wg <= 0) continue;
-      const int r0 = (ph + pad_h) & 1, s0 = (pw + pad_w) & 1;
-      c.TR = r0 < R ? (R - r0 + 1) / 2 : 0;
-      c.TS = s0 < S ? (S - s0 + 1) / 2 : 0;
-      if (c.TR == 0 || c.TS == 0) {
-        c.TR = 0; c.TS = 1;
-        if (accumulate && !bn.sums) continue;   // nothing to add (with BatchNorm sums the class still has to be read)
-      }
-      c.ish = 1; c.isw = 1; c.ioh = (ph + pad_h - r0) / 2; c.iow = (pw + pad_w - s0) / 2;
-      c.idh = -1; c.idw = -1;
-      c.wr0 = r0; c.wrs = 2; c.ws0 = s0; c.wss = 2;
-      c.osh = 2; c.osw = 2; c.ooh = ph; c.oow = pw; c.dense = 0;
-      const int rc = dispatch_nt(dy, wt, nullptr, dx, c, s, sws);
-      if (rc) return rc;
-    }
-  return 0;
-}
-
 static int dgrad_bn_tiles(int N, int H, int W, int Cin, int stride) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 4 != 0 || (stride != 1 && stride != 2)) return 0;
   return dgrad_tiles(N, H, W, Cin, stride, nullptr);
@@ -2483,149 +2428,214 @@ static int dgrad_bn_tiles(int N, int H, int W, int Cin, int stride) {
 #ifndef DSPN_HALF
 int dspn_conv2d_dgrad_bn_tiles(int N, int H, int W, int Cin, int stride) { return dgrad_bn_tiles(N, H, W, Cin, stride); }
 #endif
-
 }  // extern "C"
-static int conv2d_dgrad_bn_impl(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
-                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                             int Wo, int dx_ldc, int accumulate,
-                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
-                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
-                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
-                             void *stream, StridedAddend sa, BnRecompute rc2 = BnRecompute{0, nullptr, nullptr, 0}) {
-  DSPN_REQUIRE(N > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_dgrad: bad geometry");
-  if (rc2.mode) {      // (what the arguments alone decide; the route is dispatch_nt's)
-    const char *who = rc2.mode == 1 ? DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums) : DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply);
+
+// One call of a dspn_conv2d_dgrad_bn* entry, filled there by field name (the fields the entries share: DSPN_DGRAD_*_FIELDS)
+struct DgradCall {
+  DgradVariant variant;
+  const st_t *dy, *wt; const void *wt_planes; st_t *dx;
+  int N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate;
+  const st_t *bn_x; const float *bn_scale, *bn_shift, *bn_mean, *bn_rstd; int bn_relu;
+  float *bn_sums; size_t bn_sums_bytes; float *bn_dy_absmax;
+  int math;                                     // the entry's argument; dgrad_check leaves the mode (split_math) here ...
+  const float *dy_absmax, *w_absmax;
+  void *workspace; size_t workspace_bytes; void *stream;
+  const st_t *addend; int addend_h, addend_w;   // StoreAddend: ConvGeom::sadd
+  const float *coef; float *dx_absmax;          // Apply: the finalize's 3 Cin coefficients; the optional magnitude block of dx as stored
+  int dy_planes;                                // ... and DSPN_MATH_DY_PLANES here
+  SplitWs split_ws() const { return SplitWs{static_cast<float *>(workspace), workspace ? workspace_bytes : 0}; }
+  int chunk() const { return batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy); }      // images per launch: dy below 2 GiB
+};
+// What the ARGUMENTS alone decide about the variants, each rule once (what the route decides: variant_route_refusal)
+static int dgrad_variant_args(const DgradCall &c) {
+  if (c.variant == DgradVariant::Store) return 0;
+  const char *who = variant_entry[(int)c.variant];
+  const bool sadd = c.variant == DgradVariant::StoreAddend;
+  if (sadd)
+    DSPN_REQUIRE(c.stride == 1 && !c.accumulate, "%s: the strided addend goes with a stride-1 data gradient that is the only writer of dx (no accumulate)", who);
+  else {
     DSPN_REQUIRE(!dspn::kHalf, "%s: float tensors only (the bfloat16 build has no such kernel)", who);
-    DSPN_REQUIRE(R == 1 && S == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && Ho == H && Wo == W,
+    DSPN_REQUIRE(c.R == 1 && c.S == 1 && c.stride == 1 && c.pad_h == 0 && c.pad_w == 0 && c.Ho == c.H && c.Wo == c.W,
                  "%s: a 1 x 1 / stride-1 / pad-0 convolution only", who);
-    DSPN_REQUIRE((dx_ldc <= 0 || dx_ldc == Cin), "%s: needs a dense dx (dx_ldc %d, Cin %d)", who, dx_ldc, Cin);
-    DSPN_REQUIRE(Cin > 0 && Cin % 4 == 0, "%s: Cin %% 4 == 0", who);
-    DSPN_REQUIRE(batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy) == N, "%s: dy of 2 GiB or more", who);
   }
-  if (sa.p) {      // (what the arguments alone decide; the route is dispatch_nt's)
-    constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd);
-    DSPN_REQUIRE(stride == 1 && !accumulate, "%s: the strided addend goes with a stride-1 data gradient that is the only writer of dx (no accumulate)", who);
-    DSPN_REQUIRE((dx_ldc <= 0 || dx_ldc == Cin), "%s: the strided addend needs a dense dx (dx_ldc %d, Cin %d)", who, dx_ldc, Cin);
-    DSPN_REQUIRE(batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy) == N, "%s: dy of 2 GiB or more", who);
-  }
-  const int flags = split_math(&math, DSPN_MATH_DY_PLANES), dy_planes = (flags & DSPN_MATH_DY_PLANES) ? 1 : 0;
-  DSPN_REQUIRE(!dy_planes || (!dspn::kHalf && math == DSPN_MATH_F32_F16X2 && ldy % 32 == 0 && dy_absmax),
-               "conv2d_dgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy %% 32 == 0 and the block the planes were cut by (dy_absmax)");
-  if (const int rc = check_math_mode("conv2d_dgrad", math)) return rc;
-  if (const int rc = check_math_blocks("conv2d_dgrad", math, flags, dy_absmax, w_absmax)) return rc;
-  const int ldc = dx_ldc > 0 ? dx_ldc : Cin;
-  const int nb = batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy);
-  if (bn_sums) {
-    DSPN_REQUIRE(bn_x && bn_mean && bn_rstd && (!bn_relu || (bn_scale && bn_shift)), "conv2d_dgrad: BatchNorm operands missing");
-    DSPN_REQUIRE(ldc == Cin && nb == N, "conv2d_dgrad: BatchNorm sums need a dense dx and dy below 2 GiB");
-    const int tiles = dgrad_bn_tiles(N, H, W, Cin, stride);
-    DSPN_REQUIRE(tiles > 0 && bn_sums_bytes >= sizeof(float) * 2 * (size_t)tiles * Cin,
-                 "conv2d_dgrad: bn_sums needs dspn_conv2d_dgrad_bn_tiles() x 2 x Cin floats");
-  }
-  for (int n0 = 0; n0 < N; n0 += nb) {
-    const int n = std::min(nb, N - n0);
-    const int rc = conv2d_dgrad_one(math, OpScales{dy_absmax, w_absmax, dy_planes}, dy + (long long)n0 * Ho * Wo * ldy, wt, wt_planes, dx + (long long)n0 * H * W * ldc, n, H,
-                                    W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
-                                    BnBwd{bn_x, bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_dy_absmax}, workspace,
-                                    workspace_bytes, stream, sa, rc2);
-    if (rc) return rc;
-  }
+  DSPN_REQUIRE((c.dx_ldc <= 0 || c.dx_ldc == c.Cin), sadd ? "%s: the strided addend needs a dense dx (dx_ldc %d, Cin %d)" : "%s: needs a dense dx (dx_ldc %d, Cin %d)",
+               who, c.dx_ldc, c.Cin);
+  DSPN_REQUIRE(sadd || (c.Cin > 0 && c.Cin % 4 == 0), "%s: Cin %% 4 == 0", who);
+  DSPN_REQUIRE(c.chunk() == c.N, "%s: dy of 2 GiB or more", who);
   return 0;
 }
+// every check of a data gradient that precedes its launches' own; decodes c.math
+static int dgrad_check(DgradCall &c) {
+  DSPN_REQUIRE(c.N > 0 && c.Ho > 0 && c.Wo > 0 && c.ldy > 0, "conv2d_dgrad: bad geometry");
+  if (const int rc = dgrad_variant_args(c)) return rc;
+  const int flags = split_math(&c.math, DSPN_MATH_DY_PLANES);
+  c.dy_planes = (flags & DSPN_MATH_DY_PLANES) ? 1 : 0;
+  DSPN_REQUIRE(!c.dy_planes || (!dspn::kHalf && c.math == DSPN_MATH_F32_F16X2 && c.ldy % 32 == 0 && c.dy_absmax),
+               "conv2d_dgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy %% 32 == 0 and the block the planes were cut by (dy_absmax)");
+  if (const int rc = check_math_mode("conv2d_dgrad", c.math)) return rc;
+  if (const int rc = check_math_blocks("conv2d_dgrad", c.math, flags, c.dy_absmax, c.w_absmax)) return rc;
+  if (c.bn_sums) {
+    DSPN_REQUIRE(c.bn_x && c.bn_mean && c.bn_rstd && (!c.bn_relu || (c.bn_scale && c.bn_shift)), "conv2d_dgrad: BatchNorm operands missing");
+    DSPN_REQUIRE((c.dx_ldc <= 0 || c.dx_ldc == c.Cin) && c.chunk() == c.N, "conv2d_dgrad: BatchNorm sums need a dense dx and dy below 2 GiB");
+    const int tiles = dgrad_bn_tiles(c.N, c.H, c.W, c.Cin, c.stride);
+    DSPN_REQUIRE(tiles > 0 && c.bn_sums_bytes >= sizeof(float) * 2 * (size_t)tiles * c.Cin,
+                 "conv2d_dgrad: bn_sums needs dspn_conv2d_dgrad_bn_tiles() x 2 x Cin floats");
+  }
+  DSPN_REQUIRE(c.dy && (c.wt || c.wt_planes) && (c.dx || c.variant == DgradVariant::SumsOnly), "conv2d_dgrad: null pointer");
+  DSPN_REQUIRE(c.ldy % kEPC == 0, "conv2d_dgrad: dy channel stride must be a multiple of %d", kEPC);
+  DSPN_REQUIRE(c.stride == 1 || (c.stride == 2 && c.dil == 1), "conv2d_dgrad: stride 1, or stride 2 with dilation 1");
+  DSPN_REQUIRE(c.N > 0 && c.H > 0 && c.W > 0 && c.Cin > 0 && c.R > 0 && c.S > 0, "conv2d_dgrad: bad geometry");
+  return 0;
+}
+// The geometry of the launches of n images of a checked call -- THE place a DgradCall becomes a ConvGeom: complete for
+// stride 1; for stride 2 what the four parity classes share (conv2d_dgrad_one adds each class's grid, taps and tile base)
+static ConvGeom dgrad_geom(const DgradCall &c, int n) {
+  ConvGeom g;
+  memset(&g, 0, sizeof(g));
+  g.N = n; g.Hin = c.Ho; g.Win = c.Wo; g.Cin = c.ldy; g.Cout = c.Cin;
+  g.WTAPS = c.R * c.S; g.WS = c.S;
+  g.ldc = c.dx_ldc > 0 ? c.dx_ldc : c.Cin;
+  g.obs = (long long)c.H * c.W * g.ldc; g.OW = c.W; g.flags = c.accumulate ? 4 : 0;
+  g.bf16 = kHalf ? 1 : c.math; g.w_planes = c.wt_planes; g.a_planes = c.dy_planes; g.a_absmax = c.dy_absmax; g.b_absmax = c.w_absmax;
+  g.bn_x = c.bn_x; g.bn_scale = c.bn_scale; g.bn_shift = c.bn_shift; g.bn_mean = c.bn_mean; g.bn_rstd = c.bn_rstd;
+  g.bn_relu = c.bn_relu; g.bn_sums = c.bn_sums;
+  // the partial maxima of |dx| as stored: the apply pass wherever it is given the block, a storing call with its sums in the
+  // two-piece math, the sums pass never
+  g.bn_dy_absmax = reinterpret_cast<unsigned *>(c.variant == DgradVariant::Apply ? c.dx_absmax
+                                                : c.variant != DgradVariant::SumsOnly && c.bn_sums && !kHalf && c.math == DSPN_MATH_F32_F16X2
+                                                    ? c.bn_dy_absmax : nullptr);
+  g.sadd = c.addend; g.sadd_h = c.addend_h; g.sadd_w = c.addend_w;
+  g.bn_recompute = c.variant == DgradVariant::StoreAddend ? 0 : (int)c.variant; g.bn_coef = c.coef;
+  if (c.stride == 1) {
+    g.Hg = c.H; g.Wg = c.W; g.ish = 1; g.isw = 1; g.ioh = c.pad_h; g.iow = c.pad_w; g.idh = -c.dil; g.idw = -c.dil;
+    g.TR = c.R; g.TS = c.S; g.wr0 = 0; g.wrs = 1; g.ws0 = 0; g.wss = 1;
+    g.osh = 1; g.osw = 1; g.dense = 1;
+  }
+  return g;
+}
+// the launches of images [n0, n0 + n) of a checked call
+static int conv2d_dgrad_one(const DgradCall &c, int n0, int n) {
+  const st_t *dy = c.dy + (long long)n0 * c.Ho * c.Wo * c.ldy;
+  const ConvGeom g = dgrad_geom(c, n);
+  st_t *dx = c.dx + (long long)n0 * c.H * c.W * g.ldc;
+  if (c.stride == 1) return dispatch_nt(dy, c.wt, nullptr, dx, g, (hipStream_t)c.stream, c.split_ws());
+  int class_tiles[4] = {0, 0, 0, 0};
+  if (c.bn_sums) dgrad_tiles(n, c.H, c.W, c.Cin, c.stride, class_tiles);
+  for (int ph = 0; ph < 2; ++ph)
+    for (int pw = 0; pw < 2; ++pw) {
+      ConvGeom k = g;
+      k.Hg = (c.H - ph + 1) / 2; k.Wg = (c.W - pw + 1) / 2;
+      for (int q = 0; q < ph * 2 + pw; ++q) k.bn_tile_base += class_tiles[q];
+      if (k.Hg <= 0 || k.Wg <= 0) continue;
+      const int r0 = (ph + c.pad_h) & 1, s0 = (pw + c.pad_w) & 1;
+      k.TR = r0 < c.R ? (c.R - r0 + 1) / 2 : 0;
+      k.TS = s0 < c.S ? (c.S - s0 + 1) / 2 : 0;
+      if (k.TR == 0 || k.TS == 0) {
+        k.TR = 0; k.TS = 1;
+        if (c.accumulate && !c.bn_sums) continue;   // nothing to add (with BatchNorm sums the class still has to be read)
+      }
+      k.ish = 1; k.isw = 1; k.ioh = (ph + c.pad_h - r0) / 2; k.iow = (pw + c.pad_w - s0) / 2;
+      k.idh = -1; k.idw = -1;
+      k.wr0 = r0; k.wrs = 2; k.ws0 = s0; k.wss = 2;
+      k.osh = 2; k.osw = 2; k.ooh = ph; k.oow = pw; k.dense = 0;
+      if (const int rc = dispatch_nt(dy, c.wt, nullptr, dx, k, (hipStream_t)c.stream, c.split_ws())) return rc;
+    }
+  return 0;
+}
+// a storing call or the sums pass: the checks, then the launches in chunks of the batch that keep dy below 2 GiB
+static int conv2d_dgrad_bn_impl(DgradCall c) {
+  if (const int rc = dgrad_check(c)) return rc;
+  for (int n0 = 0, nb = c.chunk(); n0 < c.N; n0 += nb)
+    if (const int rc = conv2d_dgrad_one(c, n0, std::min(nb, c.N - n0))) return rc;
+  return 0;
+}
+// The decision for a call of a variant and nothing else: the checks, its one geometry (the rules of dgrad_variant_args leave
+// every variant stride 1 and one chunk) and plan_nt -- what the route queries ask, and what the apply pass launches from
+static int dgrad_variant_plan(DgradCall c, ConvGeom &g, NtPlan &p) {
+  if (const int rc = dgrad_check(c)) return rc;
+  g = dgrad_geom(c, c.N);
+  return plan_nt(g, c.dx, nullptr, c.split_ws(), p);
+}
+// what the four entries share (include/dspn_nn.h): operands and geometry ...
+#define DSPN_DGRAD_HEAD_PARAMS                                                                                                   \
+  const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W, int Cin, int ldy, int R, int S, int stride, \
+      int pad_h, int pad_w, int dil, int Ho, int Wo, int dx_ldc, int accumulate
+#define DSPN_DGRAD_HEAD_FIELDS                                                                                                   \
+  .dy = dy, .wt = wt, .wt_planes = wt_planes, .dx = dx, .N = N, .H = H, .W = W, .Cin = Cin, .ldy = ldy, .R = R, .S = S,         \
+  .stride = stride, .pad_h = pad_h, .pad_w = pad_w, .dil = dil, .Ho = Ho, .Wo = Wo, .dx_ldc = dx_ldc, .accumulate = accumulate
+// ... and the three that write or only form the sums tables: BatchNorm operands, math word and magnitude blocks, split workspace
+#define DSPN_DGRAD_BN_PARAMS                                                                                                     \
+  DSPN_DGRAD_HEAD_PARAMS, const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,                  \
+      const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax, int math,                    \
+      const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes
+#define DSPN_DGRAD_BN_FIELDS                                                                                                     \
+  DSPN_DGRAD_HEAD_FIELDS, .bn_x = bn_x, .bn_scale = bn_scale, .bn_shift = bn_shift, .bn_mean = bn_mean, .bn_rstd = bn_rstd,      \
+  .bn_relu = bn_relu, .bn_sums = bn_sums, .bn_sums_bytes = bn_sums_bytes, .bn_dy_absmax = bn_dy_absmax, .math = math,            \
+  .dy_absmax = dy_absmax, .w_absmax = w_absmax, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream
 extern "C" {
+int DSPN_FN(dspn_conv2d_dgrad_bn)(DSPN_DGRAD_BN_PARAMS, void *stream) {
+  return conv2d_dgrad_bn_impl(DgradCall{.variant = DgradVariant::Store, DSPN_DGRAD_BN_FIELDS});
+}
+// ... with the strided addend (include/dspn_nn.h): dx = conv + (h, w both even ? addend[n, h / 2, w / 2, :] : +0.0f)
+int DSPN_FN(dspn_conv2d_dgrad_bn_sadd)(DSPN_DGRAD_BN_PARAMS, const st_t *strided_addend, int addend_h, int addend_w, void *stream) {
+  DSPN_REQUIRE(strided_addend && addend_h > 0 && addend_w > 0, "%s: no strided addend (dspn_conv2d_dgrad_bn is the call without one)",
+               DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd));
+  return conv2d_dgrad_bn_impl(DgradCall{.variant = DgradVariant::StoreAddend, DSPN_DGRAD_BN_FIELDS, .addend = strided_addend,
+                                        .addend_h = addend_h, .addend_w = addend_w});
+}
 // The data gradient of a BatchNorm(+ReLU) output that is never stored (include/dspn_nn.h): the sums pass ...
-int DSPN_FN(dspn_conv2d_dgrad_bn_sums)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
-                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                             int Wo, int dx_ldc, int accumulate,
-                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
-                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
-                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
-                             void *stream) {
+int DSPN_FN(dspn_conv2d_dgrad_bn_sums)(DSPN_DGRAD_BN_PARAMS, void *stream) {
   constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sums);
   DSPN_REQUIRE(!dx && !accumulate && !bn_dy_absmax, "%s: stores no dx (dx == NULL, accumulate 0, no bn_dy_absmax); dspn_conv2d_dgrad_bn is the call that does", who);
   DSPN_REQUIRE(bn_sums, "%s: bn_sums missing", who);
-  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, nullptr, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, 0, bn_x,
-                              bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_sums_bytes, nullptr, math, dy_absmax,
-                              w_absmax, workspace, workspace_bytes, stream, StridedAddend{nullptr, 0, 0, 0}, BnRecompute{1, nullptr, nullptr, 0});
+  return conv2d_dgrad_bn_impl(DgradCall{.variant = DgradVariant::SumsOnly, DSPN_DGRAD_BN_FIELDS});
 }
 // ... and the apply pass, in the place of the DSPN_BN_SUMS_APPLY_ONLY call of dspn_bn_backward_from_sums
-int DSPN_FN(dspn_conv2d_dgrad_bn_apply)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
-                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                             int Wo, int dx_ldc, int accumulate,
-                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, int bn_relu, float *dx_absmax,
-                             int math, const float *dy_absmax, const float *w_absmax, const void *bn_workspace,
-                             size_t bn_workspace_bytes, void *stream) {
+int DSPN_FN(dspn_conv2d_dgrad_bn_apply)(DSPN_DGRAD_HEAD_PARAMS, const st_t *bn_x, const float *bn_scale, const float *bn_shift, int bn_relu,
+                                        float *dx_absmax, int math, const float *dy_absmax, const float *w_absmax,
+                                        const void *bn_workspace, size_t bn_workspace_bytes, void *stream) {
   constexpr const char *who = DSPN_FN_NAME(dspn_conv2d_dgrad_bn_apply);
   DSPN_REQUIRE(dx && bn_x && bn_workspace && (!bn_relu || (bn_scale && bn_shift)), "%s: null pointer", who);
   if (Cin > 0 && bn_workspace_bytes < sizeof(float) * 3 * (size_t)Cin)
     return dspn::fail(DSPN_ERR_WORKSPACE_, "%s: the BatchNorm workspace holds 3 * Cin coefficients", who);
-  // (the probe of the route query launches nothing: it leaves a parked finalize where it is)
-  const int rc = conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
-                                      bn_x, bn_scale, bn_shift, nullptr, nullptr, bn_relu, nullptr, 0, nullptr, math, dy_absmax, w_absmax,
-                                      nullptr, 0, stream, StridedAddend{nullptr, 0, 0, 0},
-                                      BnRecompute{2, static_cast<const float *>(bn_workspace), dx_absmax, 1});
-  if (rc) return rc;
+  const DgradCall c{.variant = DgradVariant::Apply, DSPN_DGRAD_HEAD_FIELDS, .bn_x = bn_x, .bn_scale = bn_scale, .bn_shift = bn_shift,
+                    .bn_relu = bn_relu, .math = math, .dy_absmax = dy_absmax, .w_absmax = w_absmax, .stream = stream,
+                    .coef = static_cast<const float *>(bn_workspace), .dx_absmax = dx_absmax};
+  ConvGeom g;
+  NtPlan p;
+  if (const int rc = dgrad_variant_plan(c, g, p)) return rc;      // (a refused call launches nothing: a parked finalize stays parked)
   dspn::bn_jobs_run((hipStream_t)stream);      // a finalize of this stream that no weight gradient took: now, as the apply half does
-  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate,
-                              bn_x, bn_scale, bn_shift, nullptr, nullptr, bn_relu, nullptr, 0, nullptr, math, dy_absmax, w_absmax,
-                              nullptr, 0, stream, StridedAddend{nullptr, 0, 0, 0},
-                              BnRecompute{2, static_cast<const float *>(bn_workspace), dx_absmax, 0});
+  return launch_nt_plan(p, dy, wt, nullptr, dx, g, (hipStream_t)stream, SplitWs{nullptr, 0}, nullptr);
 }
-int DSPN_FN(dspn_conv2d_dgrad_bn)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
-                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                             int Wo, int dx_ldc, int accumulate,
-                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
-                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
-                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
-                             void *stream) {
-  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate, bn_x,
-                              bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_sums_bytes, bn_dy_absmax, math, dy_absmax,
-                              w_absmax, workspace, workspace_bytes, stream, StridedAddend{nullptr, 0, 0, 0});
-}
-// ... with the strided addend (include/dspn_nn.h): dx = conv + (h, w both even ? addend[n, h / 2, w / 2, :] : +0.0f)
-int DSPN_FN(dspn_conv2d_dgrad_bn_sadd)(const st_t *dy, const st_t *wt, const void *wt_planes, st_t *dx, int N, int H, int W,
-                             int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                             int Wo, int dx_ldc, int accumulate,
-                             const st_t *bn_x, const float *bn_scale, const float *bn_shift, const float *bn_mean,
-                             const float *bn_rstd, int bn_relu, float *bn_sums, size_t bn_sums_bytes, float *bn_dy_absmax,
-                             int math, const float *dy_absmax, const float *w_absmax, void *workspace, size_t workspace_bytes,
-                             const st_t *strided_addend, int addend_h, int addend_w, void *stream) {
-  DSPN_REQUIRE(strided_addend && addend_h > 0 && addend_w > 0, "%s: no strided addend (dspn_conv2d_dgrad_bn is the call without one)",
-               DSPN_FN_NAME(dspn_conv2d_dgrad_bn_sadd));
-  return conv2d_dgrad_bn_impl(dy, wt, wt_planes, dx, N, H, W, Cin, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, dx_ldc, accumulate, bn_x,
-                              bn_scale, bn_shift, bn_mean, bn_rstd, bn_relu, bn_sums, bn_sums_bytes, bn_dy_absmax, math, dy_absmax,
-                              w_absmax, workspace, workspace_bytes, stream, StridedAddend{strided_addend, addend_h, addend_w, 0});
-}
+#undef DSPN_DGRAD_BN_FIELDS
+#undef DSPN_DGRAD_BN_PARAMS
+#undef DSPN_DGRAD_HEAD_FIELDS
+#undef DSPN_DGRAD_HEAD_PARAMS
 #ifndef DSPN_HALF
+// The route queries: whether dgrad_variant_plan takes the 1 x 1 / stride-1 call of that shape in the two-piece math, with BatchNorm
+// sums and ReLU mask.  The pointer q only stands for "given" (16-byte aligned, never dereferenced on the host).
+static int dgrad_query(DgradVariant v, int N, int H, int W, int Cin, int ldy, int dy_planes) {
+  const int tiles = dgrad_bn_tiles(N, H, W, Cin, 1);
+  if (tiles <= 0 || N <= 0 || ldy <= 0) return 0;
+  float *const q = reinterpret_cast<float *>(uintptr_t(256)), *const no = nullptr;
+  const bool sadd = v == DgradVariant::StoreAddend, apply = v == DgradVariant::Apply;      // (apply: the coefficients, no tables)
+  const DgradCall c{
+      .variant = v, .dy = q, .wt_planes = q, .dx = v == DgradVariant::SumsOnly ? no : q, .N = N, .H = H, .W = W, .Cin = Cin, .ldy = ldy,
+      .R = 1, .S = 1, .stride = 1, .dil = 1, .Ho = H, .Wo = W, .dx_ldc = Cin, .accumulate = apply, .bn_x = q, .bn_scale = q, .bn_shift = q,
+      .bn_mean = apply ? no : q, .bn_rstd = apply ? no : q, .bn_relu = 1, .bn_sums = apply ? no : q,
+      .bn_sums_bytes = apply ? 0 : sizeof(float) * 2 * (size_t)tiles * Cin, .bn_dy_absmax = sadd ? q : no,
+      .math = DSPN_MATH_F32_F16X2 | (dy_planes ? DSPN_MATH_DY_PLANES : 0), .dy_absmax = q, .w_absmax = q, .addend = sadd ? q : no,
+      .addend_h = sadd ? (H + 1) / 2 : 0, .addend_w = sadd ? (W + 1) / 2 : 0, .coef = apply ? q : no, .dx_absmax = apply ? q : no};
+  ConvGeom g;
+  NtPlan p;
+  return dgrad_variant_plan(c, g, p) == 0;
+}
 int dspn_conv2d_dgrad_bn_sadd_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes) {
-  // the verdict of dispatch_nt for the 1 x 1 / stride-1 call of that shape in the two-piece math, without a launch: the
-  // pointers only stand for "given" (16-byte aligned, never dereferenced on the host)
-  float *const q = reinterpret_cast<float *>(uintptr_t(256));
-  const int tiles = dgrad_bn_tiles(N, H, W, Cin, 1);
-  if (tiles <= 0 || N <= 0 || ldy <= 0) return 0;
-  return conv2d_dgrad_bn_impl(q, nullptr, q, q, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 0, q, q, q, q, q, 1, q,
-                              sizeof(float) * 2 * (size_t)tiles * Cin, q, DSPN_MATH_F32_F16X2 | (dy_planes ? DSPN_MATH_DY_PLANES : 0), q, q,
-                              nullptr, 0, nullptr, StridedAddend{q, (H + 1) / 2, (W + 1) / 2, 1}) == 0 ? 1 : 0;
+  return dgrad_query(DgradVariant::StoreAddend, N, H, W, Cin, ldy, dy_planes);
 }
-#endif
-
-#ifndef DSPN_HALF
-int dspn_conv2d_dgrad_bn_recompute_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes) {
-  // the verdict of dispatch_nt for BOTH passes of the 1 x 1 / stride-1 call of that shape, without a launch (pointers as above)
-  float *const q = reinterpret_cast<float *>(uintptr_t(256));
-  const int tiles = dgrad_bn_tiles(N, H, W, Cin, 1);
-  if (tiles <= 0 || N <= 0 || ldy <= 0) return 0;
-  const int math = DSPN_MATH_F32_F16X2 | (dy_planes ? DSPN_MATH_DY_PLANES : 0);
-  const StridedAddend none{nullptr, 0, 0, 0};
-  return conv2d_dgrad_bn_impl(q, nullptr, q, nullptr, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 0, q, q, q, q, q, 1, q,
-                              sizeof(float) * 2 * (size_t)tiles * Cin, nullptr, math, q, q, nullptr, 0, nullptr, none,
-                              BnRecompute{1, nullptr, nullptr, 1}) == 0 &&
-         conv2d_dgrad_bn_impl(q, nullptr, q, q, N, H, W, Cin, ldy, 1, 1, 1, 0, 0, 1, H, W, Cin, 1, q, q, q, nullptr, nullptr, 1, nullptr,
-                              0, nullptr, math, q, q, nullptr, 0, nullptr, none, BnRecompute{2, q, q, 1}) == 0 ? 1 : 0;
+int dspn_conv2d_dgrad_bn_recompute_route_f32(int N, int H, int W, int Cin, int ldy, int dy_planes) {      // BOTH passes
+  return dgrad_query(DgradVariant::SumsOnly, N, H, W, Cin, ldy, dy_planes) && dgrad_query(DgradVariant::Apply, N, H, W, Cin, ldy, dy_planes);
 }
-#endif
-
-#ifndef DSPN_HALF
 int dspn_conv2d_dgrad_f32(const float *dy, const float *wt, float *dx, int N, int H, int W,
                           int Cin, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                           int Wo, int dx_ldc, int accumulate, void *workspace, size_t workspace_bytes,

@@ -58,11 +58,11 @@ struct ConvGeomT {
   // (N, sadd_h, sadd_w, Cout) with sadd_h = ceil(Hg / 2), sadd_w = ceil(Wg / 2) -- the data gradient of a 1 x 1 / stride-2
   // convolution of the same input -- added at the even positions: out[n,h,w,:] = conv + (h, w both even ? sadd[n,h/2,w/2,:] : +0.0f),
   // where the accumulate addend would be added.  Only the plane-fed 128-row members on the tile-spanning loop take it
-  // (dispatch_nt refuses every other route).
+  // (plan_nt refuses every other route).
   const st_t *sadd;
   int sadd_h, sadd_w;
   unsigned sadd_bytes;             // its size (buffer bound)
-  int probe;                       // host side only: dispatch_nt returns its verdict without launching (the *_route_f32 queries)
+  int layout_pad_;                 // read by nothing (always 0): keeps the kernel-argument layout; goes with the next change to the kernels
   // The data gradient of a BatchNorm(+ReLU) output that is never stored (dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32 / _apply_f32),
   // on the routes of the strided addend: 1 = the sums pass (bn_sums as ever, out == NULL: no store, no addend, no magnitude
   // block), 2 = the apply pass -- out (+)= a g' + c1 bn_x + c0 with the finalize's coefficients bn_coef = [a | c1 | c0], 3 Cout
@@ -93,7 +93,7 @@ struct WideRoute {
   explicit operator bool() const { return tile != WideTile::None; }
 };
 // the route of one call (M output points, nk k-steps) that is legal for the family -- vector epilogue, at least one tap, no split-K,
-// A a pure copy or a float tensor: dispatch_nt checks; every run-time setting and environment knob of the family is evaluated here, once
+// A a pure copy or a float tensor: plan_nt checks; every run-time setting and environment knob of the family is evaluated here, once
 WideRoute wide_route(const ConvGeomT<float> &g, long long M, int nk);
 WideRoute wide_route(const ConvGeomT<__bf16> &g, long long M, int nk);
 // one launch of the family; bfloat16 tensors (conv_wide_h.hip): whole 64-channel blocks, no input affine

@@ -19,6 +19,9 @@ _ll = _c.c_longlong
 _f = _c.c_float
 _sz = _c.c_size_t
 
+# the dspn_conv2d_dgrad_bn* entries: operands, N .. accumulate | the BatchNorm operands, math and its blocks, the workspace
+_dgrad_head = [_vp] * 4 + [_i] * 15
+_dgrad_bn = _dgrad_head + [_vp] * 5 + [_i, _vp, _sz, _vp] + [_i, _vp, _vp] + [_vp, _sz]
 _lib.register({
     "dspn_conv2d_split_workspace_bytes": (_sz, [_ll, _i]),
     "dspn_conv2d_forward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
@@ -45,15 +48,11 @@ _lib.register({
     "dspn_conv2d_dgrad_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
                                    _sz, _vp]),
     "dspn_conv2d_dgrad_bn_tiles": (_i, [_i, _i, _i, _i, _i]),
-    "dspn_conv2d_dgrad_bn_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                      _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_conv2d_dgrad_bn_sadd_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                           _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp, _i, _i, _vp]),
+    "dspn_conv2d_dgrad_bn_f32": (_i, _dgrad_bn + [_vp]),
+    "dspn_conv2d_dgrad_bn_sadd_f32": (_i, _dgrad_bn + [_vp, _i, _i, _vp]),      # ... the addend and its extent, stream
     "dspn_conv2d_dgrad_bn_sadd_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
-    "dspn_conv2d_dgrad_bn_sums_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                           _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_conv2d_dgrad_bn_apply_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                            _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dspn_conv2d_dgrad_bn_sums_f32": (_i, _dgrad_bn + [_vp]),
+    "dspn_conv2d_dgrad_bn_apply_f32": (_i, _dgrad_head + [_vp, _vp, _vp, _i, _vp] + [_i, _vp, _vp] + [_vp, _sz, _vp]),
     "dspn_conv2d_dgrad_bn_recompute_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
     "dspn_bn_backward_from_sums_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _i, _i, _i,
                                             _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
@@ -586,6 +585,29 @@ def conv2d_dgrad_recompute_route(x_shape, ldy, dy_planes):
     return bool(L().dspn_conv2d_dgrad_bn_recompute_route_f32(N, H, W, C, ldy, int(bool(dy_planes))))
 
 
+def _dgrad_operands(dy, wt, wt_planes, wt_shape, math, dy_absmax, w_absmax, dy_planes, complete):
+    """What conv2d_dgrad and conv2d_dgrad_bn_apply decode alike -> wt's (Cin, R, S, ldy) and args(...): the arguments of their
+    entries up to w_absmax.  complete (conv2d_dgrad): missing blocks and planes are made, planes the call does not read dropped."""
+    Cin, R, S, ldy = wt.shape if wt is not None else wt_shape
+    math = _math_code(math)
+    if not (math == 3 and dy.dtype == torch.float32):
+        dy_absmax = w_absmax = None
+    elif complete:
+        assert wt_planes is None or w_absmax is not None, "f16x2 planes come with the magnitude block they were cut by"
+        assert not dy_planes or dy_absmax is not None, "piece-plane gradients come with the magnitude block they were cut by"
+        dy_absmax = absmax(dy) if dy_absmax is None else dy_absmax
+        w_absmax = absmax(wt) if w_absmax is None else w_absmax
+    if complete and not needs_planes(dy.dtype, ldy, math):
+        wt_planes = None
+    elif complete and wt_planes is None:             # planes of the matrix wt itself: rows = Cin, cols = ldy
+        wt_planes = weight_planes(wt, math=math, w_absmax=w_absmax)
+
+    def args(dx, x_shape, dx_ldc, accumulate, geometry, bn):
+        return (ptr(dy), ptr(wt), ptr(wt_planes), ptr(dx), *x_shape[:3], Cin, ldy, R, S, *geometry, dy.shape[1], dy.shape[2], dx_ldc,
+                int(accumulate), *bn, math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax), ptr(w_absmax))
+    return (Cin, R, S, ldy), args
+
+
 def conv2d_dgrad_bn_apply(dy, wt, bn_x, scale, shift, relu, bn_workspace, dx, accumulate=False, dx_absmax=None, wt_planes=None,
                           math=None, dy_absmax=None, w_absmax=None, dy_planes=False, wt_shape=None):
     """The second pass of a data gradient that is never stored (include/dspn_nn.h dspn_conv2d_dgrad_bn_apply_f32): the 1 x 1
@@ -593,16 +615,12 @@ def conv2d_dgrad_bn_apply(dy, wt, bn_x, scale, shift, relu, bn_workspace, dx, ac
     coefficients the finalize (bn_backward_from_sums(phase=1, workspace=bn_workspace)) left in bn_workspace.  In the place of
     bn_backward_from_sums(phase=2): the same dx and dx_absmax.  Refused (RuntimeError naming the entry) where no kernel takes it."""
     N, H, W, C = bn_x.shape
-    Cin, R, S, ldy = wt.shape if wt is not None else wt_shape
+    (Cin, R, S, ldy), args = _dgrad_operands(dy, wt, wt_planes, wt_shape, math, dy_absmax, w_absmax, dy_planes, complete=False)
     assert dx.shape == bn_x.shape and dy.shape == (N, H, W, ldy) and Cin == C, (dx.shape, dy.shape, Cin)
-    math = _math_code(math)
-    if not (math == 3 and dy.dtype == torch.float32):
-        dy_absmax = w_absmax = None
-    check(_f("dspn_conv2d_dgrad_bn_apply", dy)(ptr(dy), ptr(wt), ptr(wt_planes), ptr(dx), N, H, W, Cin, ldy, R, S, 1, 0, 0, 1, H, W,
-                                              dx.shape[3], int(accumulate), ptr(bn_x), ptr(scale), ptr(shift), int(relu),
-                                              ptr(dx_absmax), math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax),
-                                              ptr(w_absmax), ptr(bn_workspace), bn_workspace.numel() * bn_workspace.element_size(),
-                                              stream()), "conv2d_dgrad_bn_apply")
+    check(_f("dspn_conv2d_dgrad_bn_apply", dy)(*args(dx, bn_x.shape, dx.shape[3], accumulate, (1, 0, 0, 1),
+                                                     (ptr(bn_x), ptr(scale), ptr(shift), int(relu), ptr(dx_absmax))),
+                                              ptr(bn_workspace), bn_workspace.numel() * bn_workspace.element_size(), stream()),
+          "conv2d_dgrad_bn_apply")
     return dx
 
 
@@ -620,45 +638,26 @@ def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=F
     sums_only (with bn_bwd): the sums tables alone -- dx is not stored and None comes back; conv2d_dgrad_bn_apply forms the
     product again (include/dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32: refused where no kernel takes it)."""
     N, H, W, Cx = x_shape
-    # wt may be None when the call reads piece planes (wt_planes, split math with ldy % 32 == 0): wt_shape = (Cin, R, S, ldy)
-    Cin, R, S, ldy = wt.shape if wt is not None else wt_shape
-    assert dy.shape[3] == ldy, (dy.shape, (Cin, R, S, ldy))
+    assert dy.shape[3] == (wt.shape if wt is not None else wt_shape)[3], (dy.shape, wt_shape)
     assert wt is not None or wt_planes is not None
-    math = _math_code(math)
-    if math == 3 and dy.dtype == torch.float32:
-        assert wt_planes is None or w_absmax is not None, "f16x2 planes come with the magnitude block they were cut by"
-        assert not dy_planes or dy_absmax is not None, "piece-plane gradients come with the magnitude block they were cut by"
-        dy_absmax = absmax(dy) if dy_absmax is None else dy_absmax
-        w_absmax = absmax(wt) if w_absmax is None else w_absmax
-    else:
-        dy_absmax = w_absmax = None
-    if needs_planes(dy.dtype, ldy, math):
-        if wt_planes is None:                    # planes of the matrix wt itself: rows = Cin, cols = ldy
-            wt_planes = weight_planes(wt, math=math, w_absmax=w_absmax)
-    else:
-        wt_planes = None
-    Ho, Wo = dy.shape[1], dy.shape[2]
+    # wt may be None when the call reads piece planes (wt_planes, split math with ldy % 32 == 0): wt_shape = (Cin, R, S, ldy)
+    (Cin, R, S, ldy), args = _dgrad_operands(dy, wt, wt_planes, wt_shape, math, dy_absmax, w_absmax, dy_planes, complete=True)
     if sums_only:
         assert out is None and bn_bwd is not None and not accumulate and bn_dy_absmax is None and strided_addend is None
     elif out is None:
         out = (zeros if Cx != Cin else empty)(N, H, W, Cx, device=dy.device, dtype=dy.dtype)
     assert (wt is None or wt.dtype == dy.dtype) and (sums_only or dy.dtype == out.dtype), (dy.dtype, out)
     ws = workspace(L().dspn_conv2d_split_workspace_bytes(N * H * W, Cin), dy.device, "split")
-    ph, pw = _hw(pad)
     bx, bsc, bsh, bmu, brs, brelu, bsums = bn_bwd if bn_bwd is not None else (None, None, None, None, None, False, None)
-    args = (ptr(dy), ptr(wt), ptr(wt_planes), ptr(out), N, H, W, Cin, ldy, R, S, stride, ph, pw,
-            dil, Ho, Wo, Cx if sums_only else out.shape[3], int(accumulate), ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu),
-            ptr(brs), int(brelu), ptr(bsums), 0 if bsums is None else bsums.numel() * 4,
-            ptr(bn_dy_absmax), math | (MATH_DY_PLANES if dy_planes else 0), ptr(dy_absmax),
-            ptr(w_absmax), ptr(ws), ws.numel())
+    args = args(out, x_shape, Cx if sums_only else out.shape[3], accumulate, (stride, *_hw(pad), dil),
+                (ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu), ptr(brs), int(brelu), ptr(bsums), 0 if bsums is None else bsums.numel() * 4,
+                 ptr(bn_dy_absmax))) + (ptr(ws), ws.numel())
+    entry = "dspn_conv2d_dgrad_bn_sums" if sums_only else "dspn_conv2d_dgrad_bn"
     if strided_addend is not None:
         sa = strided_addend
         assert sa.dtype == out.dtype and sa.is_contiguous() and sa.shape == (N, (H + 1) // 2, (W + 1) // 2, Cin), (sa.shape, x_shape)
-        check(_f("dspn_conv2d_dgrad_bn_sadd", dy)(*args, ptr(sa), sa.shape[1], sa.shape[2], stream()), "conv2d_dgrad")
-    elif sums_only:
-        check(_f("dspn_conv2d_dgrad_bn_sums", dy)(*args, stream()), "conv2d_dgrad")
-    else:
-        check(_f("dspn_conv2d_dgrad_bn", dy)(*args, stream()), "conv2d_dgrad")
+        entry, args = "dspn_conv2d_dgrad_bn_sadd", args + (ptr(sa), sa.shape[1], sa.shape[2])
+    check(_f(entry, dy)(*args, stream()), "conv2d_dgrad")
     return out
 
 

@@ -183,6 +183,35 @@ def test_convolution_plan_queries_are_pinned(monkeypatch):
         assert gen.query(lib, tuple(row["args"])) == row["results"], row["args"]
 
 
+def test_data_gradient_host_verdicts_are_pinned():
+    """tests/golden/dgrad_host_verdicts.json: the host path of the data gradient decides as it did when the fixture was written --
+    both route queries under every launch setting (with the full refusal text where the verdict is 0), and return value and
+    full text of the calls its variant entries refuse, competing reasons in their order.  The refused calls carry stand-in
+    pointers, so they are replayed only where no GPU is visible (tests/test_strided_addend_gpu.py and
+    tests/test_bn1_recompute_gpu.py refuse with real tensors there)."""
+    import importlib.util
+    import json
+    import torch
+    knobs = ("DSPN_XT", "DSPN_XT8", "DSPN_XT64", "DSPN_NT_MINTILES", "DSPN_NT_CFG64")      # what tile choice and route read
+    assert not any(k in os.environ for k in knobs), "run with the DSPN_* knobs unset"
+    golden = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_dgrad_host_verdicts_golden", os.path.join(golden, "make_dgrad_host_verdicts_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "dgrad_host_verdicts.json")) as f:
+        doc = json.load(f)
+    lib = _lib.lib()
+    assert len(doc["routes"]) >= 200 and [tuple(r["args"]) for r in doc["routes"]] == gen.route_cases()
+    for row in doc["routes"]:
+        assert gen.route_query(lib, tuple(row["args"])) == row["results"], row["args"]
+    assert len(doc["refused"]) >= 100 and [(r["entry"], r["args"]) for r in doc["refused"]] == gen.refused_cases()
+    assert all(r["results"][0] in (-1, -2) for r in doc["refused"]), "every pinned call is one the host path refuses"
+    if torch.cuda.is_available():
+        return
+    for row in doc["refused"]:
+        assert gen.refused_call(lib, row["entry"], row["args"]) == row["results"], (row["entry"], row["args"])
+
+
 def test_oracle_is_clean_under_address_and_ub_sanitizers():
     """SURVEY.md section 5 (sanitizers on the host build): the C oracle's three operators over exactly-sized heap buffers and the
     degenerate inputs of the GPU tests, built with -fsanitize=address,undefined (oracle/sanitize_driver.c)"""
