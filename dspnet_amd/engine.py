@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import functional as fn, graph_plan
+from .magnitudes import Magnitudes
 
 
 # Test switch: with FUSE_BATCHNORM = False every BatchNorm runs its own statistics / apply / backward kernels and
@@ -267,35 +268,20 @@ class Graph:
         # created: a later functional.set_conv_math() does not change what an existing graph computes
         self.math = fn.get_conv_math()
         self.wp_table = None       # split math: descriptor table of every piece-plane weight operand (one launch per step)
-        # "f16x2" math: one float per operand magnitude (functional.absmax), all in one arena zeroed at the top of forward();
-        # slots are handed out while the graph is built (new_scalar) and become views of the arena in finalize()
-        self._nscal = 0
-        self.scalars = None
-        self.am_table = None       # descriptor table of the weight magnitudes (one launch per step)
-        self._am_x = {}            # (id of the raw input tensor, id of its affine scale) -> slot shared by its readers
-        self._am_wanted = set()    # magnitude slots some two-piece convolution will read off its input tensor (want_magnitude)
-        self._am_done = set()      # slots already computed in the current step
-        self._am_bwd_slots, self._am_bwd_ran = set(), False
-        self._am_table_slots = set()   # weight magnitudes taken by the one batched launch at the top of forward()
-        # range monitor of the "f16x2" math: per convolution-input slot the smallest non-zero per-channel magnitude, where a
-        # BatchNorm finalize sees the channels (range_report)
-        self.scalars_min = None
+        # "f16x2" math: the ledger of the step's operand magnitudes (magnitudes.py); nodes hold slot indices
+        self.mag = Magnitudes(self.math)
         # round 5: the range GUARD of the "f16x2" math.  Per magnitude slot the smallest non-zero per-channel magnitude travels
-        # beside the largest (scalars_min: inputs from the BatchNorm finalize, weights from one batched launch per step, output
-        # gradients from the BatchNorm backward's per-channel bounds); a convolution one of whose operands spanned more than
+        # beside the largest (the ledger's minima); a convolution one of whose operands spanned more than
         # 2^GUARD_BITS in the PREVIOUS pass runs all three of its calls in the three-piece bf16 math this step (guard_fb on the
         # node; the span of a trained net's channels moves over many steps, not within one).  DSPN_RANGE_GUARD=0 switches it off.
         self.guard = dict(enabled=os.environ.get("DSPN_RANGE_GUARD", "1") != "0", have_stats=False, risk=frozenset(),
                           calls=0, calls_total=0, at_risk_slots=0)
-        self.wmin_table = None     # descriptor table of the per-output-channel weight minima (one launch per step)
         # frozen parameters (set_freeze, before the first node is built): names and / or a regex matched with re.match
         self.fixed_names, self.freeze_re, self.freezing = frozenset(), None, False
-        # the derived operands of FROZEN weights (transposes, bf16 copies, piece planes, magnitudes, per-row minima) have tables
-        # of their own, run once and again only after set_params / load_params (frozen_stale); their magnitude slots sit at
-        # the end of the arena, behind _nscal_step, which forward() does not zero
-        self.wt_frozen = self.wp_frozen = self.am_frozen = self.wmin_frozen = None
+        # the derived operands of FROZEN weights (transposes, bf16 copies, piece planes; magnitudes and per-row minima in the
+        # ledger) have tables of their own, run once and again only after set_params / load_params (frozen_stale)
+        self.wt_frozen = self.wp_frozen = None
         self.frozen_stale = False
-        self._nscal_step = 0
 
     def set_freeze(self, fixed_param_names=None, freeze_pattern=None):
         """Freeze parameters of the nodes built from now on: every name in fixed_param_names and every name freeze_pattern
@@ -342,67 +328,25 @@ class Graph:
                 t.requires_grad = False
         return node
 
-    def new_scalar(self, backward=False):
-        """index of a fresh slot of the operand-magnitude arena ("f16x2" math).  backward=True: the magnitude of a gradient;
-        a second backward pass after one forward pass takes those again (begin_backward)"""
-        self._nscal += 1
-        if backward:
-            self._am_bwd_slots.add(self._nscal - 1)
-        return self._nscal - 1
-
-    def scalar(self, i):
-        return None if (i is None or self.scalars is None) else self.scalars[i * fn.ABSMAX_SLOTS:(i + 1) * fn.ABSMAX_SLOTS]
-
-    def want_magnitude(self, t):
-        """a two-piece convolution will multiply tensor t as it is: whoever produces it (or what it was pooled from) is asked
-        to leave its magnitude block (Conv._out_magnitude) -- nobody takes one for tensors no convolution reads"""
-        while t is not None:
-            if t.am_slot is not None:
-                self._am_wanted.add(t.am_slot)
-            t = t.alias_of
-
-    def magnitude(self, slot, tensor, src=None):
-        """"f16x2" math: the magnitude block of `tensor` in slot `slot` (a node-owned index from new_scalar), taken by a pass
-        over the tensor the first time a step asks for it and reused afterwards; None in the other math modes.
-        src: the engine Tensor behind `tensor` -- if its producer has already left a bound of it this step, that block"""
-        if slot is None or self.scalars is None or tensor.dtype != torch.float32:
-            return None
-        if src is not None and src.am_slot is not None and src.am_slot in self._am_done:
-            return self.scalar(src.am_slot)
-        out = self.scalar(slot)
-        if slot not in self._am_done:
-            fn.absmax(tensor, out=out)
-            self._am_done.add(slot)
-        return out
+    @property
+    def scalars(self):
+        """the magnitude arena of the "f16x2" math; None in the other math modes and on CPU graphs"""
+        return self.mag.arena
 
     def range_report(self):
         """"f16x2" math, after a step (one device -> host copy): (tensors seen, tensors whose channel magnitudes span more than
         2^16, largest span in bits) over the convolution inputs whose BatchNorm finalize saw per-channel extremes.  The
         two-piece math keeps fp32 relative accuracy for elements within 2^17 of their tensor's largest magnitude; channels
         further below keep an absolute error of 2^-39 of that magnitude (include/dspn_nn.h)."""
-        if self.scalars is None:
-            return (0, 0, 0.0)
-        mx = self.scalars.view(-1, fn.ABSMAX_SLOTS).max(dim=1).values.cpu().numpy()
-        mn = self.scalars_min.cpu().numpy()
-        ok = np.isfinite(mn) & (mn > 0) & np.isfinite(mx) & (mx > 0)
-        if not ok.any():
-            return (0, 0, 0.0)
-        span = np.log2(mx[ok] / mn[ok])
-        return (int(ok.sum()), int((span > 16).sum()), float(span.max()))
+        return self.mag.range_report()
 
     GUARD_BITS = 16
     GUARD_PERIOD = 4
 
-    def _spans_device(self):
-        """(2, slots) device tensor: the largest (FINITE partial maxima, as the kernels read them) and the smallest non-zero
-        per-channel magnitude per slot of the pass that has just been issued"""
-        mx = self.scalars.view(-1, fn.ABSMAX_SLOTS)
-        mx = torch.where(mx < 3.0e38, mx, torch.zeros_like(mx)).max(dim=1).values
-        return torch.stack([mx, self.scalars_min])
-
     def slot_spans(self):
-        """the same as numpy arrays (synchronises); nan / inf where a slot has no per-channel information"""
-        both = self._spans_device().cpu().numpy()
+        """the ledger's spans (largest, smallest non-zero per-channel magnitude per slot) as numpy arrays (synchronises);
+        nan / inf where a slot has no per-channel information"""
+        both = self.mag.spans_device().cpu().numpy()
         return both[0], both[1]
 
     def _update_guard(self, blocking=False):
@@ -436,12 +380,12 @@ class Graph:
         gd = self.guard
         if blocking:
             gd["queue"] = []
-            return self._spans_device().cpu().numpy()
-        pool = gd.setdefault("pinned", [torch.empty((2, self.scalars_min.numel()), dtype=torch.float32, pin_memory=True)
+            return self.mag.spans_device().cpu().numpy()
+        pool = gd.setdefault("pinned", [torch.empty((2, self.mag.slots), dtype=torch.float32, pin_memory=True)
                                         for _ in range(3)])       # (at most two copies are in flight)
         host = pool[gd.get("pin_i", 0) % 3]
         gd["pin_i"] = gd.get("pin_i", 0) + 1
-        host.copy_(self._spans_device(), non_blocking=True)
+        host.copy_(self.mag.spans_device(), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         gd.setdefault("queue", []).append((host, ev))
@@ -488,6 +432,11 @@ class Graph:
         """(convolutions on the fallback this pass, fallback kernel calls this pass, slots whose span exceeded 2^GUARD_BITS last pass)"""
         return len(self.guard["risk"]), self.guard["calls"], self.guard["at_risk_slots"]
 
+    def guard_count_call(self):
+        """a convolution call of this pass ran on the guard's fallback"""
+        self.guard["calls"] += 1
+        self.guard["calls_total"] += 1
+
     def finalize(self, seed=0):
         """allocate the flat parameter / gradient / momentum arenas and initialise"""
         graph_plan.plan(self)
@@ -525,34 +474,14 @@ class Graph:
                     self.half_operands = tab[3]
         if self.device.type == "cuda":
             wnodes = [n for n in self.nodes if getattr(n, "am_w", None) is not None and getattr(n, "w", None) is not None]
-            self._nscal_step = self._nscal
-            for n in wnodes:
-                if n.w.fixed:       # (a slot at the end: forward() zeroes the slots in front of _nscal_step only)
-                    n.am_w = self.new_scalar()
-                    if isinstance(n, Deconv4x4s2):
-                        n.am = (n.am[0], n.am_w, n.am[2])
-            if self.math == "f16x2" and self._nscal:
-                self.scalars = torch.zeros(self._nscal * fn.ABSMAX_SLOTS, dtype=torch.float32, device=self.device)
-                self.scalars_min = torch.full((self._nscal,), float("inf"), dtype=torch.float32, device=self.device)
-                self._am_table_slots = {n.am_w for n in wnodes}
-                for frozen in (False, True):
-                    sel = [n for n in wnodes if n.w.fixed == frozen]
-                    if not sel:
-                        continue
-                    am = fn.absmax_table([(n.w.data, self.scalar(n.am_w)) for n in sel], self.device)
-                    wmin = (fn.absmin_rows_table([(n.w.data.view(n.w.shape[0], -1), self.scalars_min[n.am_w:n.am_w + 1])
-                                                  for n in sel], self.device) if self.guard["enabled"] else None)
-                    if frozen:
-                        self.am_frozen, self.wmin_frozen = am, wmin
-                    else:
-                        self.am_table, self.wmin_table = am, wmin
+            self.mag.allocate(self.device, wnodes, minima=self.guard["enabled"])
             convs = [n for n in self.nodes if isinstance(n, Conv) and (n.wp is not None or n.wtp is not None)]
             for frozen in (False, True):
-                planes = [(n.w.data, n.wp, n.wtp) + ((self.scalar(n.am_w),) if self.math == "f16x2" else ())
+                planes = [(n.w.data, n.wp, n.wtp) + ((self.mag.block(n.am_w),) if self.math == "f16x2" else ())
                           for n in convs if n.w.fixed == frozen]
                 if planes:
                     setattr(self, "wp_frozen" if frozen else "wp_table", fn.weight_planes_table(planes, self.device))
-            self.frozen_stale = any(t is not None for t in (self.wt_frozen, self.wp_frozen, self.am_frozen))
+            self.frozen_stale = any(t is not None for t in (self.wt_frozen, self.wp_frozen, self.mag.am_frozen))
         if self.device.type == "cuda":
             # every Conv keeps the split-K partial sums of its weight gradient in a buffer of its own, so that the
             # slab sums of many layers run as one launch (flush_slabs) instead of one small kernel per layer
@@ -629,17 +558,9 @@ class Graph:
         if self.half_operands:         # bf16 copies (forward) and transposes (data gradient) of every weight, one launch
             fn.weight_transpose_batch(*self.wt_table)
             self.wt_batched = True
-        if self.scalars is not None:   # "f16x2" math: every operand magnitude of the step starts from zero; the weights' now
+        if self.mag.active:            # "f16x2" math: every operand magnitude of the step starts from zero; the weights' now
             self._update_guard(blocking=self.guard.pop("decide_now", False))
-            self.scalars[:self._nscal_step * fn.ABSMAX_SLOTS].zero_()     # (frozen weights' slots behind: refresh_frozen)
-            self.scalars_min[:self._nscal_step].fill_(float("inf"))
-            if self.wmin_table is not None and self.guard.get("wmin_now", True):
-                fn.absmin_rows_batch(*self.wmin_table)
-            self._am_done = set()
-            self._am_bwd_ran = False
-            if self.am_table is not None:
-                fn.absmax_batch(*self.am_table)
-                self._am_done |= self._am_table_slots
+            self.mag.begin_step(minima=self.guard.get("wmin_now", True))     # (frozen weights' slots: refresh_frozen)
         self.refresh_frozen()
         if self.wp_table is not None:  # split math: the piece planes of every weight (forward and data-gradient operands;
             fn.weight_planes_batch(*self.wp_table)     # "f16x2": cut relative to the magnitudes just taken)
@@ -679,13 +600,7 @@ class Graph:
         self.frozen_stale = False
         if self.wt_frozen is not None:
             fn.weight_transpose_batch(*self.wt_frozen)
-        if self.scalars is not None:
-            self.scalars[self._nscal_step * fn.ABSMAX_SLOTS:].zero_()
-            self.scalars_min[self._nscal_step:].fill_(float("inf"))
-            if self.wmin_frozen is not None:
-                fn.absmin_rows_batch(*self.wmin_frozen)
-            if self.am_frozen is not None:
-                fn.absmax_batch(*self.am_frozen)
+        self.mag.refresh_frozen()
         if self.wp_frozen is not None:
             fn.weight_planes_batch(*self.wp_frozen)
 
@@ -797,12 +712,7 @@ class Graph:
             assert not self.side_bwd["dirty"], "the previous backward pass left side-stream work unjoined"
             self.side_bwd["forked"] = False
         self.guard["have_stats"] = True      # (the spans of a whole pass -- inputs, weights, gradients -- exist once this one has run)
-        if self.scalars is not None:
-            if self._am_bwd_ran:       # a second backward pass on the same forward pass: new gradients, new magnitudes
-                for slot in self._am_bwd_slots & self._am_done:
-                    self.scalar(slot).zero_()
-                self._am_done -= self._am_bwd_slots
-            self._am_bwd_ran = True
+        self.mag.begin_backward()
         if self.half_operands:
             return                     # prepared by forward(); the weights have not changed since
         self.wt_batched = self.wt_table is not None
@@ -1034,7 +944,7 @@ class BatchNorm(Node):
             self.out.affine_src = (x, self.scale, self.shift, relu)
         self.out.bn_node = self
         # "f16x2" math: a MATERIALISED output leaves its magnitude as a by-product of the apply kernel
-        self.am_out = g.new_scalar() if (g.math == "f16x2" and self.out.dtype == torch.float32) else None
+        self.am_out = g.mag.new() if (g.math == "f16x2" and self.out.dtype == torch.float32) else None
         self.out.am_slot = self.am_out
         self.conv_consumers = []     # convolutions reading self.out (deferred apply), in forward order
         self.mat_consumers = []      # plain convolutions reading a MATERIALISED self.out (their last data gradient can
@@ -1078,16 +988,14 @@ class BatchNorm(Node):
             rows = int(np.prod(self.x.shape[:-1]))
             # "f16x2" math: the convolutions that fold this BatchNorm into their loaders multiply (relu)(x * scale + shift);
             # its magnitude comes out of this finalize kernel, from the extremes the producer wrote beside the statistics
-            g, mm, am = self._g, getattr(self.x.producer, "out_minmax", None), None
-            slot = g._am_x.get((id(self.x), id(self.scale))) if (mm is not None and g.scalars is not None) else None
-            if slot is not None:
-                am = g.scalar(slot)
-                g._am_done.add(slot)
+            mag, mm = self._g.mag, getattr(self.x.producer, "out_minmax", None)
+            slot = mag.input_slot(self.x, self.scale, create=False) if mm is not None else None
+            am = mag.claim(slot)
             fn.bn_stats_from_tiles(buf, tiles, tile_rows, rows, self.x.shape[-1], self.eps,
                                    None if self.gamma is None else self.gamma.data, self.beta.data,
                                    self.mean, self.rstd, self.scale, self.shift,
                                    tile_minmax=mm if am is not None else None, relu=self.relu, out_absmax=am,
-                                   out_absmin=None if am is None else g.scalars_min[slot:slot + 1],
+                                   out_absmin=None if am is None else mag.min_view(slot),
                                    out_chan_minmax=self.x_ext if am is not None else None, moving=moving)
             self.planes_ready = self.planes is not None and am is not None
             if self.planes_ready:
@@ -1096,16 +1004,13 @@ class BatchNorm(Node):
             fn.bn_stats(self.x.data, self.eps, None if self.gamma is None else self.gamma.data, self.beta.data,
                         self.mean, self.rstd, self.scale, self.shift, moving=moving)
         if not self.defer_apply:
-            am = self._g.scalar(self.am_out)
-            fn.bn_apply(self.x.data, self.scale, self.shift, relu=self.relu, out=self.out.data, out_absmax=am)
-            if am is not None:
-                self._g._am_done.add(self.am_out)
+            fn.bn_apply(self.x.data, self.scale, self.shift, relu=self.relu, out=self.out.data,
+                        out_absmax=self._g.mag.claim(self.am_out))
 
     def _x_ext_valid(self):
         """the per-channel extremes of x were written by this step's forward finalize (the magnitude slot they come with is done)"""
-        g = self._g
-        slot = g._am_x.get((id(self.x), id(self.scale)))
-        return slot is not None and slot in g._am_done
+        mag = self._g.mag
+        return mag.done(mag.input_slot(self.x, self.scale, create=False))
 
     def finalize_beside(self):
         """Round 6: called by the convolution whose data gradient has just gathered this node's backward
@@ -1163,10 +1068,8 @@ class BatchNorm(Node):
             # tensor read by this BatchNorm alone, or the residual stream, whose last writer in backward order is the next
             # unit's first BatchNorm), its magnitude comes out of the apply kernel instead of a pass of its own
             prod, g = self.x.producer, self._g
-            if (isinstance(prod, Conv) and prod.am_dy is not None and g.scalars is not None and dx.dtype == torch.float32
-                    and self.completes_x_grad):
-                am = g.scalar(prod.am_dy)
-                g._am_done.add(prod.am_dy)
+            if isinstance(prod, Conv) and dx.dtype == torch.float32 and self.completes_x_grad:
+                am = g.mag.claim(prod.am_dy)
         else:  # the parameters alone: reductions and finalize, no dx (the kernels take dx == NULL)
             dx, acc = fn.NO_OUTPUT, False
         if self.pool_grad is not None:
@@ -1187,8 +1090,8 @@ class BatchNorm(Node):
             self._from_sums(beside, (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
                                      None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
                             dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=False, dx_absmax=am,
-                                 dy_absmax=self._g.scalar(self.am_dyin), x_chan_minmax=self.x_ext, dx_planes=True,
-                                 dx_absmin=g.scalars_min[prod.am_dy:prod.am_dy + 1] if g.guard["enabled"] else None))
+                                 dy_absmax=g.mag.block(self.am_dyin), x_chan_minmax=self.x_ext, dx_planes=True,
+                                 dx_absmin=g.mag.min_view(prod.am_dy) if g.guard["enabled"] else None))
             self.x.grad_planes = True
             return
         if self.bwd_sums_ready:      # the two reductions came out of the data-gradient kernel's epilogue
@@ -1308,17 +1211,15 @@ class Conv(Node):
         # (act1 feeds conv1 and the projection shortcut); the gradient's and the weight's belong to this node.
         self.am_x = self.am_dy = self.am_w = None
         if g.math == "f16x2" and self.out.dtype == torch.float32:
-            key = (id(self.x_raw), None if self.in_affine is None else id(self.in_affine[0]))
-            if key not in g._am_x:
-                g._am_x[key] = g.new_scalar()
-            self.am_x, self.am_dy, self.am_w = g._am_x[key], g.new_scalar(backward=True), g.new_scalar()
+            self.am_x = g.mag.input_slot(self.x_raw, None if self.in_affine is None else self.in_affine[0])
+            self.am_dy, self.am_w = g.mag.new(backward=True), g.mag.new()
         # ... and of the OUTPUT as stored, where no BatchNorm reads it (no statistics epilogue: vgg16_reduced, the SSD extra layers):
         # the convolution's own epilogue leaves it (fn.conv2d_forward out_absmax), the next convolution needs no pass over the tensor
-        self.am_out = g.new_scalar() if (self.am_x is not None and not tap_expand) else None
+        self.am_out = g.mag.new() if (self.am_x is not None and not tap_expand) else None
         if self.am_out is not None:
             self.out.am_slot = self.am_out       # (pooled / aliased tensors built on it inherit the slot)
         if self.am_x is not None and self.in_affine is None:
-            g.want_magnitude(self.x_raw)         # the producer of this input leaves its magnitude if it can
+            g.mag.want(self.x_raw)        # the producer of this input leaves its magnitude if it can
         self.x_planes_bn = None      # the deferred BatchNorm that also leaves this node's input as piece planes (graph_plan.input_planes)
         self.bn_bwd_node = None      # the BatchNorm whose backward sums this node's data gradient gathers (graph_plan.bn_backward_fusion)
         self._wg_worth = None        # _wgrad_worth_a_stream, once estimated
@@ -1377,10 +1278,10 @@ class Conv(Node):
     def _magnitudes(self, which):
         """device scalars of this node's operand magnitudes ("f16x2" math; None otherwise).  `x`: computed by the first
         reader of the (tensor, affine) pair in a step; `dy`: by backward(); `w`: by Graph.forward for all weights."""
-        g = self._g
-        if self.am_x is None or g.scalars is None:
+        mag = self._g.mag
+        if self.am_x is None or not mag.active:
             return None
-        if which == "x" and self.am_x not in g._am_done:
+        if which == "x" and not mag.done(self.am_x):
             src = self.x_raw
             while src.alias_of is not None:       # BlockGrad: the same values under another name
                 src = src.alias_of
@@ -1389,16 +1290,15 @@ class Conv(Node):
             # sit at the extremes of x (monotone per channel); without one, |x| is largest at one of them
             table = getattr(prod, "out_minmax", None) if getattr(prod, "out", None) is src else None
             if table is not None:
-                fn.absmax(table.view(-1, table.shape[-1]), self.in_affine, out=g.scalar(self.am_x))
-            elif src.am_slot is not None and src.am_slot in g._am_done:
+                fn.absmax(table.view(-1, table.shape[-1]), self.in_affine, out=mag.claim(self.am_x))
+            elif mag.done(src.am_slot):
                 # round 4: a bound the producer left while it wrote the tensor (or the bound of what it was pooled from)
                 if self.in_affine is None:
-                    return g.scalar(src.am_slot)
-                fn.absmax_affine_bound(self.in_affine[0], self.in_affine[1], g.scalar(src.am_slot), g.scalar(self.am_x))
+                    return mag.block(src.am_slot)
+                fn.absmax_affine_bound(self.in_affine[0], self.in_affine[1], mag.block(src.am_slot), mag.claim(self.am_x))
             else:
-                fn.absmax(self.x_raw.data, self.in_affine, out=g.scalar(self.am_x))
-            g._am_done.add(self.am_x)
-        return g.scalar({"x": self.am_x, "dy": self.am_dy, "w": self.am_w}[which])
+                fn.absmax(self.x_raw.data, self.in_affine, out=mag.claim(self.am_x))
+        return mag.block({"x": self.am_x, "dy": self.am_dy, "w": self.am_w}[which])
 
     def forward(self):
         xa, wa = self._magnitudes("x"), self._magnitudes("w")
@@ -1412,32 +1312,29 @@ class Conv(Node):
         if self.guard_fb:
             return self._forward_fallback()
         xp = self._x_planes()
-        oa = self._out_magnitude()
         fn.conv2d_forward(self.x_raw.data if xp is None else xp, self.wop(), None if self.b is None else self.b.data, self.stride,
                           self.pad, self.dil, relu=self.relu, out=self.out.data,
                           residual=None if self.residual is None else self.residual.data,
                           in_affine=self.in_affine if xp is None else None,
                           out_stats=None if self.out_stats is None else self.out_stats[0], w_planes=self.wp,
                           math=self.math, x_absmax=xa, w_absmax=wa, out_minmax=self.out_minmax, x_planes=xp is not None,
-                          out_absmax=oa)
-        if oa is not None:
-            self._g._am_done.add(self.am_out)
+                          out_absmax=self._out_magnitude())
 
     def _out_magnitude(self):
-        """the magnitude block this call's epilogue fills (None where a BatchNorm takes statistics -- its finalize hands the
-        magnitude on -- or the math is not "f16x2")"""
-        g = self._g
-        if (not FUSE_CONV_MAGNITUDES or self.am_out is None or g.scalars is None or self.out_stats is not None
-                or self.am_out not in g._am_wanted or xa_unavailable(self)):
+        """the magnitude block this call's epilogue fills, claimed (None where a BatchNorm takes statistics -- its finalize
+        hands the magnitude on -- or the math is not "f16x2")"""
+        mag = self._g.mag
+        if (not FUSE_CONV_MAGNITUDES or self.am_out is None or not mag.active or self.out_stats is not None
+                or not mag.wanted(self.am_out) or xa_unavailable(self)):
             return None
-        return g.scalar(self.am_out)
+        return mag.claim(self.am_out)
 
     def _x_planes(self):
         """the input as piece planes, when the BatchNorm in front wrote them this step (cut by this node's x magnitude)"""
         bn = self.x_planes_bn
         if self.guard_fb:
             return None
-        return bn.planes if (bn is not None and bn.planes_ready and self.am_x in self._g._am_done) else None
+        return bn.planes if (bn is not None and bn.planes_ready and self._g.mag.done(self.am_x)) else None
 
     def _w3(self, transposed):
         """the weight operand of a fallback call: three bf16 piece planes cut on the spot (None where the three-piece kernels
@@ -1459,9 +1356,7 @@ class Conv(Node):
         oa = self._out_magnitude()
         if oa is not None:
             fn.absmax(self.out.data, out=oa)
-            self._g._am_done.add(self.am_out)
-        self._g.guard["calls"] += 1
-        self._g.guard["calls_total"] += 1
+        self._g.guard_count_call()
 
     def backward(self):
         if not self.out._gw:
@@ -1470,13 +1365,10 @@ class Conv(Node):
         planes = self.out.grad_planes            # fp16 piece planes from the BatchNorm behind this convolution (never with relu / bias / residual)
         if self.relu and self.b is not None:     # ReLU mask and bias gradient in one pass over dy
             # "f16x2" math: that pass also leaves the magnitude of the masked gradient, which both of its readers cut it by
-            dya0 = None
-            if (FUSE_CONV_MAGNITUDES and self.am_dy is not None and self._g.scalars is not None
-                    and self.am_dy not in self._g._am_done and dy.dtype == torch.float32):
-                dya0 = self._g.scalar(self.am_dy)
+            mag, dya0 = self._g.mag, None
+            if FUSE_CONV_MAGNITUDES and not mag.done(self.am_dy) and dy.dtype == torch.float32:
+                dya0 = mag.claim(self.am_dy)
             fn.relu_backward_colsum(self.out.data, dy, self.cout, dx=dy, out=self.b.grad, dx_absmax=dya0)
-            if dya0 is not None:
-                self._g._am_done.add(self.am_dy)
         elif self.relu:
             fn.relu_backward(self.out.data, dy, dx=dy)
         if self.residual is not None and self.residual.requires_grad:
@@ -1485,9 +1377,8 @@ class Conv(Node):
             fn.colsum(dy, self.cout, out=self.b.grad)
         # "f16x2" math: the gradient's magnitude once (after the in-place ReLU mask above), for both of its readers
         xa, dya, wa = self._magnitudes("x"), self._magnitudes("dy"), self._magnitudes("w")
-        if dya is not None and self.am_dy not in self._g._am_done:       # (else: the BatchNorm backward that completed dy took it)
-            fn.absmax(dy, out=dya)
-            self._g._am_done.add(self.am_dy)      # (a projection shortcut that shares this slot reads the same gradient)
+        if dya is not None and not self._g.mag.done(self.am_dy):       # (else: the BatchNorm backward that completed dy took it)
+            fn.absmax(dy, out=self._g.mag.claim(self.am_dy))    # (a projection shortcut that shares this slot reads the same gradient)
         # round 6: when this data gradient gathers the backward sums of the BatchNorm in front (bn_bwd_node), it goes FIRST and
         # that node's finalize rides in front of the weight gradient's grid (BatchNorm.finalize_beside)
         bn = self.bn_bwd_node if self.x.requires_grad else None
@@ -1554,8 +1445,7 @@ class Conv(Node):
             else:
                 fn.conv2d_wgrad(self.x_raw.data, dy, self.w.shape, self.stride, self.pad, self.dil, out=self.w.grad,
                                 in_affine=self.in_affine, math="bf16x3")
-            self._g.guard["calls"] += 1
-            self._g.guard["calls_total"] += 1
+            self._g.guard_count_call()
         elif self.slabs is not None:
             xp = self._x_planes()
             fn.conv2d_wgrad_slabs(self.x_raw.data if xp is None else xp, dy, self.w.shape, self.slabs, self.stride, self.pad,
@@ -1586,7 +1476,7 @@ class Conv(Node):
             bn_bwd = (bn.x.data, bn.scale, bn.shift, bn.mean, bn.rstd, bn.relu, bn.bwd_sums[0])
             bn.bwd_sums_ready = True
             if bn.dx_planes:         # that BatchNorm's backward bounds its dx from the largest gradient stored here
-                bn_dya = self._g.scalar(bn.am_dyin)
+                bn_dya = g.mag.claim(bn.am_dyin)
             if self._recompute_route(bn, planes, acc):
                 # the sums alone: dx stays unwritten; bn's backward runs this product again (BatchNorm._apply)
                 fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, bn_bwd=bn_bwd, wt_planes=self.wtp,
@@ -1600,8 +1490,7 @@ class Conv(Node):
                             accumulate=acc, bn_bwd=bn_bwd, wt_planes=w3, math="bf16x3", wt_shape=self.wt_shape)
             if bn_dya is not None:       # (the two-piece data gradient leaves this by-product in its epilogue)
                 fn.absmax(dx, out=bn_dya)
-            self._g.guard["calls"] += 1
-            self._g.guard["calls_total"] += 1
+            self._g.guard_count_call()
             return
         fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, out=dx, accumulate=acc,
                         bn_bwd=bn_bwd, wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa,
@@ -1683,11 +1572,11 @@ class BilinearConcatConv(Node):
         # "f16x2" math: per component, slots for the magnitudes of its input, its weight slice and its output gradient --
         # each taken once per step and shared by the forward, weight-gradient and data-gradient calls that multiply it
         f16 = g.math == "f16x2"
-        self.am = [(g.new_scalar(), g.new_scalar(), g.new_scalar(backward=True)) if f16 else (None, None, None) for _ in inputs]
+        self.am = [(g.mag.new(), g.mag.new(), g.mag.new(backward=True)) if f16 else (None, None, None) for _ in inputs]
         # round 4: every weight slice is bounded by the magnitude of the whole weight, which the one batched launch at the top
-        # of forward() takes with all the others (Graph.am_table); the inputs are materialised BatchNorm outputs, which leave
+        # of forward() takes with all the others (Magnitudes.am_table); the inputs are materialised BatchNorm outputs, which leave
         # theirs while they are written; the sampler's data-gradient passes leave the gradients'
-        self.am_w = g.new_scalar() if f16 else None
+        self.am_w = g.mag.new() if f16 else None
         for t in inputs:
             # W_c . x_c at the component's own resolution (its gradient in backward).  Every component goes through
             # the sampler, also the ones that already have the target size: once the optimizer has moved
@@ -1721,7 +1610,7 @@ class BilinearConcatConv(Node):
         for c, t in enumerate(self.inputs):
             if self.wch[c] is not None:      # bf16 operands of this slice: copy + transpose in one launch
                 fn.weight_transpose(self.wc[c], out=self.wct[c], copy=self.wch[c])
-            xa, wa = self._g.magnitude(self.am[c][0], t.data, src=t), self._g.scalar(self.am_w)
+            xa, wa = self._g.mag.take(self.am[c][0], t.data, src=t), self._g.mag.block(self.am_w)
             if self.wcp[c] is not None:
                 fn.weight_planes(self.wc[c], out=self.wcp[c], math=self.math, w_absmax=wa)
             fn.conv2d_forward(t.data, self.wc[c] if self.wch[c] is None else self.wch[c], None, 1, 0, 1, out=self.zc[c],
@@ -1743,14 +1632,13 @@ class BilinearConcatConv(Node):
             self.tpart_off = np.cumsum([0] + rows).tolist()
         Cin = self.offsets[-1]
         for c, t in enumerate(self.inputs):
-            dza = self._g.scalar(self.am[c][2])
-            if dza is not None and self.zc[c].dtype == torch.float32:
-                self._g._am_done.add(self.am[c][2])
+            mag = self._g.mag      # (a gradient that is not float32 is never read through its block: written, not claimed)
+            dza = mag.claim(self.am[c][2]) if self.zc[c].dtype == torch.float32 else mag.block(self.am[c][2])
             dz = fn.affine_sampler_backward_data_theta(self.z, self.theta.data, self.zc[c], 0,
                                                        self.tpart[self.tpart_off[c]:self.tpart_off[c + 1]], dx=self.zc[c],
                                                        dx_absmax=dza)
-            xa, wa = self._g.magnitude(self.am[c][0], t.data, src=t), self._g.scalar(self.am_w)
-            dza = self._g.magnitude(self.am[c][2], dz)
+            xa, wa = self._g.mag.take(self.am[c][0], t.data, src=t), self._g.mag.block(self.am_w)
+            dza = mag.take(self.am[c][2], dz)
             if not self.w.fixed:
                 fn.conv2d_wgrad(t.data, dz, (self.T, 1, 1, t.shape[3]), 1, 0, 1, out=self.dwc[c], math=self.math,
                                 x_absmax=xa, dy_absmax=dza)
@@ -1780,15 +1668,15 @@ class Deconv4x4s2(Node):
         self.out.channels = channels
         self.math = g.math
         self._g = g
-        self.am = (g.new_scalar(), g.new_scalar(), g.new_scalar(backward=True)) if g.math == "f16x2" else (None, None, None)   # x, w, dy
-        self.am_w = self.am[1]      # (taken with every other weight's by the batched launch at the top of forward())
+        self.am = (g.mag.new(), g.mag.new(), g.mag.new(backward=True)) if g.math == "f16x2" else (None, None, None)   # x, w, dy
+        self.am_w = self.am[1]      # (taken with every other weight's by the batched launch; a frozen weight's moves: Magnitudes.allocate)
         self.flops_fwd = 2.0 * channels * channels * 16 * H * W * N
         self.flops_bwd = self.flops_fwd * (2 if x.requires_grad else 1)
 
     def forward(self):
         fn.weight_transpose(self.w.data, out=self.wt, copy=self.wh)
-        g = self._g
-        xa, wa = g.magnitude(self.am[0], self.x.data, src=self.x), g.magnitude(self.am[1], self.w.data)
+        mag = self._g.mag
+        xa, wa = mag.take(self.am[0], self.x.data, src=self.x), mag.take(self.am_w, self.w.data)
         fn.conv2d_dgrad(self.x.data, self.wt, self.out.shape, 2, 1, 1, out=self.out.data, math=self.math, dy_absmax=xa,
                         w_absmax=wa)
 
@@ -1796,8 +1684,8 @@ class Deconv4x4s2(Node):
         if not self.out._gw:
             return
         dy = self.out.grad
-        g = self._g
-        xa, wa, dya = g.magnitude(self.am[0], self.x.data, src=self.x), g.magnitude(self.am[1], self.w.data), g.magnitude(self.am[2], dy)
+        mag = self._g.mag
+        xa, wa, dya = mag.take(self.am[0], self.x.data, src=self.x), mag.take(self.am_w, self.w.data), mag.take(self.am[2], dy)
         if not self.w.fixed:
             fn.conv2d_wgrad(dy, self.x.data, self.w.shape, 2, 1, 1, out=self.w.grad, math=self.math, x_absmax=dya,
                             dy_absmax=xa)
@@ -1858,7 +1746,7 @@ class MaxPool(Node):
             raw, sc, sh, arelu = x.affine_src
             self.x_raw, self.in_affine = raw, (sc, sh, arelu)
             if g.math == "f16x2" and self.out.dtype == torch.float32:
-                self.am_out = g.new_scalar()
+                self.am_out = g.mag.new()
                 self.out.am_slot = self.am_out
         # one byte per output element: which window position held the maximum (read by backward
         # instead of x and y)
@@ -1867,11 +1755,8 @@ class MaxPool(Node):
 
     def forward(self):
         if self.in_affine is not None:
-            am = self._g.scalar(self.am_out)
             fn.maxpool_forward(self.x_raw.data, self.k, self.s, self.p, out=self.out.data, argmax=self.argmax,
-                               in_affine=self.in_affine, out_absmax=am)
-            if am is not None:
-                self._g._am_done.add(self.am_out)
+                               in_affine=self.in_affine, out_absmax=self._g.mag.claim(self.am_out))
             return
         fn.maxpool_forward(self.x.data, self.k, self.s, self.p, out=self.out.data, argmax=self.argmax)
 

@@ -134,7 +134,7 @@ def gradient_planes(g, index):
             continue
         n.dx_planes = True
         n.x_ext = fn.zeros(2, x.shape[3], device=g.device)
-        n.am_dyin = g.new_scalar(backward=True)
+        n.am_dyin = g.mag.new(backward=True)
 
 
 def shortcut_compaction(g, index):

@@ -67,7 +67,7 @@ for n in net.g.nodes:
         bn_bwd = bn_dya = None
         if bn is not None and bn.bwd_sums is not None and n.math == "f16x2":
             bn_bwd = (bn.x.data, bn.scale, bn.shift, bn.mean, bn.rstd, bn.relu, bn.bwd_sums[0])
-            bn_dya = net.g.scalar(bn.am_dyin) if getattr(bn, "dx_planes", False) else None
+            bn_dya = net.g.mag.block(bn.am_dyin) if getattr(bn, "dx_planes", False) else None
             fused_d = 1
         # the projection units (graph_plan.shortcut_compaction), as the graph calls them: the shortcut's data gradient is the
         # stride-1 call on the subsampled grid into the compact buffer ("c"), conv1's adds that buffer at the even positions ("a")
