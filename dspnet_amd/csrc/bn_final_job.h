@@ -6,7 +6,7 @@
 // A BnFinalJob is THE description of a finalize: every BatchNorm backward entry point of nn.hip fills one (bn_final_job) and
 // either launches bn_bwd_final_kernel from it (bn_final_launch) or parks it.  dspn_bn_backward_from_sums with
 // DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_PARKED launches tile_group_kernel<1> where the table is long (>= 1024 row tiles: that
-// level needs hundreds of workgroups and stays a launch) and parks the job for the rest (bn_job_defer); conv2d_wgrad_one takes it
+// level needs hundreds of workgroups and stays a launch) and parks the job for the rest (bn_job_defer); launch_wgrad_plan (conv.hip) takes it
 // (bn_job_take) and adds rows of workgroups IN FRONT of its grid (blockIdx.y < job_rows: dispatched first) that run
 // bn_final_job_run -- sixteen channels per workgroup, beside the weight gradient's own workgroups; the apply half
 // (DSPN_BN_SUMS_APPLY_ONLY) is launched behind that kernel by stream order.  If no weight gradient came by, the apply call launches

@@ -28,6 +28,7 @@
 #include "dspn_store.h"
 #include "dspn_pieces.h"
 #include "conv_geom.h"
+#include <climits>
 #include <cstdlib>
 #include "../../include/dspn_nn.h"
 
@@ -2046,7 +2047,40 @@ int dispatch_nt(const st_t *in, const st_t *w, const float *bias, st_t *out, con
   return launch_nt_plan(p, in, w, bias, out, g, s, ws, residual);
 }
 
-struct WgradPlan { int bm; int bn; int splits; int pps; };
+// The weight gradient's host path: wgrad_shape -> wgrad_plan (pure: every figure of the launch) -> launch_wgrad_plan (decides nothing)
+// What the plan reads of a geometry -- THE place (N, Ho, Wo, Cin, Cout, R, S, stride) becomes these: P output pixels (the GEMM's
+// k), Cout x J outputs, and x_bytes: the bytes of x that the P pixels touch, for a layer whose taps re-read them (one tap: 0, no
+// bound; taps_reread: as if they did whatever R x S is -- the workspace query)
+struct WgradShape {
+  long long P; int Cout, J; long long x_bytes;
+  bool empty() const { return P <= 0 || J <= 0 || Cout <= 0; }
+  size_t slab_bytes() const { return sizeof(float) * (size_t)Cout * J; }
+};
+WgradShape wgrad_shape(int N, int Ho, int Wo, int Cin, int Cout, int R, int S, int stride, bool taps_reread = false) {
+  const long long P = (long long)N * Ho * Wo;
+  return WgradShape{P, Cout, R * S * Cin, R * S > 1 || taps_reread ? 4ll * P * Cin * std::min(stride, 2) * std::min(stride, 2) : 0};
+}
+// ... of the operands: the math mode (DSPN_MATH_*), which of them are fp16 piece planes, whether x goes through an input affine
+struct WgradOperands { int math = DSPN_MATH_FP32; bool dy_planes = false, x_planes = false, in_affine = false; };
+// ... and of the process -- THE place the weight gradient's knobs are read: DSPN_WG_TILE (experiments: 0 32x128, 1 64x128, 2 128x64,
+// else 128x128) and DSPN_WG_SPLITS (experiments) on every call; wide: conv_wgw_kernel where it applies, that is unless DSPN_WGW=0
+// (read once per process) or dspn_conv_set_wide_tiles(1) (tests, same-box A/B)
+struct WgradKnobs { long long tile = LLONG_MIN, splits = LLONG_MIN; bool wide = true; };      // LLONG_MIN: not set
+WgradKnobs wgrad_knobs() {
+  static const bool wgw_env = dspn::env_int("DSPN_WGW", 1) != 0;
+  return WgradKnobs{dspn::env_int("DSPN_WG_TILE", LLONG_MIN), dspn::env_int("DSPN_WG_SPLITS", LLONG_MIN), wgw_env && dspn::wide_tiles_mode() != 1};
+}
+// the family's members: conv_wgrad_kernel on four tiles (128 x 128 on eight waves), conv_wgw_kernel (conv_wgrad_wide.h)
+enum class WgradMember { T32x128, T64x128, T128x64, T128x128W8, Wide128x128 };
+// bm x bn tiles, kt over Cout and jt over J; `splits` slabs of pps pixels each; conv_wgrad_kernel's MODE and INTF; the launch's LDS bytes
+struct WgradPlan { int bm, bn, kt, jt, splits, pps; WgradMember member; int mode; bool in_affine; size_t lds; };
+// MODE: the math (0 fp32 MFMA .. 3 two-piece), or the two-piece math with fp16 piece planes of dy (4), of x (5: never behind an
+// input affine, wgrad_check), of both (6)
+int wgrad_mode(const WgradOperands &o) {
+  if (kHalf) return 1;
+  if (o.math != DSPN_MATH_F32_F16X2) return o.math;
+  return (o.x_planes ? 5 : 3) + (o.dy_planes ? 1 : 0);
+}
 // pixels per split are a multiple of this in BOTH builds (the float build steps 32 pixels per k-step, the bf16 build 64):
 // dspn_conv2d_wgrad_splits() -- exported once -- must size the slab buffers of either
 constexpr int kPlanPK = 64;
@@ -2056,29 +2090,31 @@ static_assert(kPlanPK % kPK == 0, "split sizes must be whole k-steps");
 // holds at once, set by LDS per workgroup), each costs its pixels plus a fixed prologue/epilogue, and
 // every split adds one slab to write and re-read.  (A plain "about 1024 workgroups" rule lands just
 // past a round boundary for the 3x3 layers: 36 tiles x 29 splits = 1044 = 2.04 rounds.)
-// x_bytes of wgrad_plan: the bytes of x that P output pixels touch, for a layer whose taps re-read them (one tap: 0, no bound)
-long long wgrad_x_footprint(long long P, int Cin, int taps, int stride) { return taps > 1 ? 4ll * P * Cin * std::min(stride, 2) * std::min(stride, 2) : 0; }
-WgradPlan wgrad_plan(long long P, int Cout, int J, long long x_bytes = 0, long long max_splits = 1 << 30) {
+// A function of its arguments alone: it launches nothing and reads no environment.  max_splits: what the caller's slab workspace
+// holds (a batch chunk of a >= 2 GiB tensor can want more slabs than the plan of the whole batch that sized the workspace): the
+// plan never has more, so its slabs always fit.
+WgradPlan wgrad_plan(const WgradShape &sh, const WgradOperands &o, const WgradKnobs &knobs, long long max_splits = 1 << 30) {
+  const auto [P, Cout, J, x_bytes] = sh;
   WgradPlan p;
   p.bm = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128);
   if (p.bm == 128 && (Cout + 63) / 64 * 64 < (Cout + 127) / 128 * 128) p.bm = 64;   // less row padding
   // J = taps x channels <= 64 (the 1x1 convolutions on 64 channels of stage 1): a 128-wide column tile would be
   // half padding
   p.bn = (J <= 64 && p.bm == 128) ? 64 : 128;   // (64 x 64 tiles measured slower than 64 x 128 for Cout <= 64)
-  if (const char *e = getenv("DSPN_WG_TILE")) {   // experiments: 0 32x128, 1 64x128, 2 128x64, 3 128x128
-    const int t = atoi(e);
-    p.bm = t == 0 ? 32 : (t == 1 ? 64 : 128);
-    p.bn = t == 2 ? 64 : 128;
+  if (knobs.tile != LLONG_MIN) {
+    p.bm = knobs.tile == 0 ? 32 : (knobs.tile == 1 ? 64 : 128);
+    p.bn = knobs.tile == 2 ? 64 : 128;
   }
-  const long long tiles = (long long)((Cout + p.bm - 1) / p.bm) * ((J + p.bn - 1) / p.bn);
+  p.kt = (Cout + p.bm - 1) / p.bm; p.jt = (J + p.bn - 1) / p.bn;
+  const long long tiles = (long long)p.kt * p.jt;
+  // the cost model's LDS figure: the FLOAT build's formula in BOTH builds, another quantity than p.lds below -- the split count
+  // must not depend on the storage type (dspn_conv2d_wgrad_splits, exported once, sizes the slabs of both)
   const long long lds = 4ll * std::max(2 * kPK * (p.bm + p.bn), p.bm * (p.bn + 4));
   const long long slots = 256 * std::min<long long>(8, (160ll << 10) / lds);
   // every tap re-reads the same pixels of x: keep one split's share of x within the Infinity Cache /
   // L2 so that only the first tap's workgroups fetch it from HBM
   long long s_min = 1;
   if (x_bytes > 0) s_min = (x_bytes + (32ll << 20) - 1) / (32ll << 20);
-  // (max_splits: what the caller's slab workspace holds -- a batch chunk of a >= 2 GiB tensor can want more slabs than the
-  // plan of the whole batch that sized the workspace)
   const long long s_max = std::max<long long>(1, std::min<long long>(std::min<long long>(P / 128, 1024), max_splits));
   s_min = std::min(s_min, s_max);
   const double flop_per_pix = 2.0 * p.bm * p.bn, slot_rate = 120e12 / (double)slots, ovh_pix = 160;
@@ -2093,65 +2129,71 @@ WgradPlan wgrad_plan(long long P, int Cout, int J, long long x_bytes = 0, long l
     if (t < best * 0.999) { best = t; splits = sp; }
     if (tiles * sp > 8 * slots) break;
   }
-  if (const char *e = getenv("DSPN_WG_SPLITS")) splits = std::max<long long>(1, std::min<long long>(atoll(e), s_max));   // experiments
+  if (knobs.splits != LLONG_MIN) splits = std::max<long long>(1, std::min<long long>(knobs.splits, s_max));
   splits = std::min(splits, s_max);
   long long pps = ((P + splits - 1) / splits + kPlanPK - 1) / kPlanPK * kPlanPK;
-  p.splits = (int)((P + pps - 1) / pps);
-  p.pps = (int)pps;
+  p.splits = (int)((P + pps - 1) / pps); p.pps = (int)pps;
+  p.mode = wgrad_mode(o); p.in_affine = o.in_affine;
+  // round 6: both operands as piece planes on a 128 x 128 tile -- global -> LDS directly, 64 x 64 per wave (conv_wgrad_wide.h);
+  // same split plan, same slabs, same bits
+  // (eight waves on 128 x 256 with a three-slot ring measured no faster where the plan fills the chip -- stages 3 and 4: 0.37 - 0.39
+  // of 833.3 either way -- and 1.5 x slower where it does not; profiles/r06_wgrad_wide_tile.txt)
+  p.member = p.mode == 6 && p.bm == 128 && p.bn == 128 && knobs.wide ? WgradMember::Wide128x128
+             : p.bm == 32 ? WgradMember::T32x128
+             : p.bm == 64 ? WgradMember::T64x128
+             : p.bn == 64 ? WgradMember::T128x64
+                          : WgradMember::T128x128W8;
+  // mainloop buffers | staged output tile
+  // (the float build sizes for its largest mode: float images 2 * kPK * (BM + BN) * 4 B; the three-piece bf16 image of the
+  // split mode, single-buffered, 3 * kPK * row bytes, is smaller than the staged output tile for every tile shape but 32 x 128)
+  const size_t tile_out = sizeof(float) * p.bm * (p.bn + 4);
+  p.lds = p.member == WgradMember::Wide128x128 ? std::max<size_t>(2 * (size_t)kPK * (128 + 128) * 4, tile_out)
+          : kHalf ? std::max<size_t>(2 * (size_t)kPK * (wg_row_bytes(p.bm) + wg_row_bytes(p.bn)), tile_out)
+                  : std::max<size_t>(std::max<size_t>(sizeof(float) * 2 * kPK * (p.bm + p.bn), tile_out),
+                                     3 * (size_t)kPK * (wg_row_bytes(p.bm) + wg_row_bytes(p.bn)));
   return p;
 }
 
 // one weight-gradient launch: the slab grid (kt x jt tiles, one row per split) and, in front of it, the rows of a parked
 // BatchNorm-backward finalize
-struct WgradLaunch { const st_t *x, *dy; float *slab; const WgradGeom &g; int kt, jt, rows; size_t lds; hipStream_t s; };
-// MODE: the math (0 fp32 MFMA .. 3 two-piece), 4 = two-piece with dy as piece planes, 5 = x, 6 = both; INTF: the input affine
-template <int WM, int WN, int TM, int TN, int MODE, bool INTF>
-int launch_wgrad_impl(const WgradLaunch &a) {
-  auto kern = conv_wgrad_kernel<WM, WN, TM, TN, MODE, INTF>;
-  static dspn::KernelDeviceState st;
-  if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), a.lds, st, "conv_wgrad"); dev < 0) return dev;
-  hipLaunchKernelGGL(kern, dim3(a.kt * a.jt, a.rows), dim3(WM * WN * 64), a.lds, a.s, a.x, a.dy, a.slab, a.g, a.kt, a.jt);
+struct WgradLaunch { const WgradPlan &p; const st_t *x, *dy; float *slab; const WgradGeom &g; hipStream_t s; };
+int launch_wgrad_kernel(void (*kern)(const st_t *, const st_t *, float *, const WgradGeom, int, int), int threads, dspn::KernelDeviceState &st,
+                        const char *what, const WgradLaunch &a) {
+  if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), a.p.lds, st, what); dev < 0) return dev;
+  hipLaunchKernelGGL(kern, dim3(a.p.kt * a.p.jt, a.p.splits + a.g.job_rows), dim3(threads), a.p.lds, a.s, a.x, a.dy, a.slab, a.g, a.p.kt, a.p.jt);
   return 0;
 }
-template <int WM, int WN, int TM, int TN, int MODE>
-int launch_wgrad_mode(const WgradLaunch &a) {
-  return a.g.in_scale ? launch_wgrad_impl<WM, WN, TM, TN, MODE, true>(a) : launch_wgrad_impl<WM, WN, TM, TN, MODE, false>(a);
+template <int WM, int WN, int TM, int TN, int MODE, bool INTF>
+int launch_wgrad_impl(const WgradLaunch &a) {
+  static dspn::KernelDeviceState st;
+  return launch_wgrad_kernel(conv_wgrad_kernel<WM, WN, TM, TN, MODE, INTF>, WM * WN * 64, st, "conv_wgrad", a);
 }
+// a tile's kernel for the plan's mode and input-affine flag (piece planes of x go with no affine)
 template <int WM, int WN, int TM, int TN>
 int launch_wgrad_tile(const WgradLaunch &a) {
-  // the math, or the two-piece math with fp16 piece planes of dy (4), of x (5: never behind an input affine, the entries check), of both (6)
-  switch (kHalf ? 1 : a.g.bf16 != 3 ? a.g.bf16 : a.g.x_planes ? 5 + a.g.dy_planes : 3 + a.g.dy_planes) {
+#define DSPN_WGRAD_MODE(M) \
+  case M: return a.p.in_affine ? launch_wgrad_impl<WM, WN, TM, TN, M, true>(a) : launch_wgrad_impl<WM, WN, TM, TN, M, false>(a)
+  switch (a.p.mode) {
 #ifndef DSPN_HALF
     case 6: return launch_wgrad_impl<WM, WN, TM, TN, 6, false>(a);
     case 5: return launch_wgrad_impl<WM, WN, TM, TN, 5, false>(a);
-    case 4: return launch_wgrad_mode<WM, WN, TM, TN, 4>(a);
-    case 3: return launch_wgrad_mode<WM, WN, TM, TN, 3>(a);
-    case 2: return launch_wgrad_mode<WM, WN, TM, TN, 2>(a);
-    case 0: return launch_wgrad_mode<WM, WN, TM, TN, 0>(a);
+    DSPN_WGRAD_MODE(4);
+    DSPN_WGRAD_MODE(3);
+    DSPN_WGRAD_MODE(2);
+    DSPN_WGRAD_MODE(0);
 #endif
-    default: return launch_wgrad_mode<WM, WN, TM, TN, 1>(a);
+    DSPN_WGRAD_MODE(1);
   }
+#undef DSPN_WGRAD_MODE
+  return dspn::fail(DSPN_ERR_ARG_, "conv2d_wgrad: no kernel for mode %d", a.p.mode);
 }
-static int launch_wgrad(int BM, int BN, const WgradLaunch &a) {
+int launch_wgrad_wide(const WgradLaunch &a) {
 #ifndef DSPN_HALF
-  // round 6: both operands as piece planes on a 128 x 128 tile -- global -> LDS directly, 64 x 64 per wave (conv_wgrad_wide.h);
-  // same split plan, same slabs, same bits.  dspn_conv_set_wide_tiles(1) / DSPN_WGW=0: conv_wgrad_kernel (tests, same-box A/B)
-  static const bool wgw_env = dspn::env_int("DSPN_WGW", 1) != 0;
-  // (eight waves on 128 x 256 with a three-slot ring measured no faster where the plan fills the chip -- stages 3 and 4: 0.37 - 0.39
-  // of 833.3 either way -- and 1.5 x slower where it does not; profiles/r06_wgrad_wide_tile.txt)
-  if (a.g.bf16 == 3 && a.g.x_planes && a.g.dy_planes && BM == 128 && BN == 128 && wgw_env && dspn::wide_tiles_mode() != 1) {
-    auto kern = conv_wgw_kernel<2, 2, 2>;
-    const size_t lds_w = std::max<size_t>(2 * (size_t)kPK * (128 + 128) * 4, sizeof(float) * 128 * (128 + 4));
-    static dspn::KernelDeviceState st;
-    if (const int dev = dspn::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_w, st, "conv_wgrad (wide)"); dev < 0) return dev;
-    hipLaunchKernelGGL(kern, dim3(a.kt * a.jt, a.rows), dim3(256), lds_w, a.s, a.x, a.dy, a.slab, a.g, a.kt, a.jt);
-    return 0;
-  }
+  static dspn::KernelDeviceState st;
+  return launch_wgrad_kernel(conv_wgw_kernel<2, 2, 2>, 256, st, "conv_wgrad (wide)", a);
+#else
+  return dspn::fail(DSPN_ERR_ARG_, "conv2d_wgrad: the bfloat16 build has no wide member");
 #endif
-  if (BM == 32) return launch_wgrad_tile<1, 4, 1, 1>(a);                     // 32 x 128
-  if (BM == 64) return launch_wgrad_tile<2, 2, 1, 2>(a);                     // 64 x 128
-  if (BN == 64) return launch_wgrad_tile<2, 2, 2, 1>(a);                     // 128 x 64
-  return launch_wgrad_tile<4, 2, 1, 2>(a);   // 128 x 128 on 8 waves: two workgroups = 4 waves per SIMD (+3..6 % over <2,2,2,2>)
 }
 
 }  // namespace
@@ -2671,117 +2713,139 @@ int DSPN_FN(dspn_conv2d_input_sum_grad)(const st_t *dy, const float *w, float *o
 
 #ifndef DSPN_HALF
 size_t dspn_conv2d_wgrad_workspace_bytes(int N, int Ho, int Wo, int Cin, int Cout, int R, int S) {
-  const long long P = (long long)N * Ho * Wo;
-  const int J = R * S * Cin;
-  if (P <= 0 || J <= 0 || Cout <= 0) return 0;
-  // the plan depends on (P, Cout, J) and on the stride (1 or 2) through the x footprint: sized for either, and for every
-  // layer as if its taps re-read x
-  size_t m = (size_t)wgrad_plan(P, Cout, J).splits;
+  WgradShape flat = wgrad_shape(N, Ho, Wo, Cin, Cout, R, S, 1);
+  if (flat.empty()) return 0;
+  flat.x_bytes = 0;
+  // the plan depends on (P, Cout, J) and on the stride (1 or 2) through the x footprint: sized for no footprint, for either
+  // stride, and for every layer as if its taps re-read x
+  const WgradKnobs knobs = wgrad_knobs();
+  size_t m = (size_t)wgrad_plan(flat, WgradOperands{}, knobs).splits;
   for (int stride = 1; stride <= 2; ++stride)
-    m = std::max(m, (size_t)wgrad_plan(P, Cout, J, wgrad_x_footprint(P, Cin, std::max(R * S, 2), stride)).splits);
-  return sizeof(float) * m * Cout * J;
+    m = std::max(m, (size_t)wgrad_plan(wgrad_shape(N, Ho, Wo, Cin, Cout, R, S, stride, true), WgradOperands{}, knobs).splits);
+  return m * flat.slab_bytes();
+}
+/* number of split-K slabs ([splits][Cout][R*S*Cin] floats) the weight gradient of this geometry produces */
+int dspn_conv2d_wgrad_splits(int N, int Ho, int Wo, int Cin, int Cout, int R, int S, int stride) {
+  const WgradShape sh = wgrad_shape(N, Ho, Wo, Cin, Cout, R, S, stride);
+  return sh.empty() ? 0 : wgrad_plan(sh, WgradOperands{}, wgrad_knobs()).splits;
 }
 #endif
+}  // extern "C"
 
-static int conv2d_wgrad_one(int math, OpScales scales, const st_t *x, InAffine tf, const st_t *dy, float *dw, int N, int H, int W, int Cin,
-                          int Cout, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
-                          int Wo, int accumulate, void *workspace, size_t workspace_bytes,
-                          void *stream) {
-  DSPN_REQUIRE(x && dy && workspace, "conv2d_wgrad: null pointer");   // dw == NULL: leave the partial slabs in workspace
-  DSPN_REQUIRE(Cin % kEPC == 0 && ldy % kEPC == 0, "conv2d_wgrad: channel strides must be multiples of %d", kEPC);
+// One call of a dspn_conv2d_wgrad* entry, filled there by field name
+struct WgradCall {
+  const st_t *x; const float *in_scale, *in_shift; int in_relu; const st_t *dy;
+  int N, H, W, Cin, Cout, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo;
+  int math;                                     // the entry's argument; wgrad_check leaves the mode (split_math) here ...
+  const float *x_absmax, *dy_absmax;
+  void *stream;
+  int accumulate;
+  float *slabs; size_t slabs_bytes;             // the split-K partial sums: the workspace of the _bn entry, the output of the _slabs entry
+  float *dw;                                    // NULL: the slabs stay (no reduce)
+  bool one_launch;                              // the _slabs entry: the whole batch in one launch, or none
+  int dy_planes, x_planes;                      // ... and DSPN_MATH_DY_PLANES / DSPN_MATH_X_PLANES here
+  long long x_image_bytes() const { return (long long)sizeof(st_t) * H * W * Cin; }
+  long long dy_image_bytes() const { return (long long)sizeof(st_t) * Ho * Wo * ldy; }
+  int chunk() const { return std::min(batch_chunk(N, x_image_bytes()), batch_chunk(N, dy_image_bytes())); }      // images per launch: x and dy below 2 GiB
+  WgradShape shape() const { return wgrad_shape(N, Ho, Wo, Cin, Cout, R, S, stride); }
+  WgradOperands operands() const { return WgradOperands{math, dy_planes != 0, x_planes != 0, in_scale != nullptr}; }
+};
+// every check of a weight gradient that precedes its launches, each rule once; decodes c.math
+static int wgrad_check(WgradCall &c) {
+  DSPN_REQUIRE(c.N > 0 && c.H > 0 && c.W > 0 && c.Cin > 0 && c.Ho > 0 && c.Wo > 0 && c.ldy > 0 && c.Cout > 0 && c.R > 0 && c.S > 0 &&
+                   c.stride > 0 && c.dil > 0,
+               "conv2d_wgrad: bad geometry");      // (nothing below divides by zero)
+  DSPN_REQUIRE((c.in_scale == nullptr) == (c.in_shift == nullptr), "conv2d_wgrad: in_scale and in_shift go together");
+  const int flags = split_math(&c.math, DSPN_MATH_DY_PLANES | DSPN_MATH_X_PLANES);
+  c.dy_planes = (flags & DSPN_MATH_DY_PLANES) ? 1 : 0;
+  c.x_planes = (flags & DSPN_MATH_X_PLANES) ? 1 : 0;
+  DSPN_REQUIRE(!c.dy_planes || (!dspn::kHalf && c.math == DSPN_MATH_F32_F16X2 && c.ldy == c.Cout && c.Cout % 32 == 0 && c.dy_absmax),
+               "conv2d_wgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy == Cout, Cout %% 32 == 0 and the block the planes were cut by (dy_absmax)");
+  DSPN_REQUIRE(!c.x_planes || (!dspn::kHalf && c.math == DSPN_MATH_F32_F16X2 && c.Cin % 32 == 0 && c.x_absmax && !c.in_scale),
+               "conv2d_wgrad: DSPN_MATH_X_PLANES needs DSPN_MATH_F32_F16X2, Cin %% 32 == 0, no input affine and the block the planes were cut by (x_absmax)");
+  if (const int rc = check_math_mode("conv2d_wgrad", c.math)) return rc;
+  if (const int rc = check_math_blocks("conv2d_wgrad", c.math, flags, c.x_absmax, c.dy_absmax)) return rc;
+  const int nb = c.chunk();
+  DSPN_REQUIRE(!c.one_launch || nb == c.N, "conv2d_wgrad_slabs: tensors of 2 GiB or more need dspn_conv2d_wgrad_f32");
+  DSPN_REQUIRE(c.x && c.dy && c.slabs, "conv2d_wgrad: null pointer");
+  DSPN_REQUIRE(c.Cin % kEPC == 0 && c.ldy % kEPC == 0, "conv2d_wgrad: channel strides must be multiples of %d", kEPC);
+  // (32-bit buffer offsets: a chunk is one image at the least)
+  DSPN_REQUIRE(nb * c.x_image_bytes() < (1ll << 31) && nb * c.dy_image_bytes() < (1ll << 31),
+               "conv2d_wgrad: tensors of 2 GiB or more are not supported");
+  // (with one slab the call is taken: wgrad_plan makes do with the slabs there are)
+  if (c.slabs_bytes < c.shape().slab_bytes())
+    return dspn::fail(DSPN_ERR_WORKSPACE_, "conv2d_wgrad: workspace %zu < %zu (one slab)", c.slabs_bytes, c.shape().slab_bytes());
+  return 0;
+}
+// The launch's geometry -- THE place a WgradCall and its plan become a WgradGeom
+static WgradGeom wgrad_geom(const WgradCall &c, const WgradPlan &p) {
   WgradGeom g;
-  g.N = N; g.Hin = H; g.Win = W; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.ldy = ldy;
-  g.sh = stride; g.sw = stride; g.ph = pad_h; g.pw = pad_w; g.dh = dil; g.dw = dil; g.R = R; g.S = S;
-  g.in_scale = tf.scale; g.in_shift = tf.shift; g.in_relu = tf.relu;
-  g.bf16 = kHalf ? 1 : math;
-  g.dy_absmax = scales.a; g.x_absmax = scales.b;
-  g.dy_planes = scales.a_planes & 1; g.x_planes = (scales.a_planes >> 1) & 1;
-  {
-    const long long xb = (long long)sizeof(st_t) * N * H * W * Cin, yb = (long long)sizeof(st_t) * N * Ho * Wo * ldy;
-    if (xb >= (1ll << 31) || yb >= (1ll << 31))
-      return dspn::fail(DSPN_ERR_ARG_, "conv2d_wgrad: tensors of 2 GiB or more are not supported");
-    g.x_bytes = (unsigned)xb; g.dy_bytes = (unsigned)yb;
-  }
-  const long long P = (long long)N * Ho * Wo;
-  const int J = R * S * Cin;
-  const long long ws_splits = (long long)(workspace_bytes / (sizeof(float) * (size_t)Cout * J));
-  if (ws_splits < 1)
-    return dspn::fail(DSPN_ERR_WORKSPACE_, "conv2d_wgrad: workspace %zu < %zu (one slab)", workspace_bytes, sizeof(float) * (size_t)Cout * J);
-  const WgradPlan plan = wgrad_plan(P, Cout, J, wgrad_x_footprint(P, Cin, R * S, stride), ws_splits);
-  const int BM = plan.bm, BN = plan.bn;
-  const int kt = (Cout + BM - 1) / BM, jt = (J + BN - 1) / BN;
-  const long long splits = plan.splits;
-  g.pix_per_split = plan.pps;
-  const size_t need = sizeof(float) * (size_t)splits * Cout * J;
-  if (workspace_bytes < need)
-    return dspn::fail(DSPN_ERR_WORKSPACE_, "conv2d_wgrad: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t s = (hipStream_t)stream;
-  float *slab = static_cast<float *>(workspace);
-  // round 6: a parked BatchNorm-backward finalize of this stream rides in front of the grid (bn_final_job.h)
-  g.job = dspn::BnFinalJob{};
-  g.job_rows = dspn::bn_job_take(s, &g.job) ? (g.job.blocks + kt * jt - 1) / (kt * jt) : 0;
-  // mainloop buffers | staged output tile
-  // (the float build sizes for its largest mode: float images 2 * kPK * (BM + BN) * 4 B; the three-piece bf16 image of the
-  // split mode, single-buffered, 3 * kPK * row bytes, is smaller than the staged output tile for every tile shape but 32 x 128)
-  const size_t lds = kHalf ? std::max<size_t>(2 * (size_t)kPK * (wg_row_bytes(BM) + wg_row_bytes(BN)), sizeof(float) * BM * (BN + 4))
-                           : std::max<size_t>(sizeof(float) * std::max(2 * kPK * (BM + BN), BM * (BN + 4)),
-                                              3 * (size_t)kPK * (wg_row_bytes(BM) + wg_row_bytes(BN)));
+  g.N = c.N; g.Hin = c.H; g.Win = c.W; g.Cin = c.Cin; g.Ho = c.Ho; g.Wo = c.Wo; g.Cout = c.Cout; g.ldy = c.ldy;
+  g.sh = c.stride; g.sw = c.stride; g.ph = c.pad_h; g.pw = c.pad_w; g.dh = c.dil; g.dw = c.dil; g.R = c.R; g.S = c.S;
+  g.pix_per_split = p.pps;
+  g.x_bytes = (unsigned)(c.N * c.x_image_bytes()); g.dy_bytes = (unsigned)(c.N * c.dy_image_bytes());
+  g.in_scale = c.in_scale; g.in_shift = c.in_shift; g.in_relu = c.in_relu;
+  g.bf16 = kHalf ? 1 : c.math;
+  g.dy_absmax = c.dy_absmax; g.x_absmax = c.x_absmax;
+  g.dy_planes = c.dy_planes; g.x_planes = c.x_planes;
+  g.job_rows = 0; g.job = dspn::BnFinalJob{};
+  return g;
+}
+// The launch the plan names, for a checked call of one chunk: it decides nothing.  Then, with c.dw, the sum of the slabs.
+static int launch_wgrad_plan(const WgradPlan &p, const WgradCall &c) {
+  hipStream_t s = (hipStream_t)c.stream;
+  WgradGeom g = wgrad_geom(c, p);
+  // round 6: a parked BatchNorm-backward finalize of this stream rides in front of the grid (bn_final_job.h) -- taken here,
+  // after the last check: a refused call leaves it parked
+  if (dspn::bn_job_take(s, &g.job)) g.job_rows = (g.job.blocks + p.kt * p.jt - 1) / (p.kt * p.jt);
   dspn::ProfScope prof(1, s);
-  if (const int rc = launch_wgrad(BM, BN, WgradLaunch{x, dy, slab, g, kt, jt, (int)splits + g.job_rows, lds, s})) return rc;
-  int rc = dspn::check_launch("conv_wgrad");
-  if (rc || !dw) return rc;
-  const long long n4 = (long long)Cout * J / 4;
+  const WgradLaunch a{p, c.x, c.dy, c.slabs, g, s};
+  int rc = 0;
+  switch (p.member) {
+    case WgradMember::T32x128: rc = launch_wgrad_tile<1, 4, 1, 1>(a); break;
+    case WgradMember::T64x128: rc = launch_wgrad_tile<2, 2, 1, 2>(a); break;
+    case WgradMember::T128x64: rc = launch_wgrad_tile<2, 2, 2, 1>(a); break;
+    case WgradMember::T128x128W8: rc = launch_wgrad_tile<4, 2, 1, 2>(a); break;   // two workgroups = 4 waves per SIMD (+3..6 % over <2,2,2,2>)
+    case WgradMember::Wide128x128: rc = launch_wgrad_wide(a); break;
+  }
+  if (rc) return rc;
+  rc = dspn::check_launch("conv_wgrad");
+  if (rc || !c.dw) return rc;
+  const long long n4 = (long long)c.Cout * c.shape().J / 4;
   const int blocks = (int)std::min<long long>((n4 + 255) / 256, 2048);
   hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, s,
-                     reinterpret_cast<const float4 *>(slab), reinterpret_cast<float4 *>(dw), n4,
-                     (int)splits, accumulate);
+                     reinterpret_cast<const float4 *>(c.slabs), reinterpret_cast<float4 *>(c.dw), n4, p.splits, c.accumulate);
   return dspn::check_launch("conv_wgrad_reduce");
 }
-
-// the argument checks of the weight-gradient entries; *math: the argument, then its mode; *planes: bit 0 dy, bit 1 x as piece planes
-static int wgrad_check(int *math, int *planes, int N, int H, int W, int Cin, int Cout, int ldy, int Ho, int Wo, const float *in_scale,
-                       const float *in_shift, const float *x_absmax, const float *dy_absmax) {
-  DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && ldy > 0, "conv2d_wgrad: bad geometry");
-  DSPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv2d_wgrad: in_scale and in_shift go together");
-  const int flags = split_math(math, DSPN_MATH_DY_PLANES | DSPN_MATH_X_PLANES);
-  *planes = ((flags & DSPN_MATH_DY_PLANES) ? 1 : 0) | ((flags & DSPN_MATH_X_PLANES) ? 2 : 0);
-  DSPN_REQUIRE(!(*planes & 1) || (!dspn::kHalf && *math == DSPN_MATH_F32_F16X2 && ldy == Cout && Cout % 32 == 0 && dy_absmax),
-               "conv2d_wgrad: DSPN_MATH_DY_PLANES needs DSPN_MATH_F32_F16X2, ldy == Cout, Cout %% 32 == 0 and the block the planes were cut by (dy_absmax)");
-  DSPN_REQUIRE(!(*planes & 2) || (!dspn::kHalf && *math == DSPN_MATH_F32_F16X2 && Cin % 32 == 0 && x_absmax && !in_scale),
-               "conv2d_wgrad: DSPN_MATH_X_PLANES needs DSPN_MATH_F32_F16X2, Cin %% 32 == 0, no input affine and the block the planes were cut by (x_absmax)");
-  if (const int rc = check_math_mode("conv2d_wgrad", *math)) return rc;
-  return check_math_blocks("conv2d_wgrad", *math, flags, x_absmax, dy_absmax);
+// the checks, then the launches in chunks of the batch that keep x and dy below 2 GiB (chunks after the first add to dw)
+static int conv2d_wgrad_impl(WgradCall c) {
+  if (const int rc = wgrad_check(c)) return rc;
+  const long long max_splits = (long long)(c.slabs_bytes / c.shape().slab_bytes());
+  const WgradKnobs knobs = wgrad_knobs();
+  for (int n0 = 0, nb = c.chunk(), N = c.N; n0 < N; n0 += nb) {
+    c.N = std::min(nb, N - n0);
+    if (const int rc = launch_wgrad_plan(wgrad_plan(c.shape(), c.operands(), knobs, max_splits), c)) return rc;
+    c.x += c.N * (c.x_image_bytes() / (long long)sizeof(st_t));
+    c.dy += c.N * (c.dy_image_bytes() / (long long)sizeof(st_t));
+    c.accumulate = 1;
+  }
+  return 0;
 }
-
+// what the two entries share (include/dspn_nn.h)
+#define DSPN_WGRAD_FIELDS                                                                                                       \
+  .x = x, .in_scale = in_scale, .in_shift = in_shift, .in_relu = in_relu, .dy = dy, .N = N, .H = H, .W = W, .Cin = Cin, .Cout = Cout, \
+  .ldy = ldy, .R = R, .S = S, .stride = stride, .pad_h = pad_h, .pad_w = pad_w, .dil = dil, .Ho = Ho, .Wo = Wo, .math = math,   \
+  .x_absmax = x_absmax, .dy_absmax = dy_absmax, .stream = stream
+extern "C" {
 int DSPN_FN(dspn_conv2d_wgrad_bn)(const st_t *x, const float *in_scale, const float *in_shift, int in_relu,
                              const st_t *dy, float *dw, int N, int H, int W, int Cin,
                              int Cout, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                              int Wo, int accumulate, int math, const float *x_absmax, const float *dy_absmax,
                              void *workspace, size_t workspace_bytes, void *stream) {
-  int planes = 0;
-  if (const int rc = wgrad_check(&math, &planes, N, H, W, Cin, Cout, ldy, Ho, Wo, in_scale, in_shift, x_absmax, dy_absmax)) return rc;
-  const int nb = std::min(batch_chunk(N, (long long)sizeof(st_t) * H * W * Cin),
-                          batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy));
-  for (int n0 = 0; n0 < N; n0 += nb) {
-    const int n = std::min(nb, N - n0);
-    const int rc = conv2d_wgrad_one(math, OpScales{dy_absmax, x_absmax, planes}, x + (long long)n0 * H * W * Cin, InAffine{in_scale, in_shift, in_relu},
-                                    dy + (long long)n0 * Ho * Wo * ldy, dw, n, H, W,
-                                    Cin, Cout, ldy, R, S, stride, pad_h, pad_w, dil, Ho, Wo, accumulate || n0 > 0,
-                                    workspace, workspace_bytes, stream);
-    if (rc) return rc;
-  }
-  return 0;
+  // (dw == NULL: the partial slabs stay in workspace)
+  return conv2d_wgrad_impl(WgradCall{DSPN_WGRAD_FIELDS, .accumulate = accumulate, .slabs = static_cast<float *>(workspace),
+                                     .slabs_bytes = workspace_bytes, .dw = dw, .one_launch = false});
 }
-
-#ifndef DSPN_HALF
-/* number of split-K slabs ([splits][Cout][R*S*Cin] floats) the weight gradient of this geometry produces */
-int dspn_conv2d_wgrad_splits(int N, int Ho, int Wo, int Cin, int Cout, int R, int S, int stride) {
-  const long long P = (long long)N * Ho * Wo;
-  const int J = R * S * Cin;
-  if (P <= 0 || J <= 0 || Cout <= 0) return 0;
-  return wgrad_plan(P, Cout, J, wgrad_x_footprint(P, Cin, R * S, stride)).splits;
-}
-#endif
 
 /* the weight-gradient GEMM alone: the split-K partial sums stay in `slabs` (dspn_conv2d_wgrad_splits() x Cout x
  * R*S*Cin floats) for a later dspn_conv2d_slab_reduce_batch_f32 */
@@ -2789,14 +2853,10 @@ int DSPN_FN(dspn_conv2d_wgrad_slabs)(const st_t *x, const float *in_scale, const
                                 const st_t *dy, float *slabs, size_t slabs_bytes, int N, int H, int W, int Cin,
                                 int Cout, int ldy, int R, int S, int stride, int pad_h, int pad_w, int dil, int Ho,
                                 int Wo, int math, const float *x_absmax, const float *dy_absmax, void *stream) {
-  int planes = 0;
-  if (const int rc = wgrad_check(&math, &planes, N, H, W, Cin, Cout, ldy, Ho, Wo, in_scale, in_shift, x_absmax, dy_absmax)) return rc;
-  DSPN_REQUIRE(std::min(batch_chunk(N, (long long)sizeof(st_t) * H * W * Cin),
-                        batch_chunk(N, (long long)sizeof(st_t) * Ho * Wo * ldy)) == N,
-               "conv2d_wgrad_slabs: tensors of 2 GiB or more need dspn_conv2d_wgrad_f32");
-  return conv2d_wgrad_one(math, OpScales{dy_absmax, x_absmax, planes}, x, InAffine{in_scale, in_shift, in_relu}, dy, nullptr, N, H, W, Cin, Cout, ldy, R, S, stride,
-                          pad_h, pad_w, dil, Ho, Wo, 0, slabs, slabs_bytes, stream);
+  return conv2d_wgrad_impl(WgradCall{DSPN_WGRAD_FIELDS, .accumulate = 0, .slabs = slabs, .slabs_bytes = slabs_bytes, .dw = nullptr,
+                                     .one_launch = true});
 }
+#undef DSPN_WGRAD_FIELDS
 
 #ifndef DSPN_HALF
 /* table: n rows of 40 bytes in DEVICE memory, { const float *slabs; float *dw; int64 n4 (= Cout*R*S*Cin/4);

@@ -1427,35 +1427,28 @@ class Conv(Node):
         return w
 
     def _weight_gradient(self, dy, planes, xa, dya):
+        # each case chooses its operands once -- x, dy, the weight's shape, (stride, pad, dil) and what else the call names
+        wshape, geom = self.w.shape, (self.stride, self.pad, self.dil)
         if self.tap_expand:
             cout, kh, kw, cin = self.w.shape
             fn.tap_spread(dy, cout, kh, kw, self.pad, out=self.z)
             # (the weight gradient multiplies the SPREAD gradient z: its magnitude is taken on the fly, these are small layers)
-            if self.slabs is not None:
-                fn.conv2d_wgrad_slabs(self.x.data, self.z, (cout * kh * kw, 1, 1, cin), self.slabs, 1, 0, 1, math=self.math,
-                                      x_absmax=xa)
-            else:
-                fn.conv2d_wgrad(self.x.data, self.z, (cout * kh * kw, 1, 1, cin), 1, 0, 1,
-                                out=self.w.grad.view(cout * kh * kw, 1, 1, cin), math=self.math, x_absmax=xa)
+            x, dy, wshape, geom = self.x.data, self.z, (cout * kh * kw, 1, 1, cin), (1, 0, 1)
+            how = dict(math=self.math, x_absmax=xa)
         elif self.guard_fb:
             assert not planes, "a convolution on the guard's fallback got its gradient as piece planes"
-            if self.slabs is not None:
-                fn.conv2d_wgrad_slabs(self.x_raw.data, dy, self.w.shape, self.slabs, self.stride, self.pad, self.dil,
-                                      in_affine=self.in_affine, math="bf16x3")
-            else:
-                fn.conv2d_wgrad(self.x_raw.data, dy, self.w.shape, self.stride, self.pad, self.dil, out=self.w.grad,
-                                in_affine=self.in_affine, math="bf16x3")
+            x, how = self.x_raw.data, dict(in_affine=self.in_affine, math="bf16x3")
             self._g.guard_count_call()
-        elif self.slabs is not None:
-            xp = self._x_planes()
-            fn.conv2d_wgrad_slabs(self.x_raw.data if xp is None else xp, dy, self.w.shape, self.slabs, self.stride, self.pad,
-                                  self.dil, in_affine=self.in_affine if xp is None else None, math=self.math, x_absmax=xa,
-                                  dy_absmax=dya, dy_planes=planes, x_planes=xp is not None)
         else:
             xp = self._x_planes()
-            fn.conv2d_wgrad(self.x_raw.data if xp is None else xp, dy, self.w.shape, self.stride, self.pad, self.dil,
-                            out=self.w.grad, in_affine=self.in_affine if xp is None else None, math=self.math, x_absmax=xa,
-                            dy_absmax=dya, dy_planes=planes, x_planes=xp is not None)
+            x = self.x_raw.data if xp is None else xp
+            how = dict(in_affine=self.in_affine if xp is None else None, math=self.math, x_absmax=xa, dy_absmax=dya,
+                       dy_planes=planes, x_planes=xp is not None)
+        # ... and one site leaves the split-K slabs for the batched reduce, or writes the gradient
+        if self.slabs is not None:
+            fn.conv2d_wgrad_slabs(x, dy, wshape, self.slabs, *geom, **how)
+        else:
+            fn.conv2d_wgrad(x, dy, wshape, *geom, out=self.w.grad.view(wshape), **how)
         self.slabs_fresh = self.slabs is not None
 
     def _data_gradient(self, dy, planes, dya, wa):

@@ -5,6 +5,7 @@ torch's current stream.  Activations are NHWC float32 with a physical channel
 count that is a multiple of 4; conv weights are [Cout, R, S, Cin]."""
 import ctypes
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -661,10 +662,24 @@ def conv2d_dgrad(dy, wt, x_shape, stride=1, pad=0, dil=1, out=None, accumulate=F
     return out
 
 
-def _wgrad_absmax(x, dy, in_affine, math, x_absmax, dy_absmax):
-    if math == 3 and x.dtype == torch.float32:      # (piece-plane gradients always come with their block: conv2d_wgrad's assert)
-        return (absmax(x, in_affine) if x_absmax is None else x_absmax, absmax(dy) if dy_absmax is None else dy_absmax)
-    return None, None
+def _wgrad_operands(x, dy, w_shape, stride, pad, dil, in_affine, math, x_absmax, dy_absmax, dy_planes, x_planes):
+    """what conv2d_wgrad and conv2d_wgrad_slabs decode alike, as the named pieces of their C entries' argument lists (which order
+    them differently): x with its affine, the geometry, the math word with its magnitude blocks"""
+    N, H, W, Cin = x.shape
+    Cout, R, S, Cw = w_shape
+    assert Cw == Cin
+    sc, sh, arelu = in_affine if in_affine is not None else (None, None, False)
+    assert x.dtype == dy.dtype
+    math = _math_code(math)
+    assert not x_planes or (x_absmax is not None and in_affine is None)
+    if math == 3 and x.dtype == torch.float32:      # (piece-plane gradients always come with their block: the assert above)
+        x_absmax, dy_absmax = absmax(x, in_affine) if x_absmax is None else x_absmax, absmax(dy) if dy_absmax is None else dy_absmax
+    else:
+        x_absmax = dy_absmax = None
+    return SimpleNamespace(
+        x=(ptr(x), ptr(sc), ptr(sh), int(arelu)),
+        geometry=(N, H, W, Cin, Cout, dy.shape[3], R, S, stride, *_hw(pad), dil, dy.shape[1], dy.shape[2]),
+        math=(math | (MATH_DY_PLANES if dy_planes else 0) | (MATH_X_PLANES if x_planes else 0), ptr(x_absmax), ptr(dy_absmax)))
 
 
 def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, dil=1, out=None, accumulate=False, in_affine=None, math=None,
@@ -672,23 +687,14 @@ def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, dil=1, out=None, accumulate=Fa
     """x (N,H,W,Cin), dy (N,Ho,Wo,ldy) -> dw (Cout,R,S,Cin); in_affine as in conv2d_forward; x_planes / dy_planes: the
     operand is fp16 piece planes cut by its magnitude block ("f16x2")"""
     N, H, W, Cin = x.shape
-    Cout, R, S, Cw = w_shape
-    assert Cw == Cin
-    Ho, Wo, ldy = dy.shape[1], dy.shape[2], dy.shape[3]
+    Cout, R, S, _ = w_shape
     if out is None:
         out = empty(Cout, R, S, Cin, device=x.device)
-    nbytes = L().dspn_conv2d_wgrad_workspace_bytes(N, Ho, Wo, Cin, Cout, R, S)
-    ws = workspace(nbytes, x.device, "wgrad")
-    ph, pw = _hw(pad)
-    sc, sh, arelu = in_affine if in_affine is not None else (None, None, False)
-    assert x.dtype == dy.dtype and out.dtype == torch.float32
-    math = _math_code(math)
-    assert not x_planes or (x_absmax is not None and in_affine is None)
-    x_absmax, dy_absmax = _wgrad_absmax(x, dy, in_affine, math, x_absmax, dy_absmax)
-    check(_f("dspn_conv2d_wgrad_bn", x)(ptr(x), ptr(sc), ptr(sh), int(arelu), ptr(dy), ptr(out), N, H, W, Cin, Cout, ldy,
-                                       R, S, stride, ph, pw, dil, Ho, Wo, int(accumulate),
-                                       math | (MATH_DY_PLANES if dy_planes else 0) | (MATH_X_PLANES if x_planes else 0),
-                                       ptr(x_absmax), ptr(dy_absmax), ptr(ws), ws.numel(), stream()), "conv2d_wgrad")
+    ws = workspace(L().dspn_conv2d_wgrad_workspace_bytes(N, dy.shape[1], dy.shape[2], Cin, Cout, R, S), x.device, "wgrad")
+    assert out.dtype == torch.float32
+    a = _wgrad_operands(x, dy, w_shape, stride, pad, dil, in_affine, math, x_absmax, dy_absmax, dy_planes, x_planes)
+    check(_f("dspn_conv2d_wgrad_bn", x)(*a.x, ptr(dy), ptr(out), *a.geometry, int(accumulate), *a.math,
+                                       ptr(ws), ws.numel(), stream()), "conv2d_wgrad")
     return out
 
 
@@ -721,20 +727,10 @@ def conv2d_wgrad_splits(x_shape, dy_shape, w_shape, stride):
 def conv2d_wgrad_slabs(x, dy, w_shape, slabs, stride=1, pad=0, dil=1, in_affine=None, math=None, x_absmax=None,
                        dy_absmax=None, dy_planes=False, x_planes=False):
     """the weight-gradient GEMM alone: split-K partial sums -> slabs (splits, Cout, R, S, Cin); see slab_reduce_batch"""
-    N, H, W, Cin = x.shape
-    Cout, R, S, Cw = w_shape
-    assert Cw == Cin
-    ph, pw = _hw(pad)
-    sc, sh, arelu = in_affine if in_affine is not None else (None, None, False)
-    assert x.dtype == dy.dtype and slabs.dtype == torch.float32
-    math = _math_code(math)
-    assert not x_planes or (x_absmax is not None and in_affine is None)
-    x_absmax, dy_absmax = _wgrad_absmax(x, dy, in_affine, math, x_absmax, dy_absmax)
-    check(_f("dspn_conv2d_wgrad_slabs", x)(ptr(x), ptr(sc), ptr(sh), int(arelu), ptr(dy), ptr(slabs), slabs.numel() * 4,
-                                          N, H, W, Cin, Cout, dy.shape[3], R, S, stride, ph, pw, dil, dy.shape[1],
-                                          dy.shape[2],
-                                          math | (MATH_DY_PLANES if dy_planes else 0) | (MATH_X_PLANES if x_planes else 0),
-                                          ptr(x_absmax), ptr(dy_absmax), stream()), "conv2d_wgrad_slabs")
+    assert slabs.dtype == torch.float32
+    a = _wgrad_operands(x, dy, w_shape, stride, pad, dil, in_affine, math, x_absmax, dy_absmax, dy_planes, x_planes)
+    check(_f("dspn_conv2d_wgrad_slabs", x)(*a.x, ptr(dy), ptr(slabs), slabs.numel() * 4, *a.geometry, *a.math,
+                                          stream()), "conv2d_wgrad_slabs")
 
 
 def slab_reduce_table(entries, device):

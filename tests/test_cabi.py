@@ -212,6 +212,38 @@ def test_data_gradient_host_verdicts_are_pinned():
         assert gen.refused_call(lib, row["entry"], row["args"]) == row["results"], (row["entry"], row["args"])
 
 
+def test_weight_gradient_host_verdicts_are_pinned(monkeypatch):
+    """tests/golden/wgrad_host_verdicts.json: the host path of the weight gradient refuses as it did when the fixture was written --
+    return value and full text of the calls that dspn_conv2d_wgrad_bn_f32 / _bf16, dspn_conv2d_wgrad_slabs_f32 / _bf16 and
+    dspn_conv2d_wgrad_f32 refuse, competing reasons in their order -- and refuses a Cout, R, S, stride or dil of 0 as bad geometry
+    (new_refusals: asserted directly, the fixture's first library divided by zero on them).  The calls carry stand-in pointers,
+    so they are replayed only where no GPU is visible (tests/test_conv_edges_gpu.py refuses with real tensors there)."""
+    import importlib.util
+    import json
+    import torch
+    for knob in ("DSPN_WG_TILE", "DSPN_WG_SPLITS"):           # read on every call
+        monkeypatch.delenv(knob, raising=False)
+    golden = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_wgrad_host_verdicts_golden", os.path.join(golden, "make_wgrad_host_verdicts_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "wgrad_host_verdicts.json")) as f:
+        doc = json.load(f)
+    lib = _lib.lib()
+    assert len(doc["refused"]) >= 60 and [(r["entry"], r["args"]) for r in doc["refused"]] == gen.refused_cases()
+    assert all(r["results"][0] in (-1, -2) for r in doc["refused"]), "every pinned call is one the host path refuses"
+    assert [(r["entry"], r["args"]) for r in doc["new_refusals"]] == gen.new_refusals()
+    zero = lambda kw: any(kw.get(k) == 0 for k in ("Cout", "R", "S", "stride", "dil"))  # noqa: E731
+    assert all(zero(kw) for _, kw in gen.new_refusals()) and not any(zero(r["args"]) for r in doc["refused"])
+    if torch.cuda.is_available():
+        return
+    for row in doc["refused"]:
+        assert gen.refused_call(lib, row["entry"], row["args"]) == row["results"], (row["entry"], row["args"])
+    for entry, kw in gen.new_refusals():
+        rc, text = gen.refused_call(lib, entry, kw)
+        assert rc == -1 and "bad geometry" in text, (entry, kw, rc, text)
+
+
 def test_oracle_is_clean_under_address_and_ub_sanitizers():
     """SURVEY.md section 5 (sanitizers on the host build): the C oracle's three operators over exactly-sized heap buffers and the
     degenerate inputs of the GPU tests, built with -fsanitize=address,undefined (oracle/sanitize_driver.c)"""

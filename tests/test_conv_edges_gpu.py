@@ -906,6 +906,31 @@ def test_wgrad_general_values_within_the_bar(gpu_device, case):
     f.done()
 
 
+def test_wgrad_refuses_empty_weights_and_leaves_nothing_behind(gpu_device):
+    """A weight gradient with Cout, R or S of 0 is refused on the host as bad geometry, before any launch (the slab count used to be
+    workspace_bytes / (4 Cout R S Cin): a division by zero) -- real tensors, both float entries.  The ordinary call of the same
+    shape that follows is bit-exact as ever (class A), in the one-call form and as slabs + reduce: the refused calls wrote
+    nothing, parked nothing and left no error behind."""
+    case = (1, 8, 8, 64, 64, 3, 1, 1, 1)
+    p, f = problem(case, "A"), Failures()
+    x, dy, _, _, _ = wgrad_operands(p, "fp32", False)
+    assert x.shape == (1, 8, 8, 64) and dy.shape == (1, 8, 8, 64)
+    lib = fn.L()
+    out = torch.full((64, 3, 3, 64), SENTINEL, device="cuda")
+    ws = fn.workspace(lib.dspn_conv2d_wgrad_workspace_bytes(1, 8, 8, 64, 64, 3, 3), x.device, "wgrad")
+    for Cout, kh, kw in ((0, 3, 3), (64, 0, 3), (64, 3, 0)):
+        geom = (1, 8, 8, 64, Cout, 64, kh, kw, 1, 1, 1, 1, 8, 8)
+        rc = lib.dspn_conv2d_wgrad_bn_f32(fn.ptr(x), None, None, 0, fn.ptr(dy), fn.ptr(out), *geom, 0, 0, None, None,
+                                          fn.ptr(ws), ws.numel(), fn.stream())
+        assert rc == -1 and b"bad geometry" in lib.dspn_last_error(), (geom, rc, lib.dspn_last_error())
+        rc = lib.dspn_conv2d_wgrad_slabs_f32(fn.ptr(x), None, None, 0, fn.ptr(dy), fn.ptr(out), out.numel() * 4, *geom, 0, None, None,
+                                             fn.stream())
+        assert rc == -1 and b"bad geometry" in lib.dspn_last_error(), (geom, rc, lib.dspn_last_error())
+    assert bool((out == SENTINEL).all()), "a refused call wrote"
+    wgrad_check(f, p, ("fp32",), "class A, after refused calls", slabs=True)
+    f.done()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # section 5: launch settings that must not change results
 @pytest.fixture
