@@ -5,6 +5,8 @@ translation) or its plain resize.
 Division of labour (MI355X-first):
   host   record lookup, JPEG / PNG decode (Pillow, a small thread pool: the decoders release the GIL), the box
          arithmetic of `_get_augmented` / `_get_resized` (a few dozen boxes per image), the random draws;
+         with device_jpeg=True only the serial half of the JPEG decode (markers, Huffman) stays here and the
+         coefficients are uploaded instead of pixels (dataset/jpeg.py, include/dspn_jpeg.h);
   device ONE upload of the decoded uint8 pixels of the whole batch and ONE launch pair (dspn_augment_batch_u8,
          include/dspn_augment.h) that does warpAffine (bilinear, OpenCV's fixed point) + flip + BGR->RGB planes + mean
          subtraction for the images and nearest warp + flip + /4 resize + LUT for the label maps.  The reference runs
@@ -26,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import jpeg
 from . import recordio
 
 # dspn_warp_sample (include/dspn_augment.h)
@@ -130,17 +133,31 @@ class _Decoded(object):
         self.size = (a.shape[1], a.shape[0])
 
 
+class _Coded(object):
+    """a JPEG payload the device will reconstruct: the probed header, with the `size` _prepare reads from a PIL image"""
+
+    def __init__(self, payload, info):
+        self.payload, self.info = payload, info
+        self.size = (int(info["width"]), int(info["height"]))
+
+
 class DataBatch(object):
     def __init__(self, data, label):
         self.data, self.label = data, label
 
 
 class MultiTaskRecordIter(object):
-    """see the module docstring; constructor arguments as in the reference (unused ones accepted and ignored)"""
+    """see the module docstring; constructor arguments as in the reference (unused ones accepted and ignored).
+    device_jpeg=True: baseline JPEG records are Huffman-decoded on the host and reconstructed on the device in front of
+    the augmentation (same pixels as Pillow's, byte for byte); any other record takes the Pillow path, counted in
+    `jpeg_fallbacks` (records of delivered batches since construction)."""
 
     def __init__(self, path_imgrec, batch_size, data_shape, path_imglist="", label_width=-1, label_pad_width=-1,
                  label_pad_value=-1, resize_mode="force", mean_pixels=(123.68, 116.779, 103.939), enable_aug=True,
-                 device=None, decode_threads=8, prefetch=True, cache_decoded=False, **kwargs):
+                 device=None, decode_threads=8, prefetch=True, cache_decoded=False, device_jpeg=False, **kwargs):
+        if device_jpeg and cache_decoded:
+            raise ValueError("device_jpeg=True with cache_decoded=True: the cache exists to avoid the host decode that "
+                             "device_jpeg removes; choose one")
         path_imgidx = path_imgrec.replace(".rec", ".idx")
         path_imglst = path_imgrec.replace(".rec", ".lst")
         self.device = device or torch.device("cuda", torch.cuda.current_device())
@@ -180,10 +197,12 @@ class MultiTaskRecordIter(object):
         # cache_decoded: keep the decoded uint8 pixels of every record in host memory (Cityscapes train: 2975 x 8.4 MB =
         # 25 GB); from the second epoch on the host phase is a memcpy instead of a JPEG + PNG decode
         self._cache = {} if cache_decoded else None
+        self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
         self._get_batch()
         if not self.provide_label:
             raise RuntimeError("Invalid ImageDetRecordIter: " + path_imgrec)
         self.reset()
+        self.jpeg_fallbacks = 0                                # the batch above was not delivered
 
     # ---- epoch control (:401-434) -------------------------------------------------------------------------------
     def reset(self):
@@ -231,7 +250,13 @@ class MultiTaskRecordIter(object):
         hit = self._cache.get(header.id) if self._cache is not None else None
         if hit is not None:
             return hdr, _Decoded(hit[0]), (None if hit[1] is None else _Decoded(hit[1])), seg_path, header.id
-        im = Image.open(io.BytesIO(payload))
+        im = None
+        if self.device_jpeg:                                   # sizes from the markers; no pixel is decoded here
+            rc, info = jpeg.probe_info(payload)
+            if rc == 0 and info["supported"]:
+                im = _Coded(payload, info)
+        if im is None:
+            im = Image.open(io.BytesIO(payload))
         seg_im = Image.open(seg_path) if os.path.exists(seg_path) else None
         if self.enable_aug:
             assert seg_im is not None, seg_path + " not found."
@@ -248,13 +273,37 @@ class MultiTaskRecordIter(object):
             if seg_im is not None:
                 seg_dst[...] = seg_im.a
             return True
-        img_dst[...] = np.asarray(im if im.mode == "RGB" else im.convert("RGB"))   # the kernel's channel map is the identity
+        if im is not None:                                     # None: the device reconstructs this image (device_jpeg)
+            img_dst[...] = np.asarray(im if im.mode == "RGB" else im.convert("RGB"))   # the kernel's channel map is the identity
         if seg_im is not None:
             a = np.asarray(seg_im if seg_im.mode in ("L", "P") else seg_im.convert("L"))
             seg_dst[...] = a
         if self._cache is not None:
             self._cache[rec_id] = (img_dst.copy(), None if seg_im is None else seg_dst.copy())
         return True
+
+    def _decode_coded(self, args):
+        """device_jpeg: entropy-decode one record into its slice of the pinned coefficient pool (worker thread; ctypes
+        releases the GIL).  -> False when the record took the Pillow path into the image pool instead (it was not
+        probed as supported, or its scan turned out corrupt)"""
+        im, seg_im, img_dst, seg_dst, rec_id, coef_dst = args
+        coded = isinstance(im, _Coded)
+        if coded and jpeg.entropy_decode(im.payload, im.info, coef_dst) != 0:
+            import io
+            from PIL import Image
+            coded, im = False, Image.open(io.BytesIO(im.payload))
+        self._decode_into((None if coded else im, seg_im, img_dst, seg_dst, rec_id))
+        return coded
+
+    def _coef_pool_set(self, k, count):
+        """pinned int16 coefficient buffers, alternated like the two byte pools (call after _pool_set(k, ...), which
+        has waited for the upload that last read set k)"""
+        if not hasattr(self, "_coef_pools"):
+            self._coef_pools = [None, None]
+        cur = self._coef_pools[k]
+        if cur is None or cur.numel() < count:
+            cur = self._coef_pools[k] = torch.empty(max(count, 64), dtype=torch.int16).pin_memory()
+        return cur
 
     def _pool_set(self, k, img_bytes, seg_bytes):
         """pinned staging buffers, two sets used alternately, grown on demand; a set is rewritten only after the
@@ -283,6 +332,10 @@ class MultiTaskRecordIter(object):
         samples = np.zeros(B, _SAMPLE)
         jobs, fnames = [], []
         io_ = so = 0
+        if self.device_jpeg:
+            coef_sizes = [int(im.info["coef_count"]) if isinstance(im, _Coded) else 0 for _, im, _, _, _ in peeked]
+            cp = self._coef_pool_set(serial % 2, sum(coef_sizes))
+            cnp, co, jsamples = cp.numpy(), 0, np.zeros(B, jpeg.SAMPLE)
         for b, (hdr, im, seg_im, seg_path, rec_id) in enumerate(peeked):
             ww, hh = im.size
             slot = start + b
@@ -304,10 +357,20 @@ class MultiTaskRecordIter(object):
             s["minv"] = invert_affine(M)
             jobs.append((im, seg_im, ip[io_:io_ + img_sizes[b]].reshape(hh, ww, 3),
                          sp[so:so + seg_sizes[b]].reshape(hh, ww) if seg_im is not None else None, rec_id))
+            if self.device_jpeg:
+                if isinstance(im, _Coded):
+                    jpeg.fill_sample(jsamples[b], im.info, co, io_)
+                jobs[-1] = jobs[-1] + (cnp[co:co + coef_sizes[b]],)
+                co += coef_sizes[b]
             io_ += img_sizes[b]
             so += seg_sizes[b]
             label[b, 3:3 + hdr.shape[0]] = hdr
             fnames.append(seg_path)
+        if self.device_jpeg:
+            coded = list(self._pool.map(self._decode_coded, jobs))
+            jsamples["skip"] = [0 if c else 1 for c in coded]
+            return {"pool": pool, "img_bytes": io_, "seg_bytes": so, "samples": samples, "label": label, "fnames": fnames,
+                    "start": start, "jpeg": {"pool": cp, "count": co, "samples": jsamples, "fallbacks": coded.count(False)}}
         list(self._pool.map(self._decode_into, jobs))
         return {"pool": pool, "img_bytes": io_, "seg_bytes": so, "samples": samples, "label": label, "fnames": fnames,
                 "start": start}
@@ -316,11 +379,23 @@ class MultiTaskRecordIter(object):
         B, (C, H, W) = self.batch_size, self.data_shape
         dev = self.device
         pool = prep["pool"]
-        img_dev = pool[0][:max(prep["img_bytes"], 1)].to(dev, non_blocking=True)
+        if self.device_jpeg:                                   # coefficients up; pixels only where Pillow decoded some
+            jp = prep["jpeg"]
+            coef_dev = jp["pool"][:max(jp["count"], 64)].to(dev, non_blocking=True)
+            img_dev = torch.empty(max(prep["img_bytes"], 1), dtype=torch.uint8, device=dev)
+            if jp["fallbacks"]:
+                img_dev.copy_(pool[0][:max(prep["img_bytes"], 1)], non_blocking=True)
+            self.jpeg_fallbacks += jp["fallbacks"]
+        else:
+            img_dev = pool[0][:max(prep["img_bytes"], 1)].to(dev, non_blocking=True)
         seg_dev = pool[1][:max(prep["seg_bytes"], 1)].to(dev, non_blocking=True)
         pool[2] = torch.cuda.Event()
         pool[2].record(torch.cuda.current_stream(dev))
         desc_dev = torch.from_numpy(prep["samples"].view(np.uint8).reshape(-1)).to(dev)
+        jpeg_keep = ()
+        if self.device_jpeg and jp["fallbacks"] < B:           # the pixels of the coded records, in front of the warp
+            jdesc_dev = torch.from_numpy(jp["samples"].view(np.uint8).reshape(-1)).to(dev)
+            jpeg_keep = (coef_dev, jdesc_dev, jpeg.reconstruct(coef_dev, jdesc_dev, img_dev))
         data = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
         seg_out = torch.empty(B, H // 4, W // 4, dtype=torch.float32, device=dev)
         _lib.check(_entry()(img_dev.data_ptr(), seg_dev.data_ptr(), desc_dev.data_ptr(), B, H, W, _CMAP_RGB,
@@ -342,7 +417,7 @@ class MultiTaskRecordIter(object):
         det_dev = torch.from_numpy(det.astype(np.float32)).to(dev)
         self._batch = DataBatch(data=[data], label=[det_dev, seg_out])
         self._fnames = prep["fnames"]
-        self._keepalive = (img_dev, seg_dev, desc_dev)          # until the next batch replaces them
+        self._keepalive = (img_dev, seg_dev, desc_dev) + jpeg_keep   # until the next batch replaces them
 
     def _drop_ahead(self):
         fut, self._ahead = getattr(self, "_ahead", None), None

@@ -2,7 +2,8 @@
  * dspn_augment.h -- C ABI of the per-batch image pipeline of liangfu/dspnet's MultiTaskRecordIter
  * (dataset/iterator.py:301-603): what `_get_augmented` / `_get_resized` (:412-548)
  * and the tail of `_get_batch` (:568-576) do to the decoded image and its segmentation map, fused into one launch per
- * batch on the device.  Decoding (JPEG / PNG) and the box arithmetic stay on the host.
+ * batch on the device.  PNG decoding and the box arithmetic stay on the host; of JPEG decoding only the entropy pass
+ * does: dspn_jpeg.h reconstructs the pixels on the device, straight into the `images` pool read here.
  *
  * Per sample the reference runs (OpenCV, third-party, version unpinned):
  *     img = cv2.warpAffine(img, M, (W, H), INTER_LINEAR,  borderValue = 128 (augmented) | 0 (resized))
