@@ -7,6 +7,8 @@ Division of labour (MI355X-first):
          arithmetic of `_get_augmented` / `_get_resized` (a few dozen boxes per image), the random draws;
          with device_jpeg=True only the serial half of the JPEG decode (markers, Huffman) stays here and the
          coefficients are uploaded instead of pixels (dataset/jpeg.py, include/dspn_jpeg.h);
+         with device_png=True only the inflate of the label map stays here and the still filtered rows are uploaded
+         (dataset/png.py, include/dspn_png.h);
   device ONE upload of the decoded uint8 pixels of the whole batch and ONE launch pair (dspn_augment_batch_u8,
          include/dspn_augment.h) that does warpAffine (bilinear, OpenCV's fixed point) + flip + BGR->RGB planes + mean
          subtraction for the images and nearest warp + flip + /4 resize + LUT for the label maps.  The reference runs
@@ -29,6 +31,7 @@ import torch
 
 from .. import _lib
 from . import jpeg
+from . import png
 from . import recordio
 
 # dspn_warp_sample (include/dspn_augment.h)
@@ -141,6 +144,14 @@ class _Coded(object):
         self.size = (int(info["width"]), int(info["height"]))
 
 
+class _CodedLabel(object):
+    """a label-map PNG the device will unfilter: the probed chunk list, with the `size` _prepare reads from a PIL image"""
+
+    def __init__(self, payload, info):
+        self.payload, self.info = payload, info
+        self.size = (info["width"], info["height"])
+
+
 class DataBatch(object):
     def __init__(self, data, label):
         self.data, self.label = data, label
@@ -150,14 +161,20 @@ class MultiTaskRecordIter(object):
     """see the module docstring; constructor arguments as in the reference (unused ones accepted and ignored).
     device_jpeg=True: baseline JPEG records are Huffman-decoded on the host and reconstructed on the device in front of
     the augmentation (same pixels as Pillow's, byte for byte); any other record takes the Pillow path, counted in
-    `jpeg_fallbacks` (records of delivered batches since construction)."""
+    `jpeg_fallbacks` (records of delivered batches since construction).
+    device_png=True: 8-bit greyscale / palette label maps are inflated on the host and unfiltered on the device in front of
+    the augmentation (same bytes as Pillow's); any other label map takes the Pillow path, counted in `png_fallbacks`."""
 
     def __init__(self, path_imgrec, batch_size, data_shape, path_imglist="", label_width=-1, label_pad_width=-1,
                  label_pad_value=-1, resize_mode="force", mean_pixels=(123.68, 116.779, 103.939), enable_aug=True,
-                 device=None, decode_threads=8, prefetch=True, cache_decoded=False, device_jpeg=False, **kwargs):
+                 device=None, decode_threads=8, prefetch=True, cache_decoded=False, device_jpeg=False, device_png=False,
+                 **kwargs):
         if device_jpeg and cache_decoded:
             raise ValueError("device_jpeg=True with cache_decoded=True: the cache exists to avoid the host decode that "
                              "device_jpeg removes; choose one")
+        if device_png and cache_decoded:
+            raise ValueError("device_png=True with cache_decoded=True: the cache exists to avoid the host decode that "
+                             "device_png removes; choose one")
         path_imgidx = path_imgrec.replace(".rec", ".idx")
         path_imglst = path_imgrec.replace(".rec", ".lst")
         self.device = device or torch.device("cuda", torch.cuda.current_device())
@@ -198,11 +215,12 @@ class MultiTaskRecordIter(object):
         # 25 GB); from the second epoch on the host phase is a memcpy instead of a JPEG + PNG decode
         self._cache = {} if cache_decoded else None
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
+        self.device_png, self.png_fallbacks = bool(device_png), 0
         self._get_batch()
         if not self.provide_label:
             raise RuntimeError("Invalid ImageDetRecordIter: " + path_imgrec)
         self.reset()
-        self.jpeg_fallbacks = 0                                # the batch above was not delivered
+        self.jpeg_fallbacks = self.png_fallbacks = 0           # the batch above was not delivered
 
     # ---- epoch control (:401-434) -------------------------------------------------------------------------------
     def reset(self):
@@ -257,7 +275,18 @@ class MultiTaskRecordIter(object):
                 im = _Coded(payload, info)
         if im is None:
             im = Image.open(io.BytesIO(payload))
-        seg_im = Image.open(seg_path) if os.path.exists(seg_path) else None
+        seg_im = None
+        if self.device_png and os.path.exists(seg_path):       # sizes from IHDR; nothing is inflated here
+            with open(seg_path, "rb") as f:
+                coded = f.read()
+            try:
+                info = png.probe(coded)
+                if info["supported"] and info["bytes_per_pixel"] == 1:
+                    seg_im = _CodedLabel(coded, info)
+            except _lib.DspnError:
+                pass                                           # malformed: Pillow decodes or raises as it always did
+        if seg_im is None:
+            seg_im = Image.open(seg_path) if os.path.exists(seg_path) else None
         if self.enable_aug:
             assert seg_im is not None, seg_path + " not found."
         if seg_im is not None:
@@ -294,6 +323,29 @@ class MultiTaskRecordIter(object):
             coded, im = False, Image.open(io.BytesIO(im.payload))
         self._decode_into((None if coded else im, seg_im, img_dst, seg_dst, rec_id))
         return coded
+
+    def _decode_label(self, args):
+        """device_png: inflate one record's label map into its slice of the pinned raw pool, then run the record's image
+        job (worker thread; zlib releases the GIL).  -> (what the image job said, False when the label map took the Pillow
+        path into the seg byte pool instead: it was not probed as supported, or its data turned out corrupt)"""
+        image_job, job, raw_dst = args
+        seg_im = job[1]
+        coded = isinstance(seg_im, _CodedLabel)
+        if coded and png.inflate_into(seg_im.payload, seg_im.info, raw_dst) != 0:
+            import io
+            from PIL import Image
+            coded, seg_im = False, Image.open(io.BytesIO(seg_im.payload))
+        return image_job(job[:1] + (None if coded else seg_im,) + job[2:]), coded
+
+    def _raw_pool_set(self, k, count):
+        """pinned uint8 buffers for the inflated label rows, alternated like the two byte pools (call after
+        _pool_set(k, ...), which has waited for the upload that last read set k)"""
+        if not hasattr(self, "_raw_pools"):
+            self._raw_pools = [None, None]
+        cur = self._raw_pools[k]
+        if cur is None or cur.numel() < count:
+            cur = self._raw_pools[k] = torch.empty(max(count, 1), dtype=torch.uint8).pin_memory()
+        return cur
 
     def _coef_pool_set(self, k, count):
         """pinned int16 coefficient buffers, alternated like the two byte pools (call after _pool_set(k, ...), which
@@ -336,6 +388,10 @@ class MultiTaskRecordIter(object):
             coef_sizes = [int(im.info["coef_count"]) if isinstance(im, _Coded) else 0 for _, im, _, _, _ in peeked]
             cp = self._coef_pool_set(serial % 2, sum(coef_sizes))
             cnp, co, jsamples = cp.numpy(), 0, np.zeros(B, jpeg.SAMPLE)
+        if self.device_png:
+            raw_sizes = [sm.info["raw_bytes"] if isinstance(sm, _CodedLabel) else 0 for _, _, sm, _, _ in peeked]
+            rp = self._raw_pool_set(serial % 2, sum(raw_sizes))
+            rnp, ro, psamples, raw_dsts = rp.numpy(), 0, np.zeros(B, png.SAMPLE), []
         for b, (hdr, im, seg_im, seg_path, rec_id) in enumerate(peeked):
             ww, hh = im.size
             slot = start + b
@@ -362,18 +418,32 @@ class MultiTaskRecordIter(object):
                     jpeg.fill_sample(jsamples[b], im.info, co, io_)
                 jobs[-1] = jobs[-1] + (cnp[co:co + coef_sizes[b]],)
                 co += coef_sizes[b]
+            if self.device_png:
+                if isinstance(seg_im, _CodedLabel):
+                    png.fill_sample(psamples[b], seg_im.info, ro, so)
+                raw_dsts.append(rnp[ro:ro + raw_sizes[b]])
+                ro += raw_sizes[b]
             io_ += img_sizes[b]
             so += seg_sizes[b]
             label[b, 3:3 + hdr.shape[0]] = hdr
             fnames.append(seg_path)
-        if self.device_jpeg:
-            coded = list(self._pool.map(self._decode_coded, jobs))
-            jsamples["skip"] = [0 if c else 1 for c in coded]
-            return {"pool": pool, "img_bytes": io_, "seg_bytes": so, "samples": samples, "label": label, "fnames": fnames,
-                    "start": start, "jpeg": {"pool": cp, "count": co, "samples": jsamples, "fallbacks": coded.count(False)}}
-        list(self._pool.map(self._decode_into, jobs))
-        return {"pool": pool, "img_bytes": io_, "seg_bytes": so, "samples": samples, "label": label, "fnames": fnames,
+        prep = {"pool": pool, "img_bytes": io_, "seg_bytes": so, "samples": samples, "label": label, "fnames": fnames,
                 "start": start}
+        image_job = self._decode_coded if self.device_jpeg else self._decode_into
+        if self.device_png:
+            done = list(self._pool.map(self._decode_label, [(image_job, job, dst) for job, dst in zip(jobs, raw_dsts)]))
+            coded = [c for c, _ in done]
+            on_device = [d for _, d in done]
+            psamples["skip"] = [0 if d else 1 for d in on_device]
+            labelled = sum(1 for _, _, sm, _, _ in peeked if sm is not None)
+            prep["png"] = {"pool": rp, "count": ro, "samples": psamples, "on_device": on_device.count(True),
+                           "fallbacks": labelled - on_device.count(True)}
+        else:
+            coded = list(self._pool.map(image_job, jobs))
+        if self.device_jpeg:
+            jsamples["skip"] = [0 if c else 1 for c in coded]
+            prep["jpeg"] = {"pool": cp, "count": co, "samples": jsamples, "fallbacks": coded.count(False)}
+        return prep
 
     def _finish(self, prep):
         B, (C, H, W) = self.batch_size, self.data_shape
@@ -388,7 +458,15 @@ class MultiTaskRecordIter(object):
             self.jpeg_fallbacks += jp["fallbacks"]
         else:
             img_dev = pool[0][:max(prep["img_bytes"], 1)].to(dev, non_blocking=True)
-        seg_dev = pool[1][:max(prep["seg_bytes"], 1)].to(dev, non_blocking=True)
+        if self.device_png:                                    # filtered rows up; label bytes only where Pillow decoded some
+            pp = prep["png"]
+            raw_dev = pp["pool"][:max(pp["count"], 1)].to(dev, non_blocking=True)
+            seg_dev = torch.empty(max(prep["seg_bytes"], 1), dtype=torch.uint8, device=dev)
+            if pp["fallbacks"]:
+                seg_dev.copy_(pool[1][:max(prep["seg_bytes"], 1)], non_blocking=True)
+            self.png_fallbacks += pp["fallbacks"]
+        else:
+            seg_dev = pool[1][:max(prep["seg_bytes"], 1)].to(dev, non_blocking=True)
         pool[2] = torch.cuda.Event()
         pool[2].record(torch.cuda.current_stream(dev))
         desc_dev = torch.from_numpy(prep["samples"].view(np.uint8).reshape(-1)).to(dev)
@@ -396,6 +474,11 @@ class MultiTaskRecordIter(object):
         if self.device_jpeg and jp["fallbacks"] < B:           # the pixels of the coded records, in front of the warp
             jdesc_dev = torch.from_numpy(jp["samples"].view(np.uint8).reshape(-1)).to(dev)
             jpeg_keep = (coef_dev, jdesc_dev, jpeg.reconstruct(coef_dev, jdesc_dev, img_dev))
+        png_keep = ()
+        if self.device_png and pp["on_device"]:                # the bytes of the coded label maps, in front of the warp
+            pdesc_dev = torch.from_numpy(pp["samples"].view(np.uint8).reshape(-1)).to(dev)
+            png.unfilter(raw_dev, pdesc_dev, seg_dev)
+            png_keep = (raw_dev, pdesc_dev)
         data = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
         seg_out = torch.empty(B, H // 4, W // 4, dtype=torch.float32, device=dev)
         _lib.check(_entry()(img_dev.data_ptr(), seg_dev.data_ptr(), desc_dev.data_ptr(), B, H, W, _CMAP_RGB,
@@ -417,7 +500,7 @@ class MultiTaskRecordIter(object):
         det_dev = torch.from_numpy(det.astype(np.float32)).to(dev)
         self._batch = DataBatch(data=[data], label=[det_dev, seg_out])
         self._fnames = prep["fnames"]
-        self._keepalive = (img_dev, seg_dev, desc_dev) + jpeg_keep   # until the next batch replaces them
+        self._keepalive = (img_dev, seg_dev, desc_dev) + jpeg_keep + png_keep   # until the next batch replaces them
 
     def _drop_ahead(self):
         fut, self._ahead = getattr(self, "_ahead", None), None

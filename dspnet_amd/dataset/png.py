@@ -1,0 +1,176 @@
+"""PNG decode split between host and device (include/dspn_png.h): the host walks the chunks and inflates the concatenated
+IDAT data (serial work; `zlib` releases the GIL around it, so a thread pool runs it in parallel), the device undoes the
+row filters (Sub / Up / Average / Paeth) for a whole batch in one call.  The samples equal Pillow's byte for byte.
+
+Supported: greyscale 8-bit, palette 8-bit (the indices are the samples: what np.asarray of a mode-"P" image gives) and
+greyscale 16-bit, not interlaced, without tRNS and without animation.
+
+`probe` and `decode_batch` are the public use (ground-truth id maps, instance-id maps, disparity maps held as PNG bytes);
+MultiTaskRecordIter(device_png=True) drives `probe`, `inflate_into` and `unfilter` with its own pinned pools."""
+import ctypes as _c
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+# dspn_png_sample (include/dspn_png.h)
+SAMPLE = np.dtype([("raw_offset", "<i8"), ("out_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
+                   ("bytes_per_pixel", "<i4"), ("skip", "<i4")])
+assert SAMPLE.itemsize == 32
+REASONS = ("ok", "bit depth below 8", "colour type is RGB, RGBA or grey + alpha", "Adam7 interlace", "tRNS chunk",
+           "acTL chunk (APNG)", "not a bit depth / colour type / method of the PNG specification")
+OK, LOW_DEPTH, COLOUR, INTERLACE, TRNS, APNG, NONSTANDARD = range(7)
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_CRITICAL = (b"IHDR", b"PLTE", b"IDAT", b"IEND")
+_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}      # colour type -> legal bit depths
+# inflate_into's statuses
+INFLATE_OK, INFLATE_ZLIB, INFLATE_LENGTH, INFLATE_FILTER = 0, 1, 2, 3
+
+_lib.register({
+    "dspn_png_unfilter_batch": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_longlong,
+                                           _c.c_void_p]),
+})
+
+
+def _malformed(what):
+    return _lib.DspnError("png_probe: " + what)
+
+
+def probe(payload):
+    """what the chunk list says, before any pixel work: a dict with width, height, bit_depth, colour_type, interlace,
+    bytes_per_pixel, row_bytes, raw_bytes (= height * (row_bytes + 1), the inflated size), supported, reason (text),
+    reason_code and idat (the (offset, length) of every IDAT chunk's data, for inflate_into).  The CRC of every critical
+    chunk is checked.  Raises DspnError on a malformed stream: bad signature, bad CRC on a critical chunk, a chunk running
+    past the end, no IHDR / IDAT / IEND, zero width or height."""
+    data = memoryview(payload)
+    n = len(data)
+    if n < 8 or bytes(data[:8]) != SIGNATURE:
+        raise _malformed("bad signature")
+    at, ihdr, idat, flags, ended = 8, None, [], set(), False
+    while not ended:
+        if n - at < 12:
+            raise _malformed("a chunk header runs past the end (no IEND)" if n > at else "no IEND chunk")
+        length, kind = struct.unpack_from(">I4s", data, at)
+        if length > n - at - 12:
+            raise _malformed("chunk %r of %d bytes runs past the end" % (kind, length))
+        body = at + 8
+        if kind in _CRITICAL:
+            (crc,) = struct.unpack_from(">I", data, body + length)
+            if zlib.crc32(data[at + 4:body + length]) != crc:
+                raise _malformed("bad CRC on chunk %r" % kind)
+        if ihdr is None:
+            if kind != b"IHDR" or length != 13:
+                raise _malformed("the first chunk is not a 13-byte IHDR")
+            ihdr = struct.unpack_from(">IIBBBBB", data, body)
+        elif kind == b"IDAT":
+            idat.append((body, length))
+        elif kind == b"IEND":
+            ended = True
+        elif kind in (b"tRNS", b"acTL"):
+            flags.add(kind)
+        at = body + length + 4
+    if not idat:
+        raise _malformed("no IDAT chunk")
+    width, height, depth, colour, compression, filtering, interlace = ihdr
+    if width == 0 or height == 0:
+        raise _malformed("zero width or height")
+    if colour not in _DEPTHS or depth not in _DEPTHS[colour] or compression or filtering or interlace > 1 or \
+            width > 0x7fffffff or height > 0x7fffffff:
+        code = NONSTANDARD
+    elif colour in (2, 4, 6):
+        code = COLOUR
+    elif depth < 8:
+        code = LOW_DEPTH
+    elif interlace:
+        code = INTERLACE
+    elif b"tRNS" in flags:
+        code = TRNS
+    elif b"acTL" in flags:
+        code = APNG
+    else:
+        code = OK
+    bpp = depth // 8 if code == OK else 0
+    return {"width": width, "height": height, "bit_depth": depth, "colour_type": colour, "interlace": interlace,
+            "bytes_per_pixel": bpp, "row_bytes": width * bpp, "raw_bytes": height * (width * bpp + 1) if bpp else 0,
+            "supported": code == OK, "reason": REASONS[code], "reason_code": code, "idat": idat}
+
+
+def inflate_into(payload, info, dst):
+    """inflate the concatenated IDAT data of a probed, supported stream into the uint8 array dst (info["raw_bytes"] bytes);
+    every row keeps its filter-type byte in front.  -> 0, or a non-zero status (never an exception) on a zlib error, an
+    inflated length other than raw_bytes, or a filter type above 4; dst may then hold anything, nothing around it does."""
+    want = info["raw_bytes"]
+    assert info["supported"] and dst.dtype == np.uint8 and dst.ndim == 1 and dst.size == want
+    data = memoryview(payload)
+    spans = info["idat"]
+    stream = data[spans[0][0]:spans[0][0] + spans[0][1]] if len(spans) == 1 else b"".join(data[o:o + n] for o, n in spans)
+    try:
+        z = zlib.decompressobj()
+        raw = z.decompress(stream, want + 1)                     # one byte more than wanted shows a stream that is too long
+    except zlib.error:
+        return INFLATE_ZLIB
+    if len(raw) != want or not z.eof:
+        return INFLATE_LENGTH
+    raw = np.frombuffer(raw, np.uint8)
+    if raw[0::info["row_bytes"] + 1].max() > 4:
+        return INFLATE_FILTER
+    dst[:] = raw
+    return INFLATE_OK
+
+
+def fill_sample(s, info, raw_offset, out_offset, skip=0):
+    """the device descriptor of a probed stream whose inflated rows start at byte raw_offset of the batch's raw pool"""
+    s["raw_offset"], s["out_offset"] = raw_offset, out_offset
+    s["width"], s["height"], s["bytes_per_pixel"], s["skip"] = info["width"], info["height"], info["bytes_per_pixel"], skip
+
+
+def unfilter(raw_dev, samples_dev, out_dev, stream=None):
+    """dspn_png_unfilter_batch: raw_dev the uint8 device pool of inflated rows, samples_dev a uint8 device tensor of
+    descriptors, out_dev the uint8 device pool the samples go to"""
+    dev = raw_dev.device
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().dspn_png_unfilter_batch(raw_dev.data_ptr(), raw_dev.numel(), samples_dev.data_ptr(),
+                                                  samples_dev.numel() // SAMPLE.itemsize, out_dev.data_ptr(),
+                                                  out_dev.numel(), st), "png_unfilter")
+
+
+def decode_batch(payloads, device):
+    """decode a list of PNG byte strings -> list of (h, w) tensors on `device`, torch.uint8 for the 8-bit formats and
+    torch.uint16 (native byte order) for 16-bit greyscale, views of one pool.  ValueError (naming the reason) for a stream
+    outside the supported set, DspnError for a malformed one."""
+    infos = []
+    for i, p in enumerate(payloads):
+        try:
+            info = probe(p)
+        except _lib.DspnError as e:
+            raise _lib.DspnError("%s (stream %d)" % (e, i)) from None
+        if not info["supported"]:
+            raise ValueError("stream %d is not decodable on the device: %s" % (i, info["reason"]))
+        infos.append(info)
+    if not infos:
+        return []
+    raw = torch.empty(sum(i["raw_bytes"] for i in infos), dtype=torch.uint8).pin_memory()
+    rnp = raw.numpy()
+    samples = np.zeros(len(infos), SAMPLE)
+    ro = oo = 0
+    for k, (p, info) in enumerate(zip(payloads, infos)):
+        status = inflate_into(p, info, rnp[ro:ro + info["raw_bytes"]])
+        if status:
+            raise _lib.DspnError("png_inflate (stream %d): %s" % (k, ("", "zlib error", "inflated length is not height * "
+                                 "(row_bytes + 1)", "filter type above 4")[status]))
+        fill_sample(samples[k], info, ro, oo)
+        ro += info["raw_bytes"]
+        oo += -(-info["height"] * info["row_bytes"] // 16) * 16   # every image 16-byte aligned in the pool
+    pool = torch.empty(oo, dtype=torch.uint8, device=device)
+    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1)).to(device)
+    unfilter(raw.to(device), desc, pool)
+    torch.cuda.current_stream(device).synchronize()             # the pinned buffer goes out of scope here
+    out = []
+    for s, info in zip(samples, infos):
+        h, w, o = info["height"], info["width"], int(s["out_offset"])
+        img = pool[o:o + h * info["row_bytes"]]
+        out.append((img.view(torch.uint16) if info["bytes_per_pixel"] == 2 else img).view(h, w))
+    return out
