@@ -32,6 +32,13 @@ _lib.register({
     "dspn_jpeg_reconstruct_workspace_bytes": (_c.c_size_t, [_c.c_longlong]),
     "dspn_jpeg_reconstruct_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p,
                                                   _c.c_longlong, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    # include/dspn_jpeg_encode.h (dataset/jpeg_encode.py is its front end)
+    "dspn_jpeg_quant_tables": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p]),
+    "dspn_jpeg_encode_geometry": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p]),
+    "dspn_jpeg_encode_workspace_bytes": (_c.c_size_t, [_c.c_longlong]),
+    "dspn_jpeg_encode_blocks_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                                    _c.c_longlong, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "dspn_jpeg_entropy_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 })
 
 
