@@ -62,3 +62,14 @@ def box_distances(disparity, boxes_px, device=None):
     table = np.concatenate([np.zeros((len(res), 1), np.int32), res], 1)
     q, _ = fn.box_rank_select(t.detach().to(device).contiguous()[None], torch.from_numpy(table).to(device))
     return [distance_from_median(v) for v in q.cpu().tolist()]
+
+
+def save_maps(paths, maps, compress_level=6):
+    """writes a batch of (hh, ww) uint16 disparity or distance maps (device or host; a (B, hh, ww) tensor or a list) as
+    16-bit greyscale PNG files, the format the dataset keeps them in: one device filter call for the batch (png_encode)"""
+    from ..detect.render import save_pngs
+    maps = list(maps)
+    bad = [tuple(m.shape) for m in maps if str(m.dtype).replace("torch.", "") != "uint16" or len(m.shape) != 2]
+    if bad:
+        raise ValueError("save_maps: (hh, ww) uint16 maps, got %s among them" % (bad[0],))
+    save_pngs(paths, maps, compress_level)

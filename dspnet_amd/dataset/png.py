@@ -32,6 +32,11 @@ INFLATE_OK, INFLATE_ZLIB, INFLATE_LENGTH, INFLATE_FILTER = 0, 1, 2, 3
 _lib.register({
     "dspn_png_unfilter_batch": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_longlong,
                                            _c.c_void_p]),
+    # include/dspn_png_encode.h (dataset/png_encode.py is its front end)
+    "dspn_png_filtered_bytes": (_c.c_longlong, [_c.c_int, _c.c_int, _c.c_int]),
+    "dspn_png_filter_workspace_bytes": (_c.c_size_t, [_c.c_int]),
+    "dspn_png_filter_batch": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_longlong,
+                                         _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 })
 
 

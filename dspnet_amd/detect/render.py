@@ -286,6 +286,19 @@ def save_png(path, tensor):
     Image.fromarray(np.ascontiguousarray(a)).save(path, format="PNG")
 
 
+def save_pngs(paths, tensors, compress_level=6):
+    """a batch of images -> PNG files: (H, W) uint8, (H, W) uint16 or (H, W, 3) uint8 RGB tensors of any mix of sizes, device
+    or host (uploaded first).  The row filters of the whole batch run on the device in one call, deflate on a thread pool
+    (dataset/png_encode.py); the pixels and the filtered stream inside each file are those of `save_png`'s file."""
+    from ..dataset import png_encode
+    paths, tensors = list(paths), list(tensors)
+    if len(paths) != len(tensors):
+        raise _lib.DspnError("save_pngs: %d paths for %d images" % (len(paths), len(tensors)))
+    for path, data in zip(paths, png_encode.encode_batch(tensors, compress_level=compress_level)):
+        with open(path, "wb") as f:
+            f.write(data)
+
+
 def save_jpeg(path, image, quality=95):
     """(H, W, 3) RGB or (H, W) grey uint8 tensor -> baseline JPEG file (4:2:0 for colour), the file Pillow would write for
     the same pixels and quality.  The encode runs on the device (dataset/jpeg_encode.py: colour conversion, downsampling,

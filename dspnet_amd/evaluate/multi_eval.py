@@ -11,7 +11,8 @@ What the reference does per batch, and where it runs here:
   (offline, on the PNGs the script writes) Cityscapes IoU / iIoU           -> evaluate.cityscapes_eval (device counts)
   result images (:344-368): the labelId map at full resolution and the 2 x 2 display mosaic, per image
                                                                            -> results_dir=...: label_ids(prob_upsampling)
-      and detect.render.display_results (device), written as PNG files; no window is opened"""
+      and detect.render.display_results (device), written as PNG files (device_png=True: filtered on the device, a batch
+      at a time); no window is opened"""
 import os
 
 import numpy as np
@@ -60,7 +61,7 @@ def filter_detections(det, score_thresh=0.1):
 
 def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use_difficult=False,
                  voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False, device_depth=False,
-                 results_dir=None):
+                 results_dir=None, device_png=False):
     """net: training graph (symbol.multitask_symbol_factory.get_multi_symbol_train); batches: iterable of dicts with
     'data' (B,3,H,W), 'label_det' (B,L,6), 'label_seg' (B,H/4,W/4) and optionally 'disparity' (B,hh,ww) host maps.
     -> dict name -> value, plus 'class_maps' (list of uint8 device tensors) when full_res=(H, W) is given.
@@ -77,7 +78,9 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
     results/<name>, the labelId map at full_res (default 1024 x 2048), and output/<name with labelTrainIds -> output>, the
     display_results mosaic.  <name> is the base name of batch['fnames'][i] (the label image's path, as the iterator gives
     it), or '%06d_gtFine_labelTrainIds.png' of the running image index.  None (the default) launches nothing, imports
-    nothing and writes nothing."""
+    nothing and writes nothing.
+    device_png=True: the files of a batch are written by one detect.render.save_pngs call (row filters on the device, deflate
+    on a thread pool) in place of two Pillow saves per image; same names, same pixels."""
     render = image_index = None
     if results_dir is not None:
         from ..detect import render
@@ -117,12 +120,19 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
                             prob_upsampling(seg_prob, (1024, 2048), len(seg_class_names)))
             mosaic = render.display_results(net.data.data, net.label_seg.data, seg_prob, list(pred_det), net.label_det.data,
                                             list(class_names), num_classes=len(seg_class_names))
+            paths, images = [], []
             for i in range(mosaic.shape[0]):
                 name = (os.path.basename(batch["fnames"][i]) if batch.get("fnames") else
                         "%06d_gtFine_labelTrainIds.png" % image_index)
-                render.save_png(os.path.join(results_dir, "results", name), ids[i])
-                render.save_png(os.path.join(results_dir, "output", name.replace("labelTrainIds", "output")), mosaic[i])
+                paths += [os.path.join(results_dir, "results", name),
+                          os.path.join(results_dir, "output", name.replace("labelTrainIds", "output"))]
+                images += [ids[i], mosaic[i]]
                 image_index += 1
+            if device_png:
+                render.save_pngs(paths, images)
+            else:
+                for path, image in zip(paths, images):
+                    render.save_png(path, image)
         if city_metric is not None:
             gt_ids = batch["gt_label_ids"]
             if full_res is not None and tuple(gt_ids.shape[-2:]) != tuple(int(v) for v in full_res):
