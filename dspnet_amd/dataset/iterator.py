@@ -44,7 +44,10 @@ _CMAP_RGB = (_c.c_int * 3)(0, 1, 2)                             # Pillow decodes
 
 _lib.register({"dspn_augment_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                                      _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.c_void_p,
-                                                     _c.c_void_p, _c.c_void_p, _c.c_void_p])})
+                                                     _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+               # include/dspn_det_augment.h (dataset/det_iterator.py is its front end)
+               "dspn_det_augment_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                                         _c.POINTER(_c.c_double), _c.c_void_p, _c.c_void_p])})
 
 
 def _entry():
