@@ -23,7 +23,6 @@ two known differences).  Out of scope: DetRecordIter (:10-111), a wrapper of MXN
 not in the reference, and the colour-jitter settings of config/config.py that only that iterator reads."""
 import ctypes as _c
 import functools
-import io
 import math
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -37,6 +36,7 @@ from . import iterator as _iterator  # noqa: F401  (registers dspn_det_augment_b
 from . import jpeg
 from .im2rec import read_list
 from .rand_sampler import RandSampler
+from .staging import HostPools
 
 # the reference's list order (:281-282)
 LINEAR, CUBIC, AREA, NEAREST, LANCZOS4 = range(5)
@@ -312,14 +312,6 @@ class DataBatch(object):
         self.data, self.label, self.pad, self.index = data, label, pad, index
 
 
-class _Coded(object):
-    """a JPEG the device will reconstruct: the probed header"""
-
-    def __init__(self, payload, info):
-        self.payload, self.info = payload, info
-        self.size = (int(info["width"]), int(info["height"]))
-
-
 class _FitView(object):
     """what train.solver.fit consumes: (batch, indices) with batch.label == [label, None]"""
 
@@ -380,7 +372,7 @@ class DetIter(object):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(decode_threads)))
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
-        self._pixels = self._coefs = self._uploaded = None
+        self._pools = HostPools(self.device.type == "cuda")
 
         self._current = 0
         self._size = imdb.num_images
@@ -461,41 +453,6 @@ class DetIter(object):
                 label[valid_mask, 3] = tmp
         return window, method, mirror, label
 
-    def _open(self, content):
-        """sizes before any pixel is decoded: a probed JPEG for the device decode, else a lazily opened Pillow image"""
-        from PIL import Image
-        if self.device_jpeg and content[:2] == b"\xff\xd8":
-            rc, info = jpeg.probe_info(content)
-            if rc == 0 and info["supported"]:
-                return _Coded(content, info)
-        return Image.open(io.BytesIO(content))
-
-    def _decode(self, job):
-        """worker thread: one image into its slice of the pixel pool, or (device_jpeg) its coefficients into theirs
-        -> True when the device reconstructs it"""
-        im, dst, coef_dst = job
-        if isinstance(im, _Coded):
-            if jpeg.entropy_decode(im.payload, im.info, coef_dst) == 0:
-                return True
-            from PIL import Image
-            im = Image.open(io.BytesIO(im.payload))            # a corrupt scan: Pillow decodes or raises
-        dst[...] = np.asarray(im if im.mode == "RGB" else im.convert("RGB"))
-        return False
-
-    def _host_buffer(self, name, count, dtype):
-        """one staging buffer per kind, pinned when the batches go to a GPU, grown on demand; rewritten only after the
-        upload that last read it has completed"""
-        if self._uploaded is not None:
-            self._uploaded.synchronize()
-            self._uploaded = None
-        cur = getattr(self, name)
-        if cur is None or cur.numel() < count:
-            cur = torch.empty(max(count, 64), dtype=dtype)
-            if self.device.type == "cuda":
-                cur = cur.pin_memory()
-            setattr(self, name, cur)
-        return cur
-
     def _prepare(self):
         """host phase: indices, files, draws, decode, descriptors and tables"""
         B, (H, W) = self.batch_size, self._data_shape
@@ -510,7 +467,7 @@ class DetIter(object):
             else:
                 index = self._index[self._current + i]
             with open(self._imdb.image_path_from_index(index), "rb") as fp:
-                im = self._open(fp.read())
+                im = jpeg.open_image(fp.read(), self.device_jpeg)    # sizes before any pixel is decoded
             width, height = im.size
             gt = self._imdb.label_from_index(index).copy() if self.is_train else None
             window, method, mirror, label = self._plan(width, height, gt)
@@ -521,51 +478,35 @@ class DetIter(object):
             labels.append(label)
             indices.append(int(index))
         samples, tables = pack_batch(plans, H, W)
-        pixels = self._host_buffer("_pixels", offset, torch.uint8)
+        jbatch = jpeg.CodedBatch([im.info if isinstance(im, jpeg.Coded) else None for im in opened],
+                                 [p["img_offset"] for p in plans])
+        pixels = self._pools.take("pixels", offset, torch.uint8)
+        coefs = self._pools.take("coefs", jbatch.count, torch.int16, floor=jbatch.FLOOR)
         pnp = pixels.numpy()
-        coef_sizes = [int(im.info["coef_count"]) if isinstance(im, _Coded) else 0 for im in opened]
-        cnp = self._host_buffer("_coefs", sum(coef_sizes), torch.int16).numpy() if self.device_jpeg else None
-        jobs, co = [], 0
-        jsamples = np.zeros(len(opened), jpeg.SAMPLE)
-        for k, (im, p) in enumerate(zip(opened, plans)):
-            dst = pnp[p["img_offset"]:p["img_offset"] + p["src_w"] * p["src_h"] * 3].reshape(p["src_h"], p["src_w"], 3)
-            if isinstance(im, _Coded):
-                jpeg.fill_sample(jsamples[k], im.info, co, p["img_offset"])
-            jobs.append((im, dst, cnp[co:co + coef_sizes[k]] if cnp is not None else None))
-            co += coef_sizes[k]
-        coded = list(self._pool.map(self._decode, jobs))
-        jsamples["skip"] = [0 if c else 1 for c in coded]
+        dsts = [pnp[p["img_offset"]:p["img_offset"] + p["src_w"] * p["src_h"] * 3].reshape(p["src_h"], p["src_w"], 3)
+                for p in plans]
+        jbatch.answered(list(self._pool.map(jpeg.decode_image, opened, dsts, jbatch.slices(coefs.numpy()))))
         return {"count": len(plans), "pixels": pixels, "pixel_bytes": offset, "samples": samples, "tables": tables,
-                "labels": labels, "indices": indices, "coef_count": co, "jsamples": jsamples,
-                "fallbacks": coded.count(False) if self.device_jpeg else 0, "on_device": coded.count(True)}
+                "labels": labels, "indices": indices, "coefs": coefs, "jpeg": jbatch}
 
     def _device_batch(self, prep):
         """device phase: one upload of pixels (or coefficients), one of descriptors and tables, one launch
         -> (B, 3, H, W) float32; slots past the samples of `prep` stay zero"""
         B, (H, W), dev = self.batch_size, self._data_shape, self.device
-        n = prep["count"]
+        n, jbatch = prep["count"], prep["jpeg"]
         data = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if n == B else \
             torch.zeros(B, 3, H, W, dtype=torch.float32, device=dev)
         if n == 0:
             return data
-        nbytes = max(prep["pixel_bytes"], 1)
-        keep = ()
-        if prep["on_device"]:                                  # coefficients up; pixels only where Pillow decoded some
-            coef_dev = self._coefs[:max(prep["coef_count"], 64)].to(dev, non_blocking=True)
-            img_dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            if prep["fallbacks"]:
-                img_dev.copy_(prep["pixels"][:nbytes], non_blocking=True)
-        else:
-            img_dev = prep["pixels"][:nbytes].to(dev, non_blocking=True)
-        self._uploaded = torch.cuda.Event()
-        self._uploaded.record(torch.cuda.current_stream(dev))
+        # pool copies, then the pools' event, then descriptors and launches: the reason is in dataset/staging.py
+        img_dev = jbatch.upload(prep["coefs"], dev, prep["pixels"][:max(prep["pixel_bytes"], 1)])
+        self._pools.uploaded(torch.cuda.current_stream(dev))
         desc = np.concatenate([prep["samples"].view(np.uint8).reshape(-1), prep["tables"].view(np.uint8)])
         desc_dev = torch.from_numpy(desc).to(dev)              # descriptors and tables in one upload (56 B each: 4-aligned)
         ndesc = n * SAMPLE.itemsize
-        if prep["on_device"]:
-            jdesc_dev = torch.from_numpy(prep["jsamples"].view(np.uint8).reshape(-1)).to(dev)
-            keep = (coef_dev, jdesc_dev, jpeg.reconstruct(coef_dev, jdesc_dev, img_dev))
-        self.jpeg_fallbacks += prep["fallbacks"]
+        keep = jbatch.launch(img_dev)
+        if self.device_jpeg:
+            self.jpeg_fallbacks += jbatch.fallbacks
         augment_on_device(img_dev, desc_dev[:ndesc], desc_dev[ndesc:].view(torch.int32), H, W, self._mean_pixels,
                           out=data[:n])
         self._keepalive = (img_dev, desc_dev) + keep           # until the next batch replaces them

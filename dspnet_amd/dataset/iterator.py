@@ -33,6 +33,7 @@ from .. import _lib
 from . import jpeg
 from . import png
 from . import recordio
+from .staging import Decoded, HostPools
 
 # dspn_warp_sample (include/dspn_augment.h)
 _SAMPLE = np.dtype([("img_offset", "<i8"), ("seg_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("flip", "<i4"),
@@ -131,30 +132,6 @@ def augmented_boxes(rows, data_shape, aug):
     return True
 
 
-class _Decoded(object):
-    """decoded pixels of a cached record, with the two attributes _prepare reads from a PIL image"""
-
-    def __init__(self, a):
-        self.a = a
-        self.size = (a.shape[1], a.shape[0])
-
-
-class _Coded(object):
-    """a JPEG payload the device will reconstruct: the probed header, with the `size` _prepare reads from a PIL image"""
-
-    def __init__(self, payload, info):
-        self.payload, self.info = payload, info
-        self.size = (int(info["width"]), int(info["height"]))
-
-
-class _CodedLabel(object):
-    """a label-map PNG the device will unfilter: the probed chunk list, with the `size` _prepare reads from a PIL image"""
-
-    def __init__(self, payload, info):
-        self.payload, self.info = payload, info
-        self.size = (info["width"], info["height"])
-
-
 class DataBatch(object):
     def __init__(self, data, label):
         self.data, self.label = data, label
@@ -217,6 +194,7 @@ class MultiTaskRecordIter(object):
         # cache_decoded: keep the decoded uint8 pixels of every record in host memory (Cityscapes train: 2975 x 8.4 MB =
         # 25 GB); from the second epoch on the host phase is a memcpy instead of a JPEG + PNG decode
         self._cache = {} if cache_decoded else None
+        self._pools = [HostPools(torch.device(self.device).type == "cuda") for _ in range(2)]
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
         self.device_png, self.png_fallbacks = bool(device_png), 0
         self._get_batch()
@@ -261,118 +239,40 @@ class MultiTaskRecordIter(object):
     # host phase (_prepare: records, decode straight into a pinned pool, boxes, descriptors; may run ahead of the
     # consumer on the producer thread) and device phase (_finish: one upload, one launch pair, on the caller's stream)
     def _peek(self, item):
-        """header, label row and the lazily opened image(s) of one record: sizes are known before any pixel is decoded.
-        With cache_decoded the images come back as arrays from the second time a record is seen."""
-        import io
-        from PIL import Image
+        """header, label row and the lazily opened image(s) of one record: sizes are known before any pixel is decoded
+        (from the markers / IHDR where the device will decode).  With cache_decoded the images come back as arrays from
+        the second time a record is seen."""
         header, payload = recordio.unpack(item)
         hdr = np.array([header.label.shape[0]] + header.label.tolist())
         seg_path = self.imglst[str(header.id)]
         hit = self._cache.get(header.id) if self._cache is not None else None
         if hit is not None:
-            return hdr, _Decoded(hit[0]), (None if hit[1] is None else _Decoded(hit[1])), seg_path, header.id
-        im = None
-        if self.device_jpeg:                                   # sizes from the markers; no pixel is decoded here
-            rc, info = jpeg.probe_info(payload)
-            if rc == 0 and info["supported"]:
-                im = _Coded(payload, info)
-        if im is None:
-            im = Image.open(io.BytesIO(payload))
+            return hdr, Decoded(hit[0]), (None if hit[1] is None else Decoded(hit[1])), seg_path, header.id
+        im = jpeg.open_image(payload, self.device_jpeg)
         seg_im = None
-        if self.device_png and os.path.exists(seg_path):       # sizes from IHDR; nothing is inflated here
+        if os.path.exists(seg_path):
             with open(seg_path, "rb") as f:
-                coded = f.read()
-            try:
-                info = png.probe(coded)
-                if info["supported"] and info["bytes_per_pixel"] == 1:
-                    seg_im = _CodedLabel(coded, info)
-            except _lib.DspnError:
-                pass                                           # malformed: Pillow decodes or raises as it always did
-        if seg_im is None:
-            seg_im = Image.open(seg_path) if os.path.exists(seg_path) else None
+                seg_im = png.open_label(f.read(), self.device_png)
         if self.enable_aug:
             assert seg_im is not None, seg_path + " not found."
         if seg_im is not None:
             assert seg_im.size == im.size, "label map and image differ in size: " + seg_path
         return hdr, im, seg_im, seg_path, header.id
 
-    def _decode_into(self, args):
-        """decode one image / label map into its slice of the pinned pools (worker thread; Pillow's decoders and
-        numpy's copy loops release the GIL)"""
-        im, seg_im, img_dst, seg_dst, rec_id = args
-        if isinstance(im, _Decoded):                           # cached pixels: one memcpy each
+    def _decode(self, job):
+        """one record into its slices of the pools (worker thread; the decoders and numpy's copy loops release the GIL)
+        -> (the device reconstructs the image, the device unfilters the label map; None: there is no label map)"""
+        im, seg_im, img_dst, seg_dst, coef_dst, raw_dst, rec_id = job
+        if isinstance(im, Decoded):                            # cached pixels: one memcpy each
             img_dst[...] = im.a
             if seg_im is not None:
                 seg_dst[...] = seg_im.a
-            return True
-        if im is not None:                                     # None: the device reconstructs this image (device_jpeg)
-            img_dst[...] = np.asarray(im if im.mode == "RGB" else im.convert("RGB"))   # the kernel's channel map is the identity
-        if seg_im is not None:
-            a = np.asarray(seg_im if seg_im.mode in ("L", "P") else seg_im.convert("L"))
-            seg_dst[...] = a
+            return False, (None if seg_im is None else False)
+        answer = (jpeg.decode_image(im, img_dst, coef_dst),
+                  None if seg_im is None else png.decode_label(seg_im, seg_dst, raw_dst))
         if self._cache is not None:
             self._cache[rec_id] = (img_dst.copy(), None if seg_im is None else seg_dst.copy())
-        return True
-
-    def _decode_coded(self, args):
-        """device_jpeg: entropy-decode one record into its slice of the pinned coefficient pool (worker thread; ctypes
-        releases the GIL).  -> False when the record took the Pillow path into the image pool instead (it was not
-        probed as supported, or its scan turned out corrupt)"""
-        im, seg_im, img_dst, seg_dst, rec_id, coef_dst = args
-        coded = isinstance(im, _Coded)
-        if coded and jpeg.entropy_decode(im.payload, im.info, coef_dst) != 0:
-            import io
-            from PIL import Image
-            coded, im = False, Image.open(io.BytesIO(im.payload))
-        self._decode_into((None if coded else im, seg_im, img_dst, seg_dst, rec_id))
-        return coded
-
-    def _decode_label(self, args):
-        """device_png: inflate one record's label map into its slice of the pinned raw pool, then run the record's image
-        job (worker thread; zlib releases the GIL).  -> (what the image job said, False when the label map took the Pillow
-        path into the seg byte pool instead: it was not probed as supported, or its data turned out corrupt)"""
-        image_job, job, raw_dst = args
-        seg_im = job[1]
-        coded = isinstance(seg_im, _CodedLabel)
-        if coded and png.inflate_into(seg_im.payload, seg_im.info, raw_dst) != 0:
-            import io
-            from PIL import Image
-            coded, seg_im = False, Image.open(io.BytesIO(seg_im.payload))
-        return image_job(job[:1] + (None if coded else seg_im,) + job[2:]), coded
-
-    def _raw_pool_set(self, k, count):
-        """pinned uint8 buffers for the inflated label rows, alternated like the two byte pools (call after
-        _pool_set(k, ...), which has waited for the upload that last read set k)"""
-        if not hasattr(self, "_raw_pools"):
-            self._raw_pools = [None, None]
-        cur = self._raw_pools[k]
-        if cur is None or cur.numel() < count:
-            cur = self._raw_pools[k] = torch.empty(max(count, 1), dtype=torch.uint8).pin_memory()
-        return cur
-
-    def _coef_pool_set(self, k, count):
-        """pinned int16 coefficient buffers, alternated like the two byte pools (call after _pool_set(k, ...), which
-        has waited for the upload that last read set k)"""
-        if not hasattr(self, "_coef_pools"):
-            self._coef_pools = [None, None]
-        cur = self._coef_pools[k]
-        if cur is None or cur.numel() < count:
-            cur = self._coef_pools[k] = torch.empty(max(count, 64), dtype=torch.int16).pin_memory()
-        return cur
-
-    def _pool_set(self, k, img_bytes, seg_bytes):
-        """pinned staging buffers, two sets used alternately, grown on demand; a set is rewritten only after the
-        upload that last read it has completed"""
-        if not hasattr(self, "_pools"):
-            self._pools = [None, None]
-        cur = self._pools[k]
-        if cur is not None and cur[2] is not None:
-            cur[2].synchronize()
-        if cur is None or cur[0].numel() < img_bytes or cur[1].numel() < seg_bytes:
-            cur = [torch.empty(max(img_bytes, 1), dtype=torch.uint8).pin_memory(),
-                   torch.empty(max(seg_bytes, 1), dtype=torch.uint8).pin_memory(), None]
-            self._pools[k] = cur
-        return cur
+        return answer
 
     def _prepare(self, start, serial):
         B, (C, H, W) = self.batch_size, self.data_shape
@@ -380,24 +280,26 @@ class MultiTaskRecordIter(object):
         peeked = [self._peek(item) for item in items]
         img_sizes = [im.size[0] * im.size[1] * 3 for _, im, _, _, _ in peeked]
         seg_sizes = [(sm.size[0] * sm.size[1] if sm is not None else 0) for _, _, sm, _, _ in peeked]
-        pool = self._pool_set(serial % 2, sum(img_sizes), sum(seg_sizes))
-        ip, sp = pool[0].numpy(), pool[1].numpy()
+        img_offsets, seg_offsets = np.cumsum([0] + img_sizes).tolist(), np.cumsum([0] + seg_sizes).tolist()
+        jbatch = jpeg.CodedBatch([im.info if isinstance(im, jpeg.Coded) else None for _, im, _, _, _ in peeked],
+                                 img_offsets)
+        pbatch = png.CodedBatch([sm.info if isinstance(sm, png.CodedLabel) else None for _, _, sm, _, _ in peeked],
+                                seg_offsets)
+        pools = self._pools[serial % 2]                        # two sets of pinned staging buffers, used alternately
+        pixels = pools.take("pixels", img_offsets[-1], torch.uint8)
+        labels = pools.take("labels", seg_offsets[-1], torch.uint8)
+        coefs = pools.take("coefs", jbatch.count, torch.int16, floor=jbatch.FLOOR)
+        raw = pools.take("raw", pbatch.count, torch.uint8)
+        ip, sp = pixels.numpy(), labels.numpy()
         label = np.ones((B, 1206)) * -1
         label[:, :3] = np.array(list(self.data_shape))
         samples = np.zeros(B, _SAMPLE)
         jobs, fnames = [], []
-        io_ = so = 0
-        if self.device_jpeg:
-            coef_sizes = [int(im.info["coef_count"]) if isinstance(im, _Coded) else 0 for _, im, _, _, _ in peeked]
-            cp = self._coef_pool_set(serial % 2, sum(coef_sizes))
-            cnp, co, jsamples = cp.numpy(), 0, np.zeros(B, jpeg.SAMPLE)
-        if self.device_png:
-            raw_sizes = [sm.info["raw_bytes"] if isinstance(sm, _CodedLabel) else 0 for _, _, sm, _, _ in peeked]
-            rp = self._raw_pool_set(serial % 2, sum(raw_sizes))
-            rnp, ro, psamples, raw_dsts = rp.numpy(), 0, np.zeros(B, png.SAMPLE), []
+        coef_dsts, raw_dsts = jbatch.slices(coefs.numpy()), pbatch.slices(raw.numpy())
         for b, (hdr, im, seg_im, seg_path, rec_id) in enumerate(peeked):
             ww, hh = im.size
             slot = start + b
+            io_, so = img_offsets[b], seg_offsets[b]
             rows = hdr[3:].reshape((-1, 6))                     # view: the edits land in hdr
             if self.enable_aug:
                 flip, theta, sx, sy, tx, ty = self.aug_params[slot]
@@ -415,73 +317,31 @@ class MultiTaskRecordIter(object):
             s["flip"], s["img_border"], s["seg_border"] = int(flip_img), ib, sb
             s["minv"] = invert_affine(M)
             jobs.append((im, seg_im, ip[io_:io_ + img_sizes[b]].reshape(hh, ww, 3),
-                         sp[so:so + seg_sizes[b]].reshape(hh, ww) if seg_im is not None else None, rec_id))
-            if self.device_jpeg:
-                if isinstance(im, _Coded):
-                    jpeg.fill_sample(jsamples[b], im.info, co, io_)
-                jobs[-1] = jobs[-1] + (cnp[co:co + coef_sizes[b]],)
-                co += coef_sizes[b]
-            if self.device_png:
-                if isinstance(seg_im, _CodedLabel):
-                    png.fill_sample(psamples[b], seg_im.info, ro, so)
-                raw_dsts.append(rnp[ro:ro + raw_sizes[b]])
-                ro += raw_sizes[b]
-            io_ += img_sizes[b]
-            so += seg_sizes[b]
+                         sp[so:so + seg_sizes[b]].reshape(hh, ww) if seg_im is not None else None,
+                         coef_dsts[b], raw_dsts[b], rec_id))
             label[b, 3:3 + hdr.shape[0]] = hdr
             fnames.append(seg_path)
-        prep = {"pool": pool, "img_bytes": io_, "seg_bytes": so, "samples": samples, "label": label, "fnames": fnames,
-                "start": start}
-        image_job = self._decode_coded if self.device_jpeg else self._decode_into
-        if self.device_png:
-            done = list(self._pool.map(self._decode_label, [(image_job, job, dst) for job, dst in zip(jobs, raw_dsts)]))
-            coded = [c for c, _ in done]
-            on_device = [d for _, d in done]
-            psamples["skip"] = [0 if d else 1 for d in on_device]
-            labelled = sum(1 for _, _, sm, _, _ in peeked if sm is not None)
-            prep["png"] = {"pool": rp, "count": ro, "samples": psamples, "on_device": on_device.count(True),
-                           "fallbacks": labelled - on_device.count(True)}
-        else:
-            coded = list(self._pool.map(image_job, jobs))
-        if self.device_jpeg:
-            jsamples["skip"] = [0 if c else 1 for c in coded]
-            prep["jpeg"] = {"pool": cp, "count": co, "samples": jsamples, "fallbacks": coded.count(False)}
-        return prep
+        answers = list(self._pool.map(self._decode, jobs))
+        jbatch.answered([a for a, _ in answers])
+        pbatch.answered([a for _, a in answers])
+        return {"pools": pools, "pixels": pixels[:max(img_offsets[-1], 1)], "labels": labels[:max(seg_offsets[-1], 1)],
+                "coefs": coefs, "raw": raw, "jpeg": jbatch, "png": pbatch, "samples": samples, "label": label,
+                "fnames": fnames, "start": start}
 
     def _finish(self, prep):
         B, (C, H, W) = self.batch_size, self.data_shape
         dev = self.device
-        pool = prep["pool"]
-        if self.device_jpeg:                                   # coefficients up; pixels only where Pillow decoded some
-            jp = prep["jpeg"]
-            coef_dev = jp["pool"][:max(jp["count"], 64)].to(dev, non_blocking=True)
-            img_dev = torch.empty(max(prep["img_bytes"], 1), dtype=torch.uint8, device=dev)
-            if jp["fallbacks"]:
-                img_dev.copy_(pool[0][:max(prep["img_bytes"], 1)], non_blocking=True)
-            self.jpeg_fallbacks += jp["fallbacks"]
-        else:
-            img_dev = pool[0][:max(prep["img_bytes"], 1)].to(dev, non_blocking=True)
-        if self.device_png:                                    # filtered rows up; label bytes only where Pillow decoded some
-            pp = prep["png"]
-            raw_dev = pp["pool"][:max(pp["count"], 1)].to(dev, non_blocking=True)
-            seg_dev = torch.empty(max(prep["seg_bytes"], 1), dtype=torch.uint8, device=dev)
-            if pp["fallbacks"]:
-                seg_dev.copy_(pool[1][:max(prep["seg_bytes"], 1)], non_blocking=True)
-            self.png_fallbacks += pp["fallbacks"]
-        else:
-            seg_dev = pool[1][:max(prep["seg_bytes"], 1)].to(dev, non_blocking=True)
-        pool[2] = torch.cuda.Event()
-        pool[2].record(torch.cuda.current_stream(dev))
+        jbatch, pbatch = prep["jpeg"], prep["png"]
+        # pool copies, then the set's event, then descriptors and launches: the reason is in dataset/staging.py
+        img_dev = jbatch.upload(prep["coefs"], dev, prep["pixels"])
+        seg_dev = pbatch.upload(prep["raw"], dev, prep["labels"])
+        prep["pools"].uploaded(torch.cuda.current_stream(dev))
         desc_dev = torch.from_numpy(prep["samples"].view(np.uint8).reshape(-1)).to(dev)
-        jpeg_keep = ()
-        if self.device_jpeg and jp["fallbacks"] < B:           # the pixels of the coded records, in front of the warp
-            jdesc_dev = torch.from_numpy(jp["samples"].view(np.uint8).reshape(-1)).to(dev)
-            jpeg_keep = (coef_dev, jdesc_dev, jpeg.reconstruct(coef_dev, jdesc_dev, img_dev))
-        png_keep = ()
-        if self.device_png and pp["on_device"]:                # the bytes of the coded label maps, in front of the warp
-            pdesc_dev = torch.from_numpy(pp["samples"].view(np.uint8).reshape(-1)).to(dev)
-            png.unfilter(raw_dev, pdesc_dev, seg_dev)
-            png_keep = (raw_dev, pdesc_dev)
+        coded_keep = jbatch.launch(img_dev) + pbatch.launch(seg_dev)    # the coded records' bytes, in front of the warp
+        if self.device_jpeg:
+            self.jpeg_fallbacks += jbatch.fallbacks
+        if self.device_png:
+            self.png_fallbacks += pbatch.fallbacks
         data = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
         seg_out = torch.empty(B, H // 4, W // 4, dtype=torch.float32, device=dev)
         _lib.check(_entry()(img_dev.data_ptr(), seg_dev.data_ptr(), desc_dev.data_ptr(), B, H, W, _CMAP_RGB,
@@ -503,7 +363,7 @@ class MultiTaskRecordIter(object):
         det_dev = torch.from_numpy(det.astype(np.float32)).to(dev)
         self._batch = DataBatch(data=[data], label=[det_dev, seg_out])
         self._fnames = prep["fnames"]
-        self._keepalive = (img_dev, seg_dev, desc_dev) + jpeg_keep + png_keep   # until the next batch replaces them
+        self._keepalive = (img_dev, seg_dev, desc_dev) + coded_keep    # until the next batch replaces them
 
     def _drop_ahead(self):
         fut, self._ahead = getattr(self, "_ahead", None), None

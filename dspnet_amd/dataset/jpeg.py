@@ -3,14 +3,16 @@ scan into quantised DCT coefficients (serial work; ctypes releases the GIL aroun
 parallel), the device dequantises, inverts the DCT, upsamples the chroma and converts to RGB for a whole batch in one
 call.  The pixels equal Pillow's (libjpeg-turbo, accurate integer IDCT, fancy upsampling) byte for byte.
 
-`probe` and `decode_batch` are the public use; MultiTaskRecordIter(device_jpeg=True) drives the same three C entry
-points with its own pinned pools."""
+`probe` and `decode_batch` are the public use; the iterators (device_jpeg=True) go through `open_image`, `decode_image`
+and `CodedBatch` with their own pools (dataset/staging.py)."""
 import ctypes as _c
+import io
 
 import numpy as np
 import torch
 
 from .. import _lib
+from . import staging
 
 # dspn_jpeg_info / dspn_jpeg_sample (include/dspn_jpeg.h)
 INFO = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("restart_interval", "<i4"),
@@ -92,6 +94,51 @@ def reconstruct(coefs, samples, images_out, stream=None):
     return ws
 
 
+class Coded(object):
+    """a JPEG payload the device will reconstruct: the probed header, with the `size` a batch layout reads from a PIL
+    image"""
+
+    def __init__(self, payload, info):
+        self.payload, self.info = payload, info
+        self.size = (int(info["width"]), int(info["height"]))
+
+
+def open_image(content, device_jpeg):
+    """sizes before any pixel is decoded: a Coded for a baseline JPEG the device decode supports (device_jpeg only), else
+    a lazily opened Pillow image"""
+    from PIL import Image
+    if device_jpeg:
+        rc, info = probe_info(content)
+        if rc == 0 and info["supported"]:
+            return Coded(content, info)
+    return Image.open(io.BytesIO(content))
+
+
+def decode_image(im, dst, coef_dst):
+    """worker thread (ctypes and Pillow's decoders release the GIL): the coefficients of a Coded into coef_dst, or the
+    pixels of anything else into the (h, w, 3) array dst.  -> True when the device reconstructs the image"""
+    if isinstance(im, Coded):
+        if entropy_decode(im.payload, im.info, coef_dst) == 0:
+            return True
+        from PIL import Image
+        im = Image.open(io.BytesIO(im.payload))                 # a corrupt scan: Pillow decodes or raises
+    dst[...] = np.asarray(im if im.mode == "RGB" else im.convert("RGB"))
+    return False
+
+
+class CodedBatch(staging.CodedBatch):
+    """staging.CodedBatch over dspn_jpeg_sample: int16 coefficients in, RGB bytes out.  The pool is cut to at least 64
+    values because the reconstruct entry refuses a count that is zero or not a multiple of 64."""
+    SAMPLE, FLOOR = SAMPLE, 64
+
+    def _describe(self, s, info, coef_base, img_offset):
+        fill_sample(s, info, coef_base, img_offset)
+        return int(info["coef_count"])
+
+    def _launch(self, coef_dev, desc_dev, images_out):
+        return (reconstruct(coef_dev, desc_dev, images_out),)   # the workspace
+
+
 def decode_batch(payloads, device):
     """decode a list of JPEG byte strings -> list of (h, w, 3) uint8 RGB tensors on `device`, views of one pool.
     ValueError (naming the reason) for a stream outside the supported set, DspnError for a malformed one."""
@@ -104,23 +151,14 @@ def decode_batch(payloads, device):
         infos.append(info)
     if not infos:
         return []
-    coefs = torch.empty(sum(int(i["coef_count"]) for i in infos), dtype=torch.int16).pin_memory()
-    cnp = coefs.numpy()
-    samples = np.zeros(len(infos), SAMPLE)
-    co = io = 0
-    for k, (p, info) in enumerate(zip(payloads, infos)):
-        n = int(info["coef_count"])
-        _lib.check(entropy_decode(p, info, cnp[co:co + n]), "jpeg_entropy_decode (stream %d)" % k)
-        fill_sample(samples[k], info, co, io)
-        co += n
-        io += int(info["width"]) * int(info["height"]) * 3
-    pool = torch.empty(io, dtype=torch.uint8, device=device)
-    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1)).to(device)
-    reconstruct(coefs.to(device), desc, pool)
+    sizes = [int(i["width"]) * int(i["height"]) * 3 for i in infos]
+    batch = CodedBatch(infos, np.cumsum([0] + sizes[:-1]))
+    coefs = torch.empty(batch.count, dtype=torch.int16).pin_memory()
+    for k, (p, info, dst) in enumerate(zip(payloads, infos, batch.slices(coefs.numpy()))):
+        _lib.check(entropy_decode(p, info, dst), "jpeg_entropy_decode (stream %d)" % k)
+    batch.answered([True] * len(infos))
+    pool = torch.empty(sum(sizes), dtype=torch.uint8, device=device)
+    batch.upload(coefs, device)
+    batch.launch(pool)
     torch.cuda.current_stream(device).synchronize()            # the pinned buffer and the workspace go out of scope here
-    out, io = [], 0
-    for info in infos:
-        h, w = int(info["height"]), int(info["width"])
-        out.append(pool[io:io + h * w * 3].view(h, w, 3))
-        io += h * w * 3
-    return out
+    return [img.view(int(i["height"]), int(i["width"]), 3) for img, i in zip(pool.split(sizes), infos)]

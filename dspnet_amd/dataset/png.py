@@ -6,8 +6,10 @@ Supported: greyscale 8-bit, palette 8-bit (the indices are the samples: what np.
 greyscale 16-bit, not interlaced, without tRNS and without animation.
 
 `probe` and `decode_batch` are the public use (ground-truth id maps, instance-id maps, disparity maps held as PNG bytes);
-MultiTaskRecordIter(device_png=True) drives `probe`, `inflate_into` and `unfilter` with its own pinned pools."""
+MultiTaskRecordIter(device_png=True) goes through `open_label`, `decode_label` and `CodedBatch` with its own pools
+(dataset/staging.py)."""
 import ctypes as _c
+import io
 import struct
 import zlib
 
@@ -15,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import staging
 
 # dspn_png_sample (include/dspn_png.h)
 SAMPLE = np.dtype([("raw_offset", "<i8"), ("out_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
@@ -142,6 +145,54 @@ def unfilter(raw_dev, samples_dev, out_dev, stream=None):
                                                   out_dev.numel(), st), "png_unfilter")
 
 
+class CodedLabel(object):
+    """a label-map PNG the device will unfilter: the probed chunk list, with the `size` a batch layout reads from a PIL
+    image"""
+
+    def __init__(self, payload, info):
+        self.payload, self.info = payload, info
+        self.size = (info["width"], info["height"])
+
+
+def open_label(content, device_png):
+    """sizes before anything is inflated: a CodedLabel for an 8-bit greyscale / palette stream the device decode supports
+    (device_png only), else a lazily opened Pillow image"""
+    from PIL import Image
+    if device_png:
+        try:
+            info = probe(content)
+            if info["supported"] and info["bytes_per_pixel"] == 1:
+                return CodedLabel(content, info)
+        except _lib.DspnError:
+            pass                                                # malformed: Pillow decodes or raises as it always did
+    return Image.open(io.BytesIO(content))
+
+
+def decode_label(im, dst, raw_dst):
+    """worker thread (zlib and Pillow's decoders release the GIL): the filtered rows of a CodedLabel into raw_dst, or the
+    samples of anything else into the (h, w) array dst.  -> True when the device unfilters the label map"""
+    if isinstance(im, CodedLabel):
+        if inflate_into(im.payload, im.info, raw_dst) == 0:
+            return True
+        from PIL import Image
+        im = Image.open(io.BytesIO(im.payload))                 # corrupt data: Pillow decodes or raises
+    dst[...] = np.asarray(im if im.mode in ("L", "P") else im.convert("L"))
+    return False
+
+
+class CodedBatch(staging.CodedBatch):
+    """staging.CodedBatch over dspn_png_sample: inflated rows with their filter bytes in, samples out"""
+    SAMPLE, FLOOR = SAMPLE, 1
+
+    def _describe(self, s, info, raw_offset, out_offset):
+        fill_sample(s, info, raw_offset, out_offset)
+        return info["raw_bytes"]
+
+    def _launch(self, raw_dev, desc_dev, out_dev):
+        unfilter(raw_dev, desc_dev, out_dev)
+        return ()
+
+
 def decode_batch(payloads, device):
     """decode a list of PNG byte strings -> list of (h, w) tensors on `device`, torch.uint8 for the 8-bit formats and
     torch.uint16 (native byte order) for 16-bit greyscale, views of one pool.  ValueError (naming the reason) for a stream
@@ -157,24 +208,21 @@ def decode_batch(payloads, device):
         infos.append(info)
     if not infos:
         return []
-    raw = torch.empty(sum(i["raw_bytes"] for i in infos), dtype=torch.uint8).pin_memory()
-    rnp = raw.numpy()
-    samples = np.zeros(len(infos), SAMPLE)
-    ro = oo = 0
-    for k, (p, info) in enumerate(zip(payloads, infos)):
-        status = inflate_into(p, info, rnp[ro:ro + info["raw_bytes"]])
+    sizes = [-(-i["height"] * i["row_bytes"] // 16) * 16 for i in infos]    # every image 16-byte aligned in the pool
+    batch = CodedBatch(infos, np.cumsum([0] + sizes[:-1]))
+    raw = torch.empty(batch.count, dtype=torch.uint8).pin_memory()
+    for k, (p, info, dst) in enumerate(zip(payloads, infos, batch.slices(raw.numpy()))):
+        status = inflate_into(p, info, dst)
         if status:
             raise _lib.DspnError("png_inflate (stream %d): %s" % (k, ("", "zlib error", "inflated length is not height * "
                                  "(row_bytes + 1)", "filter type above 4")[status]))
-        fill_sample(samples[k], info, ro, oo)
-        ro += info["raw_bytes"]
-        oo += -(-info["height"] * info["row_bytes"] // 16) * 16   # every image 16-byte aligned in the pool
-    pool = torch.empty(oo, dtype=torch.uint8, device=device)
-    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1)).to(device)
-    unfilter(raw.to(device), desc, pool)
+    batch.answered([True] * len(infos))
+    pool = torch.empty(sum(sizes), dtype=torch.uint8, device=device)
+    batch.upload(raw, device)
+    batch.launch(pool)
     torch.cuda.current_stream(device).synchronize()             # the pinned buffer goes out of scope here
     out = []
-    for s, info in zip(samples, infos):
+    for s, info in zip(batch.samples, infos):
         h, w, o = info["height"], info["width"], int(s["out_offset"])
         img = pool[o:o + h * info["row_bytes"]]
         out.append((img.view(torch.uint16) if info["bytes_per_pixel"] == 2 else img).view(h, w))

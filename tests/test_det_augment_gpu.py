@@ -156,6 +156,36 @@ def test_det_iter_equals_the_host_path(gpu_device, jpeg_list, monkeypatch, devic
                for g in got for k in range(4))
 
 
+def test_det_iter_mixed_fallback_batch(gpu_device, tmp_path):
+    """two baseline JPEGs beside a progressive one and a PNG: coefficients go up for two samples of every batch and
+    Pillow's pixels for the other two, and the batches equal those with the device decode off"""
+    from PIL import Image
+    gen = np.random.RandomState(24)
+    lines = []
+    for k, (h, w, name, kw) in enumerate([(40, 96, "a.jpg", {}), (47, 91, "b.jpg", {}), (45, 80, "c.jpg", {"progressive": True}),
+                                          (38, 51, "d.png", {})]):
+        yy, xx = np.mgrid[0:h, 0:w]
+        smooth = np.stack([(xx * 3 + yy * 2 + 40 * k) % 256, (xx * yy // 7 + 90) % 256, (255 - xx - yy) % 256], axis=2)
+        Image.fromarray(np.clip(smooth + gen.randint(-20, 21, (h, w, 3)), 0, 255).astype(np.uint8)).save(str(tmp_path / name), **kw)
+        lab = np.array([[k, .10, .15, .55, .70], [k + 3, .45, .30, .92, .88]])
+        lines.append("\t".join([str(k), "2", "5"] + ["{0:.4f}".format(x) for x in lab.ravel()] + [name]) + "\n")
+    with open(str(tmp_path / "mixed.lst"), "w") as f:
+        f.writelines(lines)
+    db = di.ListImdb(str(tmp_path / "mixed.lst"), str(tmp_path))
+    kwargs = dict(mean_pixels=list(MEAN), rand_samplers=_samplers(), rand_mirror=True, shuffle=True, rand_seed=233,
+                  device=gpu_device)
+    on = di.DetIter(db, 4, (3, 33, 41), device_jpeg=True, **kwargs)
+    got = _two_epochs(on)
+    off = di.DetIter(db, 4, (3, 33, 41), device_jpeg=False, **kwargs)
+    want = _two_epochs(off)
+    torch.cuda.synchronize()
+    assert on.jpeg_fallbacks == 4 and off.jpeg_fallbacks == 0   # the progressive file and the PNG, once per epoch
+    assert len(got) == len(want) == 2
+    for g, w in zip(got, want):
+        assert g[2:] == w[2:]
+        assert torch.equal(g[1], w[1]) and torch.equal(g[0], w[0])
+
+
 def test_fit_consumes_the_fit_view(gpu_device, jpeg_list):
     """two steps of train.solver.fit on the detection-only graph of tests/test_graph_gpu.py::test_single_task_graphs_train
     (resnet-50 at 256, batch 2), fed by DetIter.fit_view()"""

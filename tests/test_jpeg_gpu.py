@@ -132,14 +132,19 @@ def test_reconstruct_argument_checks(gpu_device):
     assert lib.dspn_jpeg_reconstruct_batch_u8(p + 2, 64, p, 1, p, 64, p, 64, None) == -1 and b"aligned" in lib.dspn_last_error()
 
 
-def _write_dataset(root, n, g, hw=(96, 160), boxes=(0, 1, 3, 5, 2, 4, 1, 6)):
-    """as tests/test_record_iter.py::_write_dataset, with record 2 re-encoded progressive and record 5 greyscale"""
+SIZES = [(96, 160)] * 4 + [(128, 192)] * 4                     # per record: every staging pool grows once after its first use
+
+
+def _write_dataset(root, n, g, progressive=(2,), sizes=SIZES, boxes=(0, 1, 3, 5, 2, 4, 1, 6)):
+    """as tests/test_record_iter.py::_write_dataset, with the records of `progressive` re-encoded progressive, record 5
+    greyscale and a size per record"""
     from PIL import Image
     os.makedirs(os.path.join(root, "cityscapes", "SegmentationClass"), exist_ok=True)
     rec = recordio.MXIndexedRecordIO(os.path.join(root, "train.idx"), os.path.join(root, "train.rec"), "w")
     lines = []
-    yy, xx = np.mgrid[:hw[0], :hw[1]]
     for i in range(n):
+        hw = sizes[i]
+        yy, xx = np.mgrid[:hw[0], :hw[1]]
         chans = [127 + 100 * np.sin(xx / g.uniform(5, 15) + g.uniform(0, 3)) * np.cos(yy / g.uniform(5, 15)) for _ in range(3)]
         img = np.clip(np.stack(chans, -1) + g.normal(0, 6, hw + (3,)), 0, 255).astype(np.uint8)
         rows = np.full((10, 6), -1.0)
@@ -148,12 +153,10 @@ def _write_dataset(root, n, g, hw=(96, 160), boxes=(0, 1, 3, 5, 2, 4, 1, 6)):
             rows[k] = [g.integers(0, 8), x0, y0, x0 + g.uniform(.01, .3), y0 + g.uniform(.01, .3), g.uniform(0, 1)]
         label = np.array([2, 6] + rows.reshape(-1).tolist(), np.float32)
         header = recordio.IRHeader(0, label, i, 0)
-        if i in (2, 5):
+        if i in progressive or i == 5:
             buf = io.BytesIO()
-            if i == 2:
-                Image.fromarray(img[:, :, ::-1].copy()).save(buf, format="JPEG", quality=92, progressive=True)
-            else:
-                Image.fromarray(img[:, :, 1].copy()).save(buf, format="JPEG", quality=92)
+            picture = img[:, :, 1] if i == 5 else img[:, :, ::-1]
+            Image.fromarray(picture.copy()).save(buf, format="JPEG", quality=92, progressive=i in progressive)
             rec.write_idx(i, recordio.pack(header, buf.getvalue()))
         else:
             rec.write_idx(i, recordio.pack_img(header, img, quality=92))
@@ -173,10 +176,14 @@ def record_file(tmp_path_factory):
     return _write_dataset(str(tmp_path_factory.mktemp("jpeg_records")), 8, np.random.Generator(np.random.PCG64(17)))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("prefetch", [True, False])
-@pytest.mark.parametrize("enable_aug", [True, False])
-def test_iterator_device_jpeg_yields_the_same_batches(gpu_device, record_file, enable_aug, prefetch):
+@pytest.fixture(scope="module")
+def progressive_record_file(tmp_path_factory):
+    """all eight records progressive: no batch has anything for the device"""
+    return _write_dataset(str(tmp_path_factory.mktemp("jpeg_records_progressive")), 8,
+                          np.random.Generator(np.random.PCG64(18)), progressive=range(8))
+
+
+def _same_batches(gpu_device, record_file, enable_aug, prefetch, fallbacks):
     import torch
     kw = dict(enable_aug=enable_aug, prefetch=prefetch, device=gpu_device)
     a = it.MultiTaskRecordIter(record_file, 4, (3, 64, 128), **kw)
@@ -193,7 +200,21 @@ def test_iterator_device_jpeg_yields_the_same_batches(gpu_device, record_file, e
         assert not b.iter_next()
         a.reset(); b.reset()
     assert seen == 16
-    assert b.jpeg_fallbacks == 2 and a.jpeg_fallbacks == 0     # the progressive record, once per epoch
+    assert b.jpeg_fallbacks == fallbacks and a.jpeg_fallbacks == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prefetch", [True, False])
+@pytest.mark.parametrize("enable_aug", [True, False])
+def test_iterator_device_jpeg_yields_the_same_batches(gpu_device, record_file, enable_aug, prefetch):
+    _same_batches(gpu_device, record_file, enable_aug, prefetch, fallbacks=2)    # the progressive record, once per epoch
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prefetch", [True, False])
+def test_iterator_device_jpeg_all_fallback_batches(gpu_device, progressive_record_file, prefetch):
+    """the pixels go up directly and nothing JPEG-related is uploaded or launched: 8 fallbacks per epoch"""
+    _same_batches(gpu_device, progressive_record_file, True, prefetch, fallbacks=16)
 
 
 def test_device_jpeg_refuses_the_decoded_cache(tmp_path):

@@ -179,15 +179,20 @@ def test_decode_batch_names_the_reason(gpu_device):
         dp.decode_batch([good, good[:-12]], gpu_device)
 
 
-def _write_dataset(root, n, g, hw=(96, 160), boxes=(0, 1, 3, 5, 2, 4, 1, 6)):
-    """as tests/test_jpeg_gpu.py::_write_dataset (record 2 progressive, record 5 greyscale), the label maps from the
-    filter-choosing writer: random filter types, record 1 as a palette stream, record 3 interlaced, record 6 as RGB"""
+SIZES = [(96, 160)] * 4 + [(128, 192)] * 4                     # per record: every staging pool grows once after its first use
+
+
+def _write_dataset(root, n, g, interlaced=(3,), sizes=SIZES, boxes=(0, 1, 3, 5, 2, 4, 1, 6)):
+    """as tests/test_jpeg_gpu.py::_write_dataset (record 2 progressive, record 5 greyscale, a size per record), the label
+    maps from the filter-choosing writer: random filter types, the records of `interlaced` interlaced, of the others
+    record 1 as a palette stream and record 6 as RGB"""
     from PIL import Image
     os.makedirs(os.path.join(root, "cityscapes", "SegmentationClass"), exist_ok=True)
     rec = recordio.MXIndexedRecordIO(os.path.join(root, "train.idx"), os.path.join(root, "train.rec"), "w")
     lines = []
-    yy, xx = np.mgrid[:hw[0], :hw[1]]
     for i in range(n):
+        hw = sizes[i]
+        yy, xx = np.mgrid[:hw[0], :hw[1]]
         chans = [127 + 100 * np.sin(xx / g.uniform(5, 15) + g.uniform(0, 3)) * np.cos(yy / g.uniform(5, 15)) for _ in range(3)]
         img = np.clip(np.stack(chans, -1) + g.normal(0, 6, hw + (3,)), 0, 255).astype(np.uint8)
         rows = np.full((10, 6), -1.0)
@@ -209,7 +214,7 @@ def _write_dataset(root, n, g, hw=(96, 160), boxes=(0, 1, 3, 5, 2, 4, 1, 6)):
         seg[g.random(hw) < .1] = 255
         seg[:4, :4] = 40
         filters = rp.filters_for(g, hw[0], "mix")
-        if i == 3:
+        if i in interlaced:
             data = rp.write_interlaced(seg)
         elif i == 6:
             data = rp.write_rgb(np.stack([seg, seg, seg], -1), filters)
@@ -229,10 +234,14 @@ def record_file(tmp_path_factory):
     return _write_dataset(str(tmp_path_factory.mktemp("png_records")), 8, np.random.Generator(np.random.PCG64(19)))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("enable_aug,prefetch,device_jpeg", [(True, True, False), (True, False, False), (False, True, False),
-                                                             (False, False, False), (True, True, True)])
-def test_iterator_device_png_yields_the_same_batches(gpu_device, record_file, enable_aug, prefetch, device_jpeg):
+@pytest.fixture(scope="module")
+def interlaced_record_file(tmp_path_factory):
+    """all eight label maps interlaced: no batch has anything for the device"""
+    return _write_dataset(str(tmp_path_factory.mktemp("png_records_interlaced")), 8,
+                          np.random.Generator(np.random.PCG64(20)), interlaced=range(8))
+
+
+def _same_batches(gpu_device, record_file, enable_aug, prefetch, device_jpeg, fallbacks):
     import torch
     kw = dict(enable_aug=enable_aug, prefetch=prefetch, device=gpu_device, device_jpeg=device_jpeg)
     a = it.MultiTaskRecordIter(record_file, 4, (3, 64, 128), **kw)
@@ -249,5 +258,20 @@ def test_iterator_device_png_yields_the_same_batches(gpu_device, record_file, en
         assert not b.iter_next()
         a.reset(); b.reset()
     assert seen == 16
-    assert b.png_fallbacks == 4 and a.png_fallbacks == 0       # the interlaced and the RGB label map, once per epoch
+    assert b.png_fallbacks == fallbacks and a.png_fallbacks == 0
     assert b.jpeg_fallbacks == a.jpeg_fallbacks == (2 if device_jpeg else 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("enable_aug,prefetch,device_jpeg", [(True, True, False), (True, False, False), (False, True, False),
+                                                             (False, False, False), (True, True, True)])
+def test_iterator_device_png_yields_the_same_batches(gpu_device, record_file, enable_aug, prefetch, device_jpeg):
+    # the interlaced and the RGB label map, once per epoch
+    _same_batches(gpu_device, record_file, enable_aug, prefetch, device_jpeg, fallbacks=4)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prefetch", [True, False])
+def test_iterator_device_png_all_fallback_batches(gpu_device, interlaced_record_file, prefetch):
+    """the label bytes go up directly and nothing PNG-related is uploaded or launched: 8 fallbacks per epoch"""
+    _same_batches(gpu_device, interlaced_record_file, True, prefetch, False, fallbacks=16)
