@@ -256,23 +256,169 @@ __device__ __forceinline__ int block_scan_pred(bool f, int *s_w, int &total) {
   return off + wprefix;
 }
 
-// K2: one workgroup per sample: bipartite stage, threshold stage, mining.
-__global__ __launch_bounds__(kTB) void target_match_kernel(
-    const float4 *__restrict__ anchors, const float *__restrict__ labels, int A, int L, int lw,
-    float overlap_threshold, float neg_ratio, float neg_thresh, TargetWs ws) {
-  __shared__ float s_gt[kMaxLabels * 4];
-  __shared__ float s_ciou[kMaxLabels];
-  __shared__ int s_ca[kMaxLabels];
-  __shared__ int s_gflag[kMaxLabels];
-  __shared__ Best s_wb[kTB / 64];
-  __shared__ Best s_best;
-  __shared__ unsigned s_hist[256];
-  __shared__ int s_w[kTB / 64];
-  __shared__ int s_G, s_cnt, s_bin, s_kk;
+// The kk-th smallest of a workgroup's 32-bit keys (kk >= 1, at most the number of keys), by a radix select over four 8-bit
+// digits: T = that key, kk = its rank among the keys equal to T (1-based: the keys below T and the first kk of the `ties`
+// keys equal to T are the kk smallest).  visit(emit) calls emit(key) for each of this thread's live keys, the same keys on
+// each of its four calls.  s_hist: unsigned[256], s_res: int[3].  Every thread of the kTB-thread workgroup calls it; three
+// barriers per digit, the last one behind the final read of s_hist and ahead of every read of s_res.
+struct RadixCut { unsigned T; int kk, ties; };
+template <class Visit>
+__device__ __forceinline__ RadixCut block_radix_select(int kk, Visit visit, unsigned *s_hist, int *s_res) {
+  const int tid = threadIdx.x;
+  unsigned prefix = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = tid; i < 256; i += kTB) s_hist[i] = 0;
+    __syncthreads();
+    visit([&](unsigned key) {
+      const bool match = (shift == 24) ? true : ((key >> (shift + 8)) == (prefix >> (shift + 8)));
+      if (match) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
+    });
+    __syncthreads();
+    if (tid < 64) {      // first bin whose running count reaches kk: four bins per lane, a shuffle scan over the lanes
+      unsigned h[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) h[q] = s_hist[4 * tid + q];
+      const int mine = (int)(h[0] + h[1] + h[2] + h[3]);
+      int incl = mine;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if (tid >= d) incl += t; }
+      const unsigned long long reach = __ballot(incl >= kk);
+      const int first = __ffsll((long long)reach) - 1;     // (at least kk keys match the prefix: some lane reaches it)
+      if (tid == first) {
+        int cum = incl - mine, bin = 4 * tid;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (cum + (int)h[q] >= kk) { bin = 4 * tid + q; break; }
+          cum += (int)h[q];
+        }
+        s_res[0] = bin; s_res[1] = kk - cum; s_res[2] = (int)s_hist[bin];
+      }
+    }
+    __syncthreads();
+    prefix |= (unsigned)s_res[0] << shift;
+    kk = s_res[1];
+  }
+  return RadixCut{prefix, kk, s_res[2]};
+}
 
+// K2: one workgroup per sample: bipartite stage, threshold stage, mining.  The stages are stated once, in
+// target_match_body, over a store that answers what they ask of an anchor -- its flag (-1 ignore, 0 negative, 1 positive),
+// a sweep over "my anchors" with their best IoU and background key, a flush of the flags at every exit:
+//   * RegStore<kPer> (A <= kPer x 1024 anchors, target_match_reg_kernel; round 5): every per-anchor quantity where one
+//     compute unit can reach it without a trip to L2 -- best IoU and background key of a thread's kPer anchors in registers,
+//     the flags in LDS, the mining candidates as a bit mask.  The generic route makes some ten sweeps over global arrays, six
+//     dependent load rounds each (0.17 ms at 32 x 6132 when it served that shape, of which the column maxima, then G x A IoUs
+//     formed in the kernel, were about half).
+//   * GlobalStore (any A, target_match_kernel): ws.row_iou / ws.bgkey / ws.flag read on each sweep with stride 1024.
+struct MatchLds {
+  unsigned long long cmax[kMaxLabels];   // column maxima as target_rows_kernel packs them
+  float gt[kMaxLabels * 4];
+  float ciou[kMaxLabels];                // best unmatched anchor of every GT: IoU ...
+  int ca[kMaxLabels];                    // ... and index
+  int gflag[kMaxLabels];                 // GT is matched
+  Best wb[kTB / 64];
+  unsigned hist[256];
+  int w[kTB / 64];
+  int sel[3];
+  int G, cnt, consumed, npos, dup;
+};
+
+template <int kPer>
+struct RegStoreLds {
+  signed char flag[kPer * kTB];
+  unsigned used[kPer * kTB / 32];      // anchors that are some matchable GT's column maximum
+};
+template <int kPer>
+struct RegStore {
+  static constexpr bool kTracksBest = true;      // offers note_best: the matching body's all-at-once shortcut
+  RegStoreLds<kPer> &s;
+  const float *row_iou;
+  const unsigned *bgkey;
+  signed char *out;
+  const int A;
+  float riou[kPer];
+  unsigned bkey[kPer];
+  unsigned cmask = 0;
+  __device__ __forceinline__ RegStore(RegStoreLds<kPer> &lds, const TargetWs &ws, int b, int num_anchors)
+      : s(lds), row_iou(ws.row_iou + (size_t)b * num_anchors), bgkey(ws.bgkey + (size_t)b * num_anchors),
+        out(ws.flag + (size_t)b * num_anchors), A(num_anchors) {}
+  __device__ __forceinline__ void init() {     // (ends ahead of a barrier of the caller's)
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const int j = u * kTB + tid;
+      riou[u] = j < A ? row_iou[j] : 0.f;
+      bkey[u] = j < A ? bgkey[j] : 0u;
+      s.flag[j] = -1;
+    }
+    for (int i = tid; i < kPer * kTB / 32; i += kTB) s.used[i] = 0u;
+  }
+  __device__ __forceinline__ int flag(int j) const { return s.flag[j]; }
+  __device__ __forceinline__ void set_flag(int j, int v) { s.flag[j] = (signed char)v; }
+  // f(u, j) for this thread's slots u and their anchors j (j >= A: no anchor), as often in every thread
+  template <class F>
+  __device__ __forceinline__ void sweep(F f) {
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) f(u, u * kTB + (int)threadIdx.x);
+  }
+  __device__ __forceinline__ float iou(int u, int) const { return riou[u]; }
+  __device__ __forceinline__ unsigned key(int u, int) const { return bkey[u]; }
+  __device__ __forceinline__ void keep_cand(int u) { cmask |= 1u << u; }
+  template <class P>
+  __device__ __forceinline__ bool cand(int u, int, P) const { return (cmask >> u) & 1u; }
+  __device__ __forceinline__ bool note_best(int a) {      // was anchor a noted before?
+    const unsigned bit = 1u << (a & 31);
+    return atomicOr(&s.used[a >> 5], bit) & bit;
+  }
+  __device__ __forceinline__ void flush() {    // a thread's own anchors: nobody else writes them after the matching stage
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) { const int j = u * kTB + tid; if (j < A) out[j] = s.flag[j]; }
+  }
+};
+
+struct GlobalStore {
+  static constexpr bool kTracksBest = false;
+  const float *row_iou;
+  const unsigned *bgkey;
+  signed char *out;
+  const int A;
+  __device__ __forceinline__ GlobalStore(const TargetWs &ws, int b, int num_anchors)
+      : row_iou(ws.row_iou + (size_t)b * num_anchors), bgkey(ws.bgkey + (size_t)b * num_anchors),
+        out(ws.flag + (size_t)b * num_anchors), A(num_anchors) {}
+  __device__ __forceinline__ void init() { for (int j = threadIdx.x; j < A; j += kTB) out[j] = -1; }
+  __device__ __forceinline__ int flag(int j) const { return out[j]; }
+  __device__ __forceinline__ void set_flag(int j, int v) { out[j] = (signed char)v; }
+  template <class F>
+  __device__ __forceinline__ void sweep(F f) {
+    int u = 0;
+    for (int base = 0; base < A; base += kTB, ++u) f(u, base + (int)threadIdx.x);
+  }
+  __device__ __forceinline__ float iou(int, int j) const { return row_iou[j]; }
+  __device__ __forceinline__ unsigned key(int, int j) const { return bgkey[j]; }
+  __device__ __forceinline__ void keep_cand(int) {}
+  template <class P>
+  __device__ __forceinline__ bool cand(int u, int j, P fresh) const { return fresh(u, j); }   // (flags of candidates stay != 1)
+  __device__ __forceinline__ void flush() {}
+};
+
+// Both routes make the same decisions in the same order.  What a reviewer has to check where the routes once differed:
+//   * Column maxima come from target_rows_kernel's per-block partials (ws.cpart, written for every A) on both routes.  A ground
+//     truth whose best IoU is 0 gets "none" from them (IoU -1, anchor 0x7fffffff) where a G x A loop in this kernel once gave
+//     (0, lowest anchor): neither is ever picked -- the cut is IoU > 1e-6 --, the second form could only trigger a
+//     recomputation that changes nothing.
+//   * The mining cut: the wave-wide bin search finds the first bin whose running count reaches the rank, as a serial search
+//     does; keys below T are taken either way, and when every key equal to T is taken (kk == ties) no order among them is
+//     needed, so that exit chooses the same anchors as the index-ordered tie scan.
+//   * Only RegStore has the all-at-once shortcut below (its bit map of best anchors is sized by kPer x 1024); GlobalStore
+//     always takes the greedy loop, which is correct in every case -- the shortcut only skips it.
+template <class Store>
+__device__ __forceinline__ void target_match_body(
+    Store &st, MatchLds &s, const float4 *__restrict__ anchors, const float *__restrict__ labels, int A, int L, int lw,
+    float overlap_threshold, float neg_ratio, float neg_thresh, const TargetWs &ws) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float *lab = labels + (size_t)b * L * lw;
-  const int G = count_valid_gt(lab, L, lw, &s_G);
+  const int G = count_valid_gt(lab, L, lw, &s.G);
   if (tid == 0) {
     int err = 0;
     if (G < L) {  // CHECK_EQ x4 on the terminating row (multibox_target.cc:98-101)
@@ -283,422 +429,182 @@ __global__ __launch_bounds__(kTB) void target_match_kernel(
     ws.ngt[b] = G;
   }
   if (G == 0) return;
-  float *row_iou = ws.row_iou + (size_t)b * A;
   int *row_gt = ws.row_gt + (size_t)b * A;
-  unsigned *bgkey = ws.bgkey + (size_t)b * A;
-  signed char *flag = ws.flag + (size_t)b * A;
 
-  for (int i = tid; i < G * 4; i += kTB) s_gt[i] = lab[(i >> 2) * lw + 1 + (i & 3)];
-  for (int j = tid; j < A; j += kTB) flag[j] = -1;
+  st.init();
+  for (int i = tid; i < G * 4; i += kTB) s.gt[i] = lab[(i >> 2) * lw + 1 + (i & 3)];
+  // column maxima: the blocks' partials, one (GT, block) pair per thread
+  for (int k = tid; k < G; k += kTB) s.cmax[k] = 0ull;
+  if (tid == 0) { s.cnt = 0; s.dup = 0; }
   __syncthreads();
-
-  // column maxima: best unmatched anchor of every GT, one wave per GT
-  for (int k = wave; k < G; k += kTB / 64) {
-    const float gl = s_gt[4 * k], gt = s_gt[4 * k + 1], gr = s_gt[4 * k + 2], gb = s_gt[4 * k + 3];
-    Best v{-1.0f, 0x7fffffff, k};
-    for (int j = lane; j < A; j += 64) {
-      const float iou = target_iou(anchors[j], gl, gt, gr, gb);
-      if (iou > v.iou) { v.iou = iou; v.a = j; }
-    }
-    v = wave_best(v);
-    if (lane == 0) { s_ciou[k] = v.iou; s_ca[k] = v.a; s_gflag[k] = 0; }
+  for (int i = tid; i < G * ws.nblk; i += kTB) {
+    const int q = i / G, k = i - q * G;
+    const unsigned long long c = ws.cpart[((size_t)b * ws.nblk + q) * L + k];
+    if (c) atomicMax(&s.cmax[k], c);
+  }
+  __syncthreads();
+  for (int k = tid; k < G; k += kTB) {
+    const unsigned long long m = s.cmax[k];
+    const float ciou = m ? __uint_as_float((unsigned)(m >> 32)) : -1.0f;
+    const int ca = m ? (int)(0xffffffffu - (unsigned)m) : 0x7fffffff;
+    s.ciou[k] = ciou; s.ca[k] = ca; s.gflag[k] = 0;
+    if constexpr (Store::kTracksBest)
+      if (ciou > 1e-6f && st.note_best(ca)) s.dup = 1;     // would be picked, and another such GT shares its best anchor
   }
   __syncthreads();
 
+  // positives so far = npos + s.cnt (the threshold stage adds its own to s.cnt)
+  int npos = 0;
+  bool at_once = false;
+  if constexpr (Store::kTracksBest) at_once = !s.dup;
+  if (at_once) {
+    // No two ground truths that can be matched (IoU > 1e-6) share their best anchor: every pick of the greedy loop takes a GT
+    // with its column maximum, no pick changes another GT's maximum that matters (a GT at or below the cut may lose its
+    // anchor, but whatever replaces it is no larger and never picked) -- the result is all of them at once.
+    int add = 0;
+    for (int k = tid; k < G; k += kTB)
+      if (s.ciou[k] > 1e-6f) { st.set_flag(s.ca[k], 1); row_gt[s.ca[k]] = k; ++add; }
+    for (int m = 32; m >= 1; m >>= 1) add += __shfl_xor(add, m, 64);
+    if (lane == 0 && add) atomicAdd(&s.cnt, add);
+  } else
   // greedy bipartite matching (multibox_target.cc:113-149).  Round 4: wave 0 alone runs consecutive picks -- arg-max over
   // the unmatched GTs in the total order (IoU desc, anchor asc, gt asc), mark, next -- and the workgroup only meets at a
   // barrier when a pick consumed an anchor that is still some unmatched GT's column maximum, which then has to be recomputed
   // by all 1024 threads (rare: two ground truths sharing their best anchor).  The picks and their order are exactly those
   // of the one-pick-per-barrier loop this replaces (3 barriers x up to 40 picks per sample: ~0.2 ms of a 0.30 ms kernel).
-  int npos = 0;
   for (;;) {
     if (wave == 0) {
       int consumed = -1;                 // anchor whose consumption forces a recompute (-1: matching is complete)
       for (;;) {
         Best v{-2.0f, 0x7fffffff, -1};
         for (int k = lane; k < G; k += 64) {
-          if (s_gflag[k]) continue;
-          Best c{s_ciou[k], s_ca[k], k};
+          if (s.gflag[k]) continue;
+          Best c{s.ciou[k], s.ca[k], k};
           if (better(c, v)) v = c;
         }
         v = wave_best(v);
         if (v.k < 0 || !(v.iou > 1e-6f)) break;
-        if (lane == 0) { flag[v.a] = 1; row_gt[v.a] = v.k; s_gflag[v.k] = 1; }
+        if (lane == 0) { st.set_flag(v.a, 1); row_gt[v.a] = v.k; s.gflag[v.k] = 1; }
         ++npos;
-        // (the LDS accesses of one wave complete in order; the fence keeps hipcc from carrying s_gflag over in registers)
+        // (the LDS accesses of one wave complete in order; the fence keeps hipcc from carrying s.gflag over in registers)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         bool hit = false;
-        for (int k = lane; k < G; k += 64) hit |= (k != v.k && !s_gflag[k] && s_ca[k] == v.a);
+        for (int k = lane; k < G; k += 64) hit |= (k != v.k && !s.gflag[k] && s.ca[k] == v.a);
         if (__ballot(hit) != 0ull) { consumed = v.a; break; }
       }
-      if (lane == 0) { s_best.a = consumed; s_best.k = npos; }
+      if (lane == 0) { s.consumed = consumed; s.npos = npos; }
     }
     __syncthreads();
-    const int consumed = s_best.a;
-    npos = s_best.k;
+    const int consumed = s.consumed;
+    npos = s.npos;
     if (consumed < 0) break;
     // GTs whose best anchor was just consumed need a new column maximum
     for (int k = 0; k < G; ++k) {
-      if (s_gflag[k] || s_ca[k] != consumed) continue;   // block-uniform
-      const float gl = s_gt[4 * k], gt = s_gt[4 * k + 1], gr = s_gt[4 * k + 2], gb = s_gt[4 * k + 3];
+      if (s.gflag[k] || s.ca[k] != consumed) continue;   // block-uniform
+      const float gl = s.gt[4 * k], gt = s.gt[4 * k + 1], gr = s.gt[4 * k + 2], gb = s.gt[4 * k + 3];
       Best v{-1.0f, 0x7fffffff, k};
       for (int j = tid; j < A; j += kTB) {
-        if (flag[j] == 1) continue;
+        if (st.flag(j) == 1) continue;
         const float iou = target_iou(anchors[j], gl, gt, gr, gb);
         if (iou > v.iou) { v.iou = iou; v.a = j; }
       }
       v = wave_best(v);
-      if (lane == 0) s_wb[wave] = v;
+      if (lane == 0) s.wb[wave] = v;
       __syncthreads();
       if (wave == 0) {
-        Best u = lane < kTB / 64 ? s_wb[lane] : Best{-1.0f, 0x7fffffff, k};
+        Best u = lane < kTB / 64 ? s.wb[lane] : Best{-1.0f, 0x7fffffff, k};
         u = wave_best(u);
-        if (lane == 0) { s_ciou[k] = u.iou; s_ca[k] = u.a; }
+        if (lane == 0) { s.ciou[k] = u.iou; s.ca[k] = u.a; }
       }
       __syncthreads();
     }
   }
-  __syncthreads();
-
-  // threshold stage (multibox_target.cc:151-180) + candidate census
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  {
-    int add = 0;
-    if (overlap_threshold > 0) {
-      for (int j = tid; j < A; j += kTB) {
-        if (flag[j] == 1) continue;
-        if (row_iou[j] > overlap_threshold) { flag[j] = 1; ++add; }
-      }
-    }
-    for (int m = 32; m >= 1; m >>= 1) add += __shfl_xor(add, m, 64);
-    if (lane == 0 && add) atomicAdd(&s_cnt, add);
-  }
-  __syncthreads();
-  npos += s_cnt;
-  __syncthreads();
-
-  if (!(neg_ratio > 0)) {  // use all negatives (multibox_target.cc:242-249)
-    for (int j = tid; j < A; j += kTB) if (flag[j] != 1) flag[j] = 0;
-    return;
-  }
-  int num_negative = (int)((float)npos * neg_ratio);
-  if (num_negative > A - npos) num_negative = A - npos;
-  if (num_negative <= 0) return;
-
-  // candidates: not positive and best IoU below the mining threshold
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  {
-    int c = 0;
-    for (int j = tid; j < A; j += kTB) c += (flag[j] != 1 && row_iou[j] < neg_thresh) ? 1 : 0;
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-    if (lane == 0 && c) atomicAdd(&s_cnt, c);
-  }
-  __syncthreads();
-  const int ncand = s_cnt;
-  if (ncand < num_negative) {  // CHECK_GE(temp.size(), num_negative), multibox_target.cc:236
-    if (tid == 0) ws.err[b] = 3;
-    num_negative = ncand;
-  }
-  if (num_negative == ncand) {
-    for (int j = tid; j < A; j += kTB)
-      if (flag[j] != 1 && row_iou[j] < neg_thresh) flag[j] = 0;
-    return;
-  }
-
-  // radix-select the num_negative-th smallest P(background); ties go to the
-  // lower anchor index ( == std::stable_sort on -prob, multibox_target.cc:58-70,237 )
-  unsigned prefix = 0;
-  int kk = num_negative;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = tid; i < 256; i += kTB) s_hist[i] = 0;
-    __syncthreads();
-    for (int j = tid; j < A; j += kTB) {
-      if (flag[j] == 1 || !(row_iou[j] < neg_thresh)) continue;
-      const unsigned key = bgkey[j];
-      const bool match = (shift == 24) ? true : ((key >> (shift + 8)) == (prefix >> (shift + 8)));
-      if (match) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int cum = 0, bin = 0;
-      for (; bin < 256; ++bin) {
-        const int h = (int)s_hist[bin];
-        if (cum + h >= kk) break;
-        cum += h;
-      }
-      s_bin = bin; s_kk = kk - cum;
-    }
-    __syncthreads();
-    prefix |= (unsigned)s_bin << shift;
-    kk = s_kk;
-    __syncthreads();
-  }
-  const unsigned T = prefix;
-  int taken_ties = 0;
-  for (int base = 0; base < A; base += kTB) {
-    const int j = base + tid;
-    bool cand = false; unsigned key = 0;
-    if (j < A) { cand = (flag[j] != 1 && row_iou[j] < neg_thresh); key = bgkey[j]; }
-    const bool tie = cand && key == T;
-    int total;
-    const int off = block_scan_pred(tie, s_w, total);
-    if (cand && (key < T || (tie && taken_ties + off < kk))) flag[j] = 0;
-    taken_ties += total;
-  }
-}
-
-// K2, A <= kPer x 1024 anchors (round 5): the same stages with every per-anchor quantity where one compute unit can reach it
-// without a trip to L2 -- best IoU and background key of a thread's kPer anchors in registers, the flags in LDS -- and the
-// column maxima merged from target_rows_kernel's per-block partials instead of G x A IoUs formed here.  The generic kernel
-// above made some ten sweeps over global arrays, six dependent load rounds each (0.17 ms at 32 x 6132, of which the column
-// maxima were about half).  Decisions and their order are those of the generic kernel.
-template <int kPer>
-__global__ __launch_bounds__(kTB) void target_match_reg_kernel(
-    const float4 *__restrict__ anchors, const float *__restrict__ labels, int A, int L, int lw,
-    float overlap_threshold, float neg_ratio, float neg_thresh, TargetWs ws) {
-  __shared__ float s_gt[kMaxLabels * 4];
-  __shared__ float s_ciou[kMaxLabels];
-  __shared__ int s_ca[kMaxLabels];
-  __shared__ int s_gflag[kMaxLabels];
-  __shared__ Best s_wb[kTB / 64];
-  __shared__ Best s_best;
-  __shared__ unsigned s_hist[256];
-  __shared__ int s_w[kTB / 64];
-  __shared__ int s_G, s_cnt, s_bin, s_kk, s_ties, s_dup;
-  __shared__ signed char s_flag[kPer * kTB];
-  __shared__ unsigned long long s_cmax[kMaxLabels];
-  __shared__ unsigned s_used[kPer * kTB / 32];      // anchors that are some matchable GT's column maximum
-
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float *lab = labels + (size_t)b * L * lw;
-  const int G = count_valid_gt(lab, L, lw, &s_G);
-  if (tid == 0) {
-    int err = 0;
-    if (G < L) {  // CHECK_EQ x4 on the terminating row (multibox_target.cc:98-101)
-      const float *row = lab + G * lw;
-      if (row[1] != -1.0f || row[2] != -1.0f || row[3] != -1.0f || row[4] != -1.0f) err = 2;
-    }
-    ws.err[b] = err;
-    ws.ngt[b] = G;
-  }
-  if (G == 0) return;
-  int *row_gt = ws.row_gt + (size_t)b * A;
-  signed char *flag = ws.flag + (size_t)b * A;
-
-  float riou[kPer];
-  unsigned key[kPer];
-#pragma unroll
-  for (int u = 0; u < kPer; ++u) {
-    const int j = u * kTB + tid;
-    riou[u] = j < A ? ws.row_iou[(size_t)b * A + j] : 0.f;
-    key[u] = j < A ? ws.bgkey[(size_t)b * A + j] : 0u;
-    s_flag[j] = -1;
-  }
-  auto flush = [&]() {      // a thread's own anchors: nobody else writes them after the matching stage
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) { const int j = u * kTB + tid; if (j < A) flag[j] = s_flag[j]; }
-  };
-  for (int i = tid; i < G * 4; i += kTB) s_gt[i] = lab[(i >> 2) * lw + 1 + (i & 3)];
-  // column maxima: the blocks' partials, one (GT, block) pair per thread
-  for (int k = tid; k < G; k += kTB) s_cmax[k] = 0ull;
-  for (int i = tid; i < kPer * kTB / 32; i += kTB) s_used[i] = 0u;
-  if (tid == 0) s_dup = 0;
-  __syncthreads();
-  for (int i = tid; i < G * ws.nblk; i += kTB) {
-    const int q = i / G, k = i - q * G;
-    const unsigned long long c = ws.cpart[((size_t)b * ws.nblk + q) * L + k];
-    if (c) atomicMax(&s_cmax[k], c);
-  }
-  __syncthreads();
-  for (int k = tid; k < G; k += kTB) {
-    const unsigned long long m = s_cmax[k];
-    const float ciou = m ? __uint_as_float((unsigned)(m >> 32)) : -1.0f;
-    const int ca = m ? (int)(0xffffffffu - (unsigned)m) : 0x7fffffff;
-    s_ciou[k] = ciou; s_ca[k] = ca; s_gflag[k] = 0;
-    if (ciou > 1e-6f) {       // would be picked: does another such GT share its best anchor?
-      const unsigned bit = 1u << (ca & 31);
-      if (atomicOr(&s_used[ca >> 5], bit) & bit) s_dup = 1;
-    }
-  }
-  __syncthreads();
-
-  // greedy bipartite matching (multibox_target.cc:113-149), as in the generic kernel: wave 0 runs consecutive picks, the
-  // workgroup meets only when a pick consumed an anchor that is still some unmatched GT's column maximum
-  int npos = 0;
-  if (!s_dup) {
-    // No two ground truths that can be matched (IoU > 1e-6) share their best anchor: every pick of the greedy loop takes a GT
-    // with its column maximum, no pick changes another GT's maximum that matters (a GT at or below the cut may lose its
-    // anchor, but whatever replaces it is no larger and never picked) -- the result is all of them at once.
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    int add = 0;
-    for (int k = tid; k < G; k += kTB)
-      if (s_ciou[k] > 1e-6f) { s_flag[s_ca[k]] = 1; row_gt[s_ca[k]] = k; ++add; }
-    for (int m = 32; m >= 1; m >>= 1) add += __shfl_xor(add, m, 64);
-    if (lane == 0 && add) atomicAdd(&s_cnt, add);
-    __syncthreads();
-    npos = s_cnt;
-  } else
-  for (;;) {
-    if (wave == 0) {
-      int consumed = -1;
-      for (;;) {
-        Best v{-2.0f, 0x7fffffff, -1};
-        for (int k = lane; k < G; k += 64) {
-          if (s_gflag[k]) continue;
-          Best c{s_ciou[k], s_ca[k], k};
-          if (better(c, v)) v = c;
-        }
-        v = wave_best(v);
-        if (v.k < 0 || !(v.iou > 1e-6f)) break;
-        if (lane == 0) { s_flag[v.a] = 1; row_gt[v.a] = v.k; s_gflag[v.k] = 1; }
-        ++npos;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        bool hit = false;
-        for (int k = lane; k < G; k += 64) hit |= (k != v.k && !s_gflag[k] && s_ca[k] == v.a);
-        if (__ballot(hit) != 0ull) { consumed = v.a; break; }
-      }
-      if (lane == 0) { s_best.a = consumed; s_best.k = npos; }
-    }
-    __syncthreads();
-    const int consumed = s_best.a;
-    npos = s_best.k;
-    if (consumed < 0) break;
-    for (int k = 0; k < G; ++k) {
-      if (s_gflag[k] || s_ca[k] != consumed) continue;   // block-uniform
-      const float gl = s_gt[4 * k], gt = s_gt[4 * k + 1], gr = s_gt[4 * k + 2], gb = s_gt[4 * k + 3];
-      Best v{-1.0f, 0x7fffffff, k};
-      for (int j = tid; j < A; j += kTB) {
-        if (s_flag[j] == 1) continue;
-        const float iou = target_iou(anchors[j], gl, gt, gr, gb);
-        if (iou > v.iou) { v.iou = iou; v.a = j; }
-      }
-      v = wave_best(v);
-      if (lane == 0) s_wb[wave] = v;
-      __syncthreads();
-      if (wave == 0) {
-        Best u = lane < kTB / 64 ? s_wb[lane] : Best{-1.0f, 0x7fffffff, k};
-        u = wave_best(u);
-        if (lane == 0) { s_ciou[k] = u.iou; s_ca[k] = u.a; }
-      }
-      __syncthreads();
-    }
-  }
-  if (tid == 0) s_cnt = 0;
   __syncthreads();
 
   // threshold stage (multibox_target.cc:151-180)
   {
     int add = 0;
-    if (overlap_threshold > 0) {
-#pragma unroll
-      for (int u = 0; u < kPer; ++u) {
-        const int j = u * kTB + tid;
-        if (j < A && s_flag[j] != 1 && riou[u] > overlap_threshold) { s_flag[j] = 1; ++add; }
-      }
-    }
+    if (overlap_threshold > 0)
+      st.sweep([&](int u, int j) {
+        if (j < A && st.flag(j) != 1 && st.iou(u, j) > overlap_threshold) { st.set_flag(j, 1); ++add; }
+      });
     for (int m = 32; m >= 1; m >>= 1) add += __shfl_xor(add, m, 64);
-    if (lane == 0 && add) atomicAdd(&s_cnt, add);
+    if (lane == 0 && add) atomicAdd(&s.cnt, add);
   }
   __syncthreads();
-  npos += s_cnt;
+  npos += s.cnt;
   __syncthreads();
 
   if (!(neg_ratio > 0)) {  // use all negatives (multibox_target.cc:242-249)
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) { const int j = u * kTB + tid; if (s_flag[j] != 1) s_flag[j] = 0; }
-    flush();
+    st.sweep([&](int, int j) { if (j < A && st.flag(j) != 1) st.set_flag(j, 0); });
+    st.flush();
     return;
   }
   int num_negative = (int)((float)npos * neg_ratio);
   if (num_negative > A - npos) num_negative = A - npos;
-  if (num_negative <= 0) { flush(); return; }
+  if (num_negative <= 0) { st.flush(); return; }
 
   // candidates: not positive and best IoU below the mining threshold
-  unsigned cand = 0;
-  if (tid == 0) s_cnt = 0;
+  auto fresh = [&](int u, int j) { return j < A && st.flag(j) != 1 && st.iou(u, j) < neg_thresh; };
+  if (tid == 0) s.cnt = 0;
   __syncthreads();
   {
     int c = 0;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const int j = u * kTB + tid;
-      if (j < A && s_flag[j] != 1 && riou[u] < neg_thresh) { cand |= 1u << u; ++c; }
-    }
+    st.sweep([&](int u, int j) { if (fresh(u, j)) { st.keep_cand(u); ++c; } });
     for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-    if (lane == 0 && c) atomicAdd(&s_cnt, c);
+    if (lane == 0 && c) atomicAdd(&s.cnt, c);
   }
   __syncthreads();
-  const int ncand = s_cnt;
+  const int ncand = s.cnt;
   if (ncand < num_negative) {  // CHECK_GE(temp.size(), num_negative), multibox_target.cc:236
     if (tid == 0) ws.err[b] = 3;
     num_negative = ncand;
   }
   if (num_negative == ncand) {
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) if ((cand >> u) & 1u) s_flag[u * kTB + tid] = 0;
-    flush();
+    st.sweep([&](int u, int j) { if (st.cand(u, j, fresh)) st.set_flag(j, 0); });
+    st.flush();
     return;
   }
 
   // radix-select the num_negative-th smallest P(background); ties go to the lower anchor index
   // ( == std::stable_sort on -prob, multibox_target.cc:58-70,237 )
-  unsigned prefix = 0;
-  int kk = num_negative;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = tid; i < 256; i += kTB) s_hist[i] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      if (!((cand >> u) & 1u)) continue;
-      const bool match = (shift == 24) ? true : ((key[u] >> (shift + 8)) == (prefix >> (shift + 8)));
-      if (match) atomicAdd(&s_hist[(key[u] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (wave == 0) {      // first bin whose running count reaches kk: four bins per lane, a shuffle scan over the lanes
-      unsigned h[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) h[q] = s_hist[4 * lane + q];
-      const int mine = (int)(h[0] + h[1] + h[2] + h[3]);
-      int incl = mine;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
-      const unsigned long long reach = __ballot(incl >= kk);
-      const int first = __ffsll((long long)reach) - 1;     // (ncand >= kk candidates match the prefix: some lane reaches it)
-      if (lane == first) {
-        int cum = incl - mine, bin = 4 * lane;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (cum + (int)h[q] >= kk) { bin = 4 * lane + q; break; }
-          cum += (int)h[q];
-        }
-        s_bin = bin; s_kk = kk - cum; s_ties = (int)s_hist[bin];
-      }
-    }
-    __syncthreads();
-    prefix |= (unsigned)s_bin << shift;
-    kk = s_kk;
-  }
-  const unsigned T = prefix;
-  if (kk == s_ties) {       // every anchor at the cut is taken: no order among them is needed (the usual case)
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) if (((cand >> u) & 1u) && key[u] <= T) s_flag[u * kTB + tid] = 0;
-    flush();
+  const RadixCut cut = block_radix_select(
+      num_negative,
+      [&](auto emit) { st.sweep([&](int u, int j) { if (st.cand(u, j, fresh)) emit(st.key(u, j)); }); }, s.hist, s.sel);
+  if (cut.kk == cut.ties) {       // every anchor at the cut is taken: no order among them is needed (the usual case)
+    st.sweep([&](int u, int j) { if (st.cand(u, j, fresh) && st.key(u, j) <= cut.T) st.set_flag(j, 0); });
+    st.flush();
     return;
   }
   int taken_ties = 0;
-#pragma unroll
-  for (int u = 0; u < kPer; ++u) {
-    const bool c = (cand >> u) & 1u;
-    const bool tie = c && key[u] == T;
+  st.sweep([&](int u, int j) {
+    const bool c = st.cand(u, j, fresh);
+    const unsigned key = c ? st.key(u, j) : 0u;
+    const bool tie = c && key == cut.T;
     int total;
-    const int off = block_scan_pred(tie, s_w, total);
-    if (c && (key[u] < T || (tie && taken_ties + off < kk))) s_flag[u * kTB + tid] = 0;
+    const int off = block_scan_pred(tie, s.w, total);
+    if (c && (key < cut.T || (tie && taken_ties + off < cut.kk))) st.set_flag(j, 0);
     taken_ties += total;
-  }
-  flush();
+  });
+  st.flush();
+}
+
+__global__ __launch_bounds__(kTB) void target_match_kernel(
+    const float4 *__restrict__ anchors, const float *__restrict__ labels, int A, int L, int lw,
+    float overlap_threshold, float neg_ratio, float neg_thresh, TargetWs ws) {
+  __shared__ MatchLds s;
+  GlobalStore st(ws, blockIdx.x, A);
+  target_match_body(st, s, anchors, labels, A, L, lw, overlap_threshold, neg_ratio, neg_thresh, ws);
+}
+
+template <int kPer>
+__global__ __launch_bounds__(kTB) void target_match_reg_kernel(
+    const float4 *__restrict__ anchors, const float *__restrict__ labels, int A, int L, int lw,
+    float overlap_threshold, float neg_ratio, float neg_thresh, TargetWs ws) {
+  __shared__ MatchLds s;
+  __shared__ RegStoreLds<kPer> sl;
+  RegStore<kPer> st(sl, ws, blockIdx.x, A);
+  target_match_body(st, s, anchors, labels, A, L, lw, overlap_threshold, neg_ratio, neg_thresh, ws);
 }
 
 // K3: expand flags into the three outputs (multibox_target.cc:251-281; init
@@ -900,43 +806,10 @@ __global__ __launch_bounds__(kTB) void det_decode_sort_kernel(
   __syncthreads();
   if (select) {
     unsigned long long *sel = keys + n2cap;
-    unsigned prefix = 0;
-    int kk = nkeep;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      for (int i = tid; i < 256; i += kTB) s_hist[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < V; i += kTB) {
-        const unsigned hi = (unsigned)(keys[i] >> 32);
-        const bool match = (shift == 24) ? true : ((hi >> (shift + 8)) == (prefix >> (shift + 8)));
-        if (match) atomicAdd(&s_hist[(hi >> shift) & 255u], 1u);
-      }
-      __syncthreads();
-      if (tid < 64) {      // first bin whose running count reaches kk: four bins per lane, a shuffle scan over the lanes
-        unsigned h[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) h[q] = s_hist[4 * tid + q];
-        const int mine = (int)(h[0] + h[1] + h[2] + h[3]);
-        int incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if (tid >= d) incl += t; }
-        const unsigned long long reach = __ballot(incl >= kk);
-        const int first = __ffsll((long long)reach) - 1;
-        if (tid == first) {
-          int cum = incl - mine, bin = 4 * tid;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            if (cum + (int)h[q] >= kk) { bin = 4 * tid + q; break; }
-            cum += (int)h[q];
-          }
-          s_sel[0] = bin; s_sel[1] = kk - cum; s_sel[2] = (int)s_hist[bin];
-        }
-      }
-      __syncthreads();
-      prefix |= (unsigned)s_sel[0] << shift;
-      kk = s_sel[1];
-    }
-    const unsigned T = prefix;
-    const int nless = nkeep - kk, ties = s_sel[2];
+    const RadixCut cut = block_radix_select(
+        nkeep, [&](auto emit) { for (int i = tid; i < V; i += kTB) emit((unsigned)(keys[i] >> 32)); }, s_hist, s_sel);
+    const unsigned T = cut.T;
+    const int kk = cut.kk, nless = nkeep - kk, ties = cut.ties;
     if (tid == 0) s_sel[3] = 0;
     __syncthreads();
     if (kk == ties) {          // every row at the cut is kept: any slot will do, the sort below orders them

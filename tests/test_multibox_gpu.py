@@ -78,8 +78,9 @@ def test_target_small_random(gpu_device, seed, ratio, thr, nthr):
 
 @pytest.mark.parametrize("hw,batch", [((512, 512), 8), ((512, 1024), 3), ((512, 512), 32)])
 def test_target_dspnet_shape(gpu_device, hw, batch):
-    """the training configuration of symbol/multitask_symbol_builder.py:517-521 (round 4: also at the headline batch, 32 x 6132
-    anchors, against the oracle -- the greedy matching loop of target_match_kernel was rewritten this round)"""
+    """the training configuration of symbol/multitask_symbol_builder.py:517-521, against the oracle on both routes of the
+    matching kernel: 6132 anchors (also at the headline batch, 32) take target_match_reg_kernel<8>, the 12264 anchors of
+    512 x 1024 take target_match_kernel; the two share one body (multibox.hip: target_match_body)"""
     anc = mc.r50_anchors(*hw)
     lab, pred = mc.target_inputs(anc, batch=batch, seed=233)
     got = run_target(anc, lab, pred, overlap_threshold=.5, ignore_label=-1,
@@ -98,27 +99,100 @@ def test_target_all_ties_resolved_by_index(gpu_device):
     run_target(anc, lab, pred, negative_mining_ratio=3)
 
 
-def test_target_duplicate_and_overlapping_gt(gpu_device):
-    """several GTs share their best anchor -> the column-maximum recomputation path"""
-    anc = mc.r50_anchors(512, 512)
-    lab = -np.ones((3, 200, 6), np.float32)
+def duplicate_gt_labels(num_labels):
+    lab = -np.ones((3, num_labels, 6), np.float32)
     for k in range(12):
         lab[0, k] = [k % 8, .30, .30, .62, .62, .1 * (k % 9)]            # identical boxes
     for k in range(30):
         lab[1, k] = [k % 8, .2 + .002 * k, .2, .5 + .002 * k, .5, .5]    # near-duplicates
     lab[2, 0] = [0, .0, .0, .004, .004, .3]                              # tiny box, IoU ~ 0
     lab[2, 1] = [1, .9, .9, .9, .9, .3]                                  # zero-area box
+    return lab
+
+
+def test_target_duplicate_and_overlapping_gt(gpu_device):
+    """several GTs share their best anchor -> the column-maximum recomputation path"""
+    anc = mc.r50_anchors(512, 512)
+    lab = duplicate_gt_labels(200)
     gen = np.random.default_rng(3)
     pred = gen.standard_normal((3, 9, anc.shape[1])).astype(np.float32)
     run_target(anc, lab, pred, negative_mining_ratio=3)
 
 
-@pytest.mark.parametrize("num_anchors", [3382, 256 * 5 + 7, 256 * 9 + 33, 64 * 3 + 50, 6132])
+# The matching stages on both sides of the dispatch rule of dspn_multibox_target_f32 (num_anchors <= 8 * 1024: per-anchor
+# quantities in registers and LDS, target_match_reg_kernel<8>; more: in global memory, target_match_kernel): the last size
+# of the first route, the first of the second, a table ending in a partial wave, and the full 512 x 1024 table.
+ROUTE_SIZES = [8192, 8193, 8192 + 64 * 3 + 50, 12264]
+_WIDE = []
+
+
+def route_anchors(n):
+    if not _WIDE:
+        _WIDE.append(mc.r50_anchors(512, 1024))
+    return _WIDE[0][:, :n].copy()
+
+
+@pytest.mark.parametrize("n", ROUTE_SIZES)
+@pytest.mark.parametrize("pred_kind", ["zero", "random"])
+def test_target_routes_duplicate_gt(gpu_device, n, pred_kind):
+    """12 identical boxes (12 greedy picks on shared best anchors: the recomputation path), 30 near-duplicates, a tiny and a
+    zero-area box.  Zero cls_pred makes every key equal (mining cuts inside a run of ties: the index-ordered tie scan);
+    random cls_pred makes them distinct (the radix select and its kk == ties exit)."""
+    anc, lab = route_anchors(n), duplicate_gt_labels(40)
+    pred = np.zeros((3, 9, n), np.float32)
+    if pred_kind == "random":
+        pred = np.random.default_rng(3).standard_normal((3, 9, n)).astype(np.float32)
+    ct = run_target(anc, lab, pred, negative_mining_ratio=3)[2]
+    # (the CPU oracle's counts: the case must not quietly stop reaching the paths)
+    assert ((ct > 0).sum(axis=1) == [12, 30, 1]).all() and ((ct == 0).sum(axis=1) == [36, 90, 3]).all()
+
+
+@pytest.mark.parametrize("n", ROUTE_SIZES)
+def test_target_routes_every_candidate_and_all_negatives(gpu_device, n):
+    """negative_mining_ratio 1e4 asks for more negatives than there are candidates' worth of anchors: every candidate is
+    taken (the num_negative == ncand exit); the second sample has no ground truth (the G == 0 return).  On the full table
+    some anchors lie between the mining threshold (.5) and the overlap threshold (.7), neither positive nor candidate: fewer
+    candidates than requested, the reference's CHECK_GE, which the oracle reports as -3 and the operator as a deferred code
+    with the request clamped -- the same outputs.  negative_mining_ratio -1: the all-negatives exit."""
+    anc = route_anchors(n)
+    lab, pred = mc.target_inputs(anc, batch=2, num_labels=40, max_gt=12, seed=9)
+    kw = dict(negative_mining_ratio=1e4, overlap_threshold=.7)
+    exp, rc = om.multibox_target(anc, lab, pred, return_code=True, **kw)
+    a = dev(anc)
+    got = host(op.MultiBoxTarget(a, dev(lab), dev(pred), **kw))
+    mc.assert_target_equal(got, exp)
+    ct = got[2]
+    assert (ct[1] == -1).all()
+    assert rc == (-3 if n == 12264 else 0)
+    if rc == 0:
+        op.MultiBoxTarget_check(2, a.device)
+        assert (ct[0] > 0).sum() == 6 and (ct[0] == 0).sum() == n - 6
+    else:
+        assert (ct[0] > 0).sum() == 6 and 0 < (ct[0] == -1).sum() < 100
+        with pytest.raises(DspnError, match="fewer mining candidates"):
+            op.MultiBoxTarget_check(2, a.device)
+    ct = run_target(anc, lab, pred, negative_mining_ratio=-1, overlap_threshold=.7)[2]
+    op.MultiBoxTarget_check(2, a.device)
+    assert (ct[0] > 0).sum() == 6 and (ct[0] == 0).sum() == n - 6 and (ct[1] == -1).all()
+
+
+def test_target_routes_full_label_table(gpu_device):
+    """G == L (no terminator row) on the first size of the generic route"""
+    anc = route_anchors(8193)
+    lab, pred = mc.target_inputs(anc, batch=2, num_labels=7, num_classes=3, max_gt=7, seed=8)
+    lab[0] = mc.target_inputs(anc, batch=1, num_labels=7, num_classes=3, max_gt=7, seed=21)[0][0]
+    lab[0, :, 0] = np.abs(lab[0, :, 0])          # no -1 terminator at all: G == L
+    lab[0, :, 1:5] = np.abs(lab[0, :, 1:5])
+    run_target(anc, lab, pred, negative_mining_ratio=3, overlap_threshold=0.1)
+
+
+@pytest.mark.parametrize("num_anchors", [3382, 256 * 5 + 7, 256 * 9 + 33, 64 * 3 + 50, 6132, 8193, 8192 + 64 * 3 + 50])
 def test_target_best_anchor_in_the_last_partial_wave(gpu_device, num_anchors):
     """round 5: the best anchor of a ground truth is found per 64-anchor wave inside target_rows_kernel (a butterfly over the
     wave's lanes); ground truths that coincide with the LAST anchors of the table have their column maximum in a wave whose
-    upper lanes hold no anchor (the inceptionv3 1024x512 graph, 3382 anchors, met this case)"""
-    anc = mc.r50_anchors(512, 512)[:, :num_anchors].copy()
+    upper lanes hold no anchor (the inceptionv3 1024x512 graph, 3382 anchors, met this case).  The sizes above 8192, cut from
+    the 512 x 1024 table, take the generic route of the matching kernel, which merges the same per-block partials"""
+    anc = mc.r50_anchors(512, 512)[:, :num_anchors].copy() if num_anchors <= 6132 else route_anchors(num_anchors)
     lab = -np.ones((2, 40, 6), np.float32)
     for k, j in enumerate(range(num_anchors - 1, num_anchors - 12, -2)):
         box = np.clip(anc[0, j], 0.0, 1.0)
@@ -253,6 +327,17 @@ def test_detection_equal_scores_keep_anchor_order(gpu_device):
     prob = np.full((2, 3, A), 1 / 3, np.float32)
     loc = np.zeros((2, A * 5), np.float32)
     run_detection(anc, prob, loc, nms_threshold=0.7)
+
+
+def test_detection_equal_scores_across_the_topk_cut(gpu_device):
+    """268 anchors with one score: the key capacity is 512 and nms_topk 100 a selected list of capacity 128, so the rows are
+    SELECTED ahead of the sort, and the cut falls inside a run of equal keys: the select's position-ordered tie scan"""
+    anc = mc.small_anchors(8, 8)
+    A = anc.shape[1]
+    assert A == 268
+    prob = np.full((2, 3, A), 1 / 3, np.float32)
+    loc = np.zeros((2, A * 5), np.float32)
+    run_detection(anc, prob, loc, nms_threshold=0.7, nms_topk=100)
 
 
 def test_detection_single_class_and_no_valid_rows(gpu_device):
