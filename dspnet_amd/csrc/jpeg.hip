@@ -7,7 +7,8 @@
 //                        wave reads 1 KiB of consecutive coefficients), the block turns through LDS, lane t runs column t of pass 1
 //                        and row t of pass 2 and stores 8 samples.  No DC-only shortcut: the general form gives the same bits, and
 //                        every lane runs the same instructions.
-//   jpeg_colour_kernel : chroma upsampling ("fancy", over the real extent, edges replicated) + YCbCr -> RGB, planes -> the
+//   jpeg_colour_kernel : chroma upsampling ("fancy", over the real extent, edges replicated; box for a chroma plane of at most
+//                        two columns) + YCbCr -> RGB, planes -> the
 //                        (h, w, 3) bytes at img_offset.  One thread per 4 pixels of a row: one dword of luma, the chroma
 //                        neighbours from L1, 12 output bytes as 3 dwords where the address allows it.
 // Per image of h x w pixels with luma sampling H x V (n = samples per pixel: 3, 2 or 1.5; 1 for grey), over the padded grids:
@@ -173,6 +174,12 @@ __device__ __forceinline__ void chroma4(const unsigned char *__restrict__ plane,
     const unsigned w = *reinterpret_cast<const unsigned *>(plane + (long long)y * stride + x0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) out[j] = (int)((w >> (8 * j)) & 255u);
+    return;
+  }
+  if (cw <= 2) {                                    // libjpeg-turbo's choice for a plane of one or two columns: box, down the rows too
+    const unsigned char *r = plane + (long long)(vs == 2 ? y >> 1 : y) * stride;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const int c = (x0 + j) >> 1; out[j] = r[c > cw - 1 ? cw - 1 : c]; }
     return;
   }
   const int c0 = x0 >> 1;

@@ -27,6 +27,7 @@ assert SAMPLE.itemsize == 272
 REASONS = ("ok", "progressive", "extended sequential", "arithmetic coding", "lossless or hierarchical",
            "sample precision is not 8 bits", "neither 1 nor 3 components", "unsupported sampling factors",
            "more than one scan", "colour transform is not YCbCr", "16-bit quantisation table")
+MAX_BATCH = 1024                                               # kMaxB of csrc/jpeg.hip: descriptors of one reconstruct call
 
 _lib.register({
     "dspn_jpeg_probe": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
@@ -142,6 +143,9 @@ class CodedBatch(staging.CodedBatch):
 def decode_batch(payloads, device):
     """decode a list of JPEG byte strings -> list of (h, w, 3) uint8 RGB tensors on `device`, views of one pool.
     ValueError (naming the reason) for a stream outside the supported set, DspnError for a malformed one."""
+    payloads = list(payloads)
+    if len(payloads) > MAX_BATCH:                               # before any stream is decoded: the entry would refuse it after all of them
+        raise ValueError("decode_batch: %d streams, the batch limit of one call is %d" % (len(payloads), MAX_BATCH))
     infos = []
     for i, p in enumerate(payloads):
         rc, info = probe_info(p)

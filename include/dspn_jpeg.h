@@ -20,6 +20,8 @@
  *     2 x 2: rows s = 3 near + far (far: the row above for even output rows, below for odd ones), then
  *            even = (3 s[x] + s[x - 1] + 8) >> 4, odd = (3 s[x] + s[x + 1] + 7) >> 4
  *     2 x 1: even = (3 p[x] + p[x - 1] + 1) >> 2, odd = (3 p[x] + p[x + 1] + 2) >> 2
+ *     a chroma plane of at most two columns (images up to 4 pixels wide): each sample repeated 2 x 2 or 2 x 1 instead,
+ *            down the rows as well (libjpeg-turbo takes the triangle filter only for downsampled_width > 2)
  *   colour, F(x) = int(x * 65536 + 0.5), cb -= 128, cr -= 128, arithmetic shifts, clamp to 0..255:
  *     R = Y + ((F(1.402) cr + 32768) >> 16); B = Y + ((F(1.772) cb + 32768) >> 16);
  *     G = Y + ((-F(0.34414) cb + 32768 - F(0.71414) cr) >> 16); one component writes Y to all three channels.

@@ -67,3 +67,87 @@ def pillow_real_blocks(case):
         out[o:o + 64 * bw * bh] = plane[:bh, :bw].reshape(-1)
     out.setflags(write=False)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The low-level harness of tests/test_jpeg_encode_gpu.py and tests/test_pipeline_edges_gpu.py
+GUARD = 256                                                    # guard bytes (a whole number of int16 blocks and of dwords)
+# the eight images a 1024-descriptor call repeats: all four layouts, odd sizes (odd image offsets), both qualities
+BATCH_CASES = [(56, 72, "4:4:4", 95, "noise"), (40, 88, "4:2:2", 30, "noise"), (48, 80, "4:2:0", 95, "smooth"),
+               (72, 56, "grey", 95, "noise"), (33, 95, "4:4:4", 30, "smooth"), (71, 49, "4:2:0", 95, "noise"),
+               (64, 64, "4:2:2", 95, "noise"), (47, 91, "grey", 30, "noise")]
+
+
+@functools.lru_cache(maxsize=None)
+def reference_blocks(case):
+    """ref_jpeg's reading of Pillow's stream, cut to the real grids: per component (blocks_h, blocks_w, 64); read-only"""
+    import ref_jpeg
+    data = pillow_file(case)
+    P = ref_jpeg.parse(data)
+    planes = ref_jpeg.coefficients(data, P)
+    s, _ = sample_of(case)
+    return [planes[c][:int(s["blocks_h"][c]), :int(s["blocks_w"][c])].copy() for c in range(P["ncomp"])]
+
+
+def describe_batch(cases, skip=()):
+    """descriptors of one dspn_jpeg_encode_blocks_batch_u8 call over `cases` with GUARD bytes around every sample's pixels
+    and coefficients -> (samples, [(pixel offset, image)], int16 count of the coefficient pool, bytes of the image pool)"""
+    samples = np.zeros(len(cases), je.SAMPLE)
+    pix, co, io_ = [], GUARD // 2, 0
+    for k, case in enumerate(cases):
+        img = pixels(case)
+        io_ += GUARD
+        pix.append((io_, img))
+        n = je.fill_sample(samples[k], case[1], case[0], 1 if case[2] == "grey" else 3, je.SUBSAMPLING.get(case[2], (1, 1)),
+                           je.quant_tables(case[3]), co, io_)
+        samples[k]["skip"] = int(k in skip)
+        co += n + GUARD // 2
+        io_ += img.size + GUARD
+    return samples, pix, co, io_
+
+
+def low_level_batch(cases, dev, skip=(), spoil=None, stream=None):
+    """one dspn_jpeg_encode_blocks_batch_u8 call over `cases` with GUARD bytes of 0xA5 around every sample's pixels and
+    coefficients and around the workspace -> (coefficient pool as int16 with guards, samples, workspace bytes with guards)"""
+    import torch
+    from dspnet_amd import _lib
+    samples, pix, co, io_ = describe_batch(cases, skip)
+    if spoil:
+        spoil(samples)
+    pool = np.full(io_, 0xA5, np.uint8)
+    for at, img in pix:
+        pool[at:at + img.size] = img.reshape(-1)
+    pdev = torch.from_numpy(pool).to(dev)
+    cdev = torch.full((co,), -23131, dtype=torch.int16, device=dev)                 # 0xA5A5
+    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1).copy()).to(dev)
+    ws_bytes = _lib.lib().dspn_jpeg_encode_workspace_bytes(co)
+    assert ws_bytes >= co
+    ws = torch.full((ws_bytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+    cmap = (je._c.c_int * 3)(0, 1, 2)
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream.cuda_stream
+    torch.cuda.synchronize(dev)                                 # the fills above ran on the current stream
+    _lib.check(_lib.lib().dspn_jpeg_encode_blocks_batch_u8(pdev.data_ptr(), pdev.numel(), cmap, desc.data_ptr(), len(cases),
+                                                           cdev.data_ptr(), co, ws.data_ptr() + GUARD, ws_bytes, st))
+    torch.cuda.synchronize(dev)
+    return cdev.cpu().numpy(), samples, ws.cpu().numpy()
+
+
+def regions(samples, k):
+    s = samples[k]
+    return [(int(s["coef_offset"][c]), 64 * int(s["blocks_w"][c]) * int(s["blocks_h"][c])) for c in range(int(s["ncomp"]))]
+
+
+def check_batch(cases, coefs, samples, ws, untouched=()):
+    covered = np.zeros(coefs.size, bool)
+    for k, case in enumerate(cases):
+        for c, (at, n) in enumerate(regions(samples, k)):
+            covered[at:at + n] = True
+            if k in untouched:
+                assert (coefs[at:at + n] == -23131).all(), "sample %d (%s) was written" % (k, name(case))
+                assert (ws[GUARD + at:GUARD + at + n] == 0xA5).all(), "the planes of sample %d (%s) were written" % (k, name(case))
+            else:
+                np.testing.assert_array_equal(coefs[at:at + n], reference_blocks(case)[c].reshape(-1),
+                                              err_msg="%s component %d" % (name(case), c))
+    assert (coefs[~covered] == -23131).all(), "guard words of the coefficient pool overwritten"
+    assert (~covered).sum() == (GUARD // 2) * (len(cases) + 1)
+    assert (ws[:GUARD] == 0xA5).all() and (ws[-GUARD:] == 0xA5).all(), "guard bytes of the workspace overwritten"

@@ -225,7 +225,9 @@ def pixels(P, planes):
     chroma = []
     for c in (1, 2):
         p = comp[c][:ch, :cw]
-        if (hs, vs) == (2, 1):
+        if hs == 2 and cw <= 2:                                 # jdsample.c: fancy upsampling only for downsampled_width > 2
+            p = np.repeat(np.repeat(p, 2, 1), vs, 0)
+        elif (hs, vs) == (2, 1):
             p = _upsample_h2v1(p)
         elif (hs, vs) == (2, 2):
             p = _upsample_h2v2(p)

@@ -1,7 +1,6 @@
 """Device half of the JPEG encode (dspn_jpeg_encode_blocks_batch_u8) and its callers: the quantised coefficients equal those
 of Pillow's stream for the same pixels (read with tests/ref_jpeg.py), the files equal Pillow's byte for byte, nothing is
 written outside a valid sample's blocks, and record files written through the device equal those written with pack_img."""
-import functools
 import io
 import os
 
@@ -9,79 +8,14 @@ import numpy as np
 import pytest
 
 import jpeg_encode_cases as ec
-import ref_jpeg
 from dspnet_amd import _lib
 from dspnet_amd.dataset import iterator as it
 from dspnet_amd.dataset import jpeg_encode as je
 from dspnet_amd.dataset import recordio
 
-GUARD = 256                                                    # guard bytes (a whole number of int16 blocks and of dwords)
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_blocks(case):
-    """ref_jpeg's reading of Pillow's stream, cut to the real grids: per component (blocks_h, blocks_w, 64); read-only"""
-    data = ec.pillow_file(case)
-    P = ref_jpeg.parse(data)
-    planes = ref_jpeg.coefficients(data, P)
-    s, _ = ec.sample_of(case)
-    return [planes[c][:int(s["blocks_h"][c]), :int(s["blocks_w"][c])].copy() for c in range(P["ncomp"])]
-
-
-def _low_level_batch(cases, dev, skip=(), spoil=None, stream=None):
-    """one dspn_jpeg_encode_blocks_batch_u8 call over `cases` with GUARD bytes of 0xA5 around every sample's pixels and
-    coefficients and around the workspace -> (coefficient pool as int16 with guards, samples, workspace bytes with guards)"""
-    import torch
-    samples = np.zeros(len(cases), je.SAMPLE)
-    pix, co, io_ = [], GUARD // 2, 0
-    for k, case in enumerate(cases):
-        img = ec.pixels(case)
-        io_ += GUARD
-        pix.append((io_, img))
-        n = je.fill_sample(samples[k], case[1], case[0], 1 if case[2] == "grey" else 3, je.SUBSAMPLING.get(case[2], (1, 1)),
-                           je.quant_tables(case[3]), co, io_)
-        samples[k]["skip"] = int(k in skip)
-        co += n + GUARD // 2
-        io_ += img.size + GUARD
-    if spoil:
-        spoil(samples)
-    pool = np.full(io_, 0xA5, np.uint8)
-    for at, img in pix:
-        pool[at:at + img.size] = img.reshape(-1)
-    pdev = torch.from_numpy(pool).to(dev)
-    cdev = torch.full((co,), -23131, dtype=torch.int16, device=dev)                 # 0xA5A5
-    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1).copy()).to(dev)
-    ws_bytes = _lib.lib().dspn_jpeg_encode_workspace_bytes(co)
-    assert ws_bytes >= co
-    ws = torch.full((ws_bytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=dev)
-    cmap = (je._c.c_int * 3)(0, 1, 2)
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream.cuda_stream
-    torch.cuda.synchronize(dev)                                 # the fills above ran on the current stream
-    _lib.check(_lib.lib().dspn_jpeg_encode_blocks_batch_u8(pdev.data_ptr(), pdev.numel(), cmap, desc.data_ptr(), len(cases),
-                                                           cdev.data_ptr(), co, ws.data_ptr() + GUARD, ws_bytes, st))
-    torch.cuda.synchronize(dev)
-    return cdev.cpu().numpy(), samples, ws.cpu().numpy()
-
-
-def _regions(samples, k):
-    s = samples[k]
-    return [(int(s["coef_offset"][c]), 64 * int(s["blocks_w"][c]) * int(s["blocks_h"][c])) for c in range(int(s["ncomp"]))]
-
-
-def _check_batch(cases, coefs, samples, ws, untouched=()):
-    covered = np.zeros(coefs.size, bool)
-    for k, case in enumerate(cases):
-        for c, (at, n) in enumerate(_regions(samples, k)):
-            covered[at:at + n] = True
-            if k in untouched:
-                assert (coefs[at:at + n] == -23131).all(), "sample %d (%s) was written" % (k, ec.name(case))
-                assert (ws[GUARD + at:GUARD + at + n] == 0xA5).all(), "the planes of sample %d (%s) were written" % (k, ec.name(case))
-            else:
-                np.testing.assert_array_equal(coefs[at:at + n], _reference_blocks(case)[c].reshape(-1),
-                                              err_msg="%s component %d" % (ec.name(case), c))
-    assert (coefs[~covered] == -23131).all(), "guard words of the coefficient pool overwritten"
-    assert (~covered).sum() == (GUARD // 2) * (len(cases) + 1)
-    assert (ws[:GUARD] == 0xA5).all() and (ws[-GUARD:] == 0xA5).all(), "guard bytes of the workspace overwritten"
+# the low-level harness lives next to the cases (tests/test_pipeline_edges_gpu.py shares it)
+GUARD, _reference_blocks, _low_level_batch, _regions, _check_batch = (ec.GUARD, ec.reference_blocks, ec.low_level_batch, ec.regions,
+                                                                      ec.check_batch)
 
 
 @pytest.mark.gpu

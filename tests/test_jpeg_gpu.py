@@ -51,32 +51,7 @@ def test_decode_batch_names_the_reason(gpu_device):
 
 def _low_level_batch(names, skip, dev, guard=64, spoil=None):
     """one dspn_jpeg_reconstruct_batch_u8 call with `guard` bytes of 0xA5 around every sample's output -> (pool, regions)"""
-    import torch
-    infos, coefs = [], []
-    for n in names:
-        rc, info = dj.probe_info(jc.stream(n))
-        assert rc == 0 and info["supported"]
-        c = np.zeros(int(info["coef_count"]), np.int16)
-        assert dj.entropy_decode(jc.stream(n), info, c) == 0
-        infos.append(info); coefs.append(c)
-    samples = np.zeros(len(names), dj.SAMPLE)
-    co, io_, regions = 0, 0, []
-    for k, info in enumerate(infos):
-        io_ += guard
-        dj.fill_sample(samples[k], info, co, io_)
-        samples[k]["skip"] = int(k in skip)
-        n = int(info["width"]) * int(info["height"]) * 3
-        regions.append((io_, n))
-        co += coefs[k].size
-        io_ += n + guard
-    if spoil:
-        spoil(samples)
-    pool = torch.full((io_,), 0xA5, dtype=torch.uint8, device=dev)
-    cdev = torch.from_numpy(np.concatenate(coefs)).to(dev)
-    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1).copy()).to(dev)
-    dj.reconstruct(cdev, desc, pool)
-    torch.cuda.synchronize(dev)
-    return pool.cpu().numpy(), regions
+    return jc.low_level_batch([jc.stream(n) for n in names], skip, dev, guard, spoil)
 
 
 @pytest.mark.gpu

@@ -218,46 +218,28 @@ def test_augment_kernel_random_affines(gpu_device):
     """the C entry directly: random source sizes, affines that leave the image on every side, both flips"""
     import ctypes as c
     import torch
-    from dspnet_amd import _lib
+    import augment_cases as ac
     g = np.random.Generator(np.random.PCG64(9))
     B, H, W = 6, 48, 80
     imgs = [_smooth_image(g, int(g.integers(20, 70)), int(g.integers(20, 90))) for _ in range(B)]
     segs = [g.integers(0, 256, im.shape[:2]).astype(np.uint8) for im in imgs]
-    samples = np.zeros(B, it._SAMPLE)
-    Ms, io, so = [], 0, 0
-    for b, im in enumerate(imgs):
+    Ms = []
+    for b in range(B):
         th = g.uniform(-.5, .5)
         sx, sy = g.uniform(.4, 2.5), g.uniform(.4, 2.5)
-        M = [sx * np.cos(th), -sy * np.sin(th), g.uniform(-30, 30), sx * np.sin(th), sy * np.cos(th), g.uniform(-20, 20)]
-        Ms.append(M)
-        samples[b] = (io, so if b != 2 else -1, im.shape[0], im.shape[1], b % 2, 128 if b % 3 else 7, 255 if b % 3 else 3, 0,
-                      it.invert_affine(M))
-        io += im.size
-        so += segs[b].size
-    dev = gpu_device
-    ipool = torch.from_numpy(np.concatenate([i.reshape(-1) for i in imgs])).to(dev)
-    spool = torch.from_numpy(np.concatenate([s.reshape(-1) for s in segs])).to(dev)
-    desc = torch.from_numpy(samples.view(np.uint8).reshape(-1).copy()).to(dev)
+        Ms.append([sx * np.cos(th), -sy * np.sin(th), g.uniform(-30, 30), sx * np.sin(th), sy * np.cos(th), g.uniform(-20, 20)])
+    flips = [b % 2 for b in range(B)]
+    borders = [(128 if b % 3 else 7, 255 if b % 3 else 3) for b in range(B)]
     lut = np.arange(256, dtype=np.uint8)[::-1].copy()
-    data = torch.empty(B, 3, H, W, device=dev)
-    seg_out = torch.empty(B, H // 4, W // 4, device=dev)
     mean = [123.68, 116.779, 103.939]
-    _lib.check(it._entry()(ipool.data_ptr(), spool.data_ptr(), desc.data_ptr(), B, H, W, it._CMAP_BGR, (c.c_double * 3)(*mean),
-                           torch.from_numpy(lut).to(dev).data_ptr(), data.data_ptr(), seg_out.data_ptr(),
-                           torch.cuda.current_stream(dev).cuda_stream), "augment")
-    got, got_seg = data.cpu().numpy(), seg_out.cpu().numpy()
+    got, got_seg, _ = ac.run_batch(gpu_device, imgs, segs, Ms, H, W, flips, borders, no_seg={2}, lut=lut, mean=mean)
     for b in range(B):
-        s = samples[b]
-        w = oa.warp_affine(imgs[b], np.array(Ms[b]).reshape(2, 3), (W, H), True, int(s["img_border"]))
-        ws = oa.warp_affine(segs[b], np.array(Ms[b]).reshape(2, 3), (W, H), False, int(s["seg_border"]))
-        if s["flip"]:
-            w, ws = w[:, ::-1], ws[:, ::-1]
-        d, q = oa.finish_sample(w, ws, (3, H, W), mean, lut.astype(np.float64))
+        d, q = ac.oracle_sample(imgs[b], segs[b], Ms[b], H, W, flips[b], borders[b], has_seg=b != 2, lut=lut, mean=mean)
         np.testing.assert_array_equal(got[b], d)
-        np.testing.assert_array_equal(got_seg[b], q if b != 2 else np.zeros_like(q))
+        np.testing.assert_array_equal(got_seg[b], q)
     # argument checks
-    assert it._entry()(ipool.data_ptr(), spool.data_ptr(), desc.data_ptr(), B, 50, W, it._CMAP_BGR, (c.c_double * 3)(*mean),
-                       0, data.data_ptr(), seg_out.data_ptr(), 0) != 0
+    p = torch.zeros(64, dtype=torch.uint8, device=gpu_device).data_ptr()
+    assert it._entry()(p, p, p, B, 50, W, it._CMAP_BGR, (c.c_double * 3)(*mean), 0, p, p, 0) != 0
 
 
 @pytest.mark.gpu
