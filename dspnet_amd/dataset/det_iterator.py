@@ -19,8 +19,14 @@ padded from the middle of the epoch (:229); when not training the interpolation 
 the end stay zero images (:226-227).
 
 The resize follows OpenCV's as this project understands it; PARITY STATUS: unpinned (include/dspn_det_augment.h lists the
-two known differences).  Out of scope: DetRecordIter (:10-111), a wrapper of MXNet's C++ ImageDetRecordIter whose text is
-not in the reference, and the colour-jitter settings of config/config.py that only that iterator reads."""
+two known differences).
+
+The colour-jitter settings of config/config.py (`ColorJitter`: hue, saturation, illumination, contrast), which in the
+reference only MXNet's C++ detection augmenter reads, are available here as DetIter(color_jitter=..., jitter_seed=...):
+one more launch on the decoded pixels in front of the crop (dataset/colour_jitter.py, include/dspn_colour_jitter.h), with
+parameters from a RandomState of their own, so the global stream above is the same with the feature on or off.
+
+Out of scope: DetRecordIter (:10-111), a wrapper of MXNet's C++ ImageDetRecordIter whose text is not in the reference."""
 import ctypes as _c
 import functools
 import math
@@ -32,6 +38,7 @@ import torch
 
 from .. import _lib
 from ..detect.render import nearest_tables
+from . import colour_jitter
 from . import iterator as _iterator  # noqa: F401  (registers dspn_det_augment_batch_u8 beside dspn_augment_batch_u8)
 from . import jpeg
 from .im2rec import read_list
@@ -339,11 +346,14 @@ class DetIter(object):
     image_path_from_index(i) and label_from_index(i) -> (rows, 5+) array with -1 rows below the valid ones.
     device_jpeg=True: baseline JPEGs are Huffman-decoded on the host and reconstructed on the device in front of the
     augmentation (same pixels as Pillow's, byte for byte); any other file takes the Pillow path, counted in
-    `jpeg_fallbacks`."""
+    `jpeg_fallbacks`.
+    color_jitter: a colour_jitter.ColorJitter (or a dict with its keys); when training and some probability in it is not
+    zero, every batch draws per-sample parameters from np.random.RandomState(jitter_seed) and one launch jitters the
+    decoded pixels in front of the crop.  None, or all probabilities zero: no draw, no launch."""
 
     def __init__(self, imdb, batch_size, data_shape, mean_pixels=[128, 128, 128], rand_samplers=[], rand_mirror=False,
                  shuffle=False, rand_seed=None, is_train=True, max_crop_trial=50, device=None, decode_threads=8,
-                 device_jpeg=False):
+                 device_jpeg=False, color_jitter=None, jitter_seed=0):
         self._imdb = imdb
         self.batch_size = batch_size
         if isinstance(data_shape, int):
@@ -373,6 +383,8 @@ class DetIter(object):
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(decode_threads)))
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
         self._pools = HostPools(self.device.type == "cuda")
+        self._jitter = colour_jitter.config(color_jitter) if is_train else None
+        self._jitter_rs = np.random.RandomState(jitter_seed) if self._jitter is not None else None
 
         self._current = 0
         self._size = imdb.num_images
@@ -478,6 +490,7 @@ class DetIter(object):
             labels.append(label)
             indices.append(int(index))
         samples, tables = pack_batch(plans, H, W)
+        jitter = colour_jitter.draw(self._jitter, len(plans), self._jitter_rs) if self._jitter is not None else None
         jbatch = jpeg.CodedBatch([im.info if isinstance(im, jpeg.Coded) else None for im in opened],
                                  [p["img_offset"] for p in plans])
         pixels = self._pools.take("pixels", offset, torch.uint8)
@@ -487,7 +500,7 @@ class DetIter(object):
                 for p in plans]
         jbatch.answered(list(self._pool.map(jpeg.decode_image, opened, dsts, jbatch.slices(coefs.numpy()))))
         return {"count": len(plans), "pixels": pixels, "pixel_bytes": offset, "samples": samples, "tables": tables,
-                "labels": labels, "indices": indices, "coefs": coefs, "jpeg": jbatch}
+                "labels": labels, "indices": indices, "coefs": coefs, "jpeg": jbatch, "jitter": jitter}
 
     def _device_batch(self, prep):
         """device phase: one upload of pixels (or coefficients), one of descriptors and tables, one launch
@@ -507,6 +520,9 @@ class DetIter(object):
         keep = jbatch.launch(img_dev)
         if self.device_jpeg:
             self.jpeg_fallbacks += jbatch.fallbacks
+        if prep["jitter"] is not None:                         # on the decoded pixels, in front of the crop
+            s = prep["samples"]
+            keep += colour_jitter.apply(img_dev, prep["jitter"], s["img_offset"], np.stack([s["src_h"], s["src_w"]], axis=1))
         augment_on_device(img_dev, desc_dev[:ndesc], desc_dev[ndesc:].view(torch.int32), H, W, self._mean_pixels,
                           out=data[:n])
         self._keepalive = (img_dev, desc_dev) + keep           # until the next batch replaces them

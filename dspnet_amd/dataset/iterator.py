@@ -13,6 +13,8 @@ Division of labour (MI355X-first):
          include/dspn_augment.h) that does warpAffine (bilinear, OpenCV's fixed point) + flip + BGR->RGB planes + mean
          subtraction for the images and nearest warp + flip + /4 resize + LUT for the label maps.  The reference runs
          four OpenCV passes per sample on the host and uploads float32 planes.
+         With color_jitter=... one more launch shifts hue / lightness / saturation and scales the contrast of the decoded
+         pixels in front of the warp (dataset/colour_jitter.py, include/dspn_colour_jitter.h; off by default).
 
 The shuffle and the augmentation parameters come from the same MT19937 stream as the reference
 (`np.random.seed(233)`, then shuffle / rand in the reference's call order, :381-383, :406-419), so for a given
@@ -30,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import colour_jitter
 from . import jpeg
 from . import png
 from . import recordio
@@ -143,12 +146,16 @@ class MultiTaskRecordIter(object):
     the augmentation (same pixels as Pillow's, byte for byte); any other record takes the Pillow path, counted in
     `jpeg_fallbacks` (records of delivered batches since construction).
     device_png=True: 8-bit greyscale / palette label maps are inflated on the host and unfiltered on the device in front of
-    the augmentation (same bytes as Pillow's); any other label map takes the Pillow path, counted in `png_fallbacks`."""
+    the augmentation (same bytes as Pillow's); any other label map takes the Pillow path, counted in `png_fallbacks`.
+    color_jitter: a colour_jitter.ColorJitter (or a dict with its keys); with enable_aug and some probability in it not
+    zero, every epoch draws a table of per-slot parameters from a private RandomState(jitter_seed) beside `aug_params`,
+    and one launch jitters the decoded pixels in front of the warp.  The flat jitter keys that `**cfg.train` brings stay
+    among the ignored **kwargs: only this argument switches the feature on."""
 
     def __init__(self, path_imgrec, batch_size, data_shape, path_imglist="", label_width=-1, label_pad_width=-1,
                  label_pad_value=-1, resize_mode="force", mean_pixels=(123.68, 116.779, 103.939), enable_aug=True,
                  device=None, decode_threads=8, prefetch=True, cache_decoded=False, device_jpeg=False, device_png=False,
-                 **kwargs):
+                 color_jitter=None, jitter_seed=0, **kwargs):
         if device_jpeg and cache_decoded:
             raise ValueError("device_jpeg=True with cache_decoded=True: the cache exists to avoid the host decode that "
                              "device_jpeg removes; choose one")
@@ -172,6 +179,8 @@ class MultiTaskRecordIter(object):
             self.num_samples = sum(1 for _ in f)
         self.index_table = np.arange(self.num_samples)
         self._rs = np.random.RandomState(233)                  # np.random.seed(233) (:381)
+        self._jitter = colour_jitter.config(color_jitter) if enable_aug else None
+        self._jitter_rs = np.random.RandomState(jitter_seed) if self._jitter is not None else None
         self._rs.shuffle(self.index_table)
         self._reset_aug_params()
         self.curr_index = 0
@@ -220,6 +229,8 @@ class MultiTaskRecordIter(object):
         p[:, 4] = -r.rand(n) * self.data_shape[2] * (p[:, 2] - 1.)
         p[:, 5] = -r.rand(n) * self.data_shape[1] * (p[:, 3] - 1.)
         self.aug_params = p
+        # a stream of its own: _rs, and with it the order and the geometry, is the same with the feature on or off
+        self.jitter_params = colour_jitter.draw(self._jitter, n, self._jitter_rs) if self._jitter is not None else None
 
     def iter_next(self):
         return (self.curr_index + self.batch_size) <= self.num_samples
@@ -326,7 +337,8 @@ class MultiTaskRecordIter(object):
         pbatch.answered([a for _, a in answers])
         return {"pools": pools, "pixels": pixels[:max(img_offsets[-1], 1)], "labels": labels[:max(seg_offsets[-1], 1)],
                 "coefs": coefs, "raw": raw, "jpeg": jbatch, "png": pbatch, "samples": samples, "label": label,
-                "fnames": fnames, "start": start}
+                "fnames": fnames, "start": start,
+                "jitter": None if self.jitter_params is None else self.jitter_params[start:start + B]}
 
     def _finish(self, prep):
         B, (C, H, W) = self.batch_size, self.data_shape
@@ -342,6 +354,10 @@ class MultiTaskRecordIter(object):
             self.jpeg_fallbacks += jbatch.fallbacks
         if self.device_png:
             self.png_fallbacks += pbatch.fallbacks
+        if prep["jitter"] is not None:                         # on the decoded pixels, in front of the warp
+            s = prep["samples"]
+            coded_keep += colour_jitter.apply(img_dev, prep["jitter"], s["img_offset"],
+                                              np.stack([s["src_h"], s["src_w"]], axis=1))
         data = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
         seg_out = torch.empty(B, H // 4, W // 4, dtype=torch.float32, device=dev)
         _lib.check(_entry()(img_dev.data_ptr(), seg_dev.data_ptr(), desc_dev.data_ptr(), B, H, W, _CMAP_RGB,
