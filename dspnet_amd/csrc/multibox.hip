@@ -15,6 +15,7 @@
 //     algorithm (see expf_cr).
 #include "dspn_common.h"
 #include "../../include/dspn_multibox.h"
+#include <cmath>
 #include <cstdint>
 #include <algorithm>
 
@@ -68,8 +69,9 @@ __device__ __forceinline__ float expf_cr(float x) {
   return (float)y;
 }
 // glibc's logf is 0.818 ulp (table-driven, not reproducible without its table);
-// it only feeds loc_target VALUES, never an index, so a correctly rounded log is
-// used and the tests allow 1 ulp on those two columns.
+// it only feeds loc_target VALUES, never an index, so the rounded double logarithm is
+// used; the tests hold those two columns to exactly that value, which lies within one
+// float of glibc's (tests/mbx_cases.py: log_bracket, assert_log_columns).
 __device__ __forceinline__ float logf_cr(float x) { return (float)log((double)x); }
 __device__ __forceinline__ float fmaxr(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float fminr(float a, float b) { return a < b ? a : b; }
@@ -540,8 +542,9 @@ __device__ __forceinline__ void target_match_body(
     st.flush();
     return;
   }
-  int num_negative = (int)((float)npos * neg_ratio);
-  if (num_negative > A - npos) num_negative = A - npos;
+  // (the clamp to A - npos comes first, in float: the reference converts first, which is undefined from 2^31 on)
+  const float want = (float)npos * neg_ratio;
+  int num_negative = !(want < (float)(A - npos)) ? A - npos : (int)want;
   if (num_negative <= 0) { st.flush(); return; }
 
   // candidates: not positive and best IoU below the mining threshold
@@ -1254,6 +1257,7 @@ int dspn_multibox_target_f32(const float *anchors_dev, const float *labels_dev,
   DSPN_REQUIRE(variances, "MultiBoxTarget: variances must have 4 values");
   if (negative_mining_ratio > 0)
     DSPN_REQUIRE(negative_mining_thresh > 0, "negative_mining_thresh must be > 0");
+  DSPN_REQUIRE(std::isfinite(negative_mining_ratio), "MultiBoxTarget: negative_mining_ratio must be finite");
   DSPN_REQUIRE(anchors_dev && labels_dev && cls_preds_dev && loc_target_dev && loc_mask_dev &&
                    cls_target_dev && workspace_dev, "MultiBoxTarget: null pointer");
   const TargetLayout l = target_layout(batch, num_anchors, num_labels);

@@ -100,7 +100,10 @@ size_t dspn_multibox_target_workspace_bytes(int batch, int num_anchors, int num_
  * Data-dependent reference aborts (multibox_target.cc:98-101, :236) cannot
  * abort a stream: they set a per-sample code in the first `batch` ints of the
  * workspace (0 ok, 2 = padded label row not all -1, 3 = fewer mining candidates
- * than requested negatives); see dspn_multibox_target_errors(). */
+ * than requested negatives); see dspn_multibox_target_errors().
+ * negative_mining_ratio must be finite.  The number of negatives is
+ * positives * ratio clamped to num_anchors - positives BEFORE the conversion to
+ * int (multibox_target.cc:190-191 converts first: undefined from 2^31 on). */
 int dspn_multibox_target_f32(const float *anchors_dev, const float *labels_dev,
                              const float *cls_preds_dev,
                              int batch, int num_anchors, int num_labels,

@@ -68,7 +68,8 @@ def multibox_prior(in_height, in_width, sizes, ratios, clip=False, steps=(-1.0, 
 def multibox_target(anchor, label, cls_pred, overlap_threshold=0.5, ignore_label=-1.0,
                     negative_mining_ratio=-1.0, negative_mining_thresh=0.5,
                     minimum_negative_samples=0, variances=(0.1, 0.1, 0.2, 0.2),
-                    return_code=False):
+                    return_code=False, return_matched=False):
+    """return_matched: ([loc_target, loc_mask, cls_target], return code, (B, A) int32 ground truth of each positive anchor)"""
     anchor, label, cls_pred = _f32(anchor), _f32(label), _f32(cls_pred)
     B, L, lw = label.shape
     A = anchor.shape[-2]
@@ -77,16 +78,41 @@ def multibox_target(anchor, label, cls_pred, overlap_threshold=0.5, ignore_label
     loc_t = np.empty((B, A * 5), np.float32)
     loc_m = np.empty((B, A * 5), np.float32)
     cls_t = np.empty((B, A), np.float32)
-    rc = lib().dspn_oracle_multibox_target(
-        _p(anchor), _p(label), _p(cls_pred), B, A, L, lw, C,
-        ctypes.c_float(overlap_threshold), ctypes.c_float(ignore_label),
-        ctypes.c_float(negative_mining_ratio), ctypes.c_float(negative_mining_thresh),
-        int(minimum_negative_samples), _p(var), _p(loc_t), _p(loc_m), _p(cls_t))
+    args = (_p(anchor), _p(label), _p(cls_pred), B, A, L, lw, C,
+            ctypes.c_float(overlap_threshold), ctypes.c_float(ignore_label),
+            ctypes.c_float(negative_mining_ratio), ctypes.c_float(negative_mining_thresh),
+            int(minimum_negative_samples), _p(var), _p(loc_t), _p(loc_m), _p(cls_t))
+    if return_matched:
+        matched = np.empty((B, A), np.int32)
+        rc = lib().dspn_oracle_multibox_target_matched(*args, matched.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return [loc_t, loc_m, cls_t], rc, matched
+    rc = lib().dspn_oracle_multibox_target(*args)
     if return_code:
         return [loc_t, loc_m, cls_t], rc
     if rc != 0:
         raise ValueError(f"oracle multibox_target rc={rc}")
     return [loc_t, loc_m, cls_t]
+
+
+def bg_prob(cls_pred):
+    """(B, A) background probabilities of (B, C+1, A) logits, exactly as multibox_target's mining loop ranks them"""
+    cls_pred = _f32(cls_pred)
+    B, C, A = cls_pred.shape
+    out = np.empty((B, A), np.float32)
+    rc = lib().dspn_oracle_bg_prob(_p(cls_pred), B, A, C, _p(out))
+    if rc != 0:
+        raise ValueError(f"oracle bg_prob rc={rc}")
+    return out
+
+
+def logf(x):
+    """libm's logf, the call of encode_loc, element by element"""
+    x = _f32(x)
+    out = np.empty_like(x)
+    fn = lib().dspn_oracle_logf
+    fn.restype = None
+    fn(_p(x), ctypes.c_long(x.size), _p(out))
+    return out
 
 
 def multibox_detection(cls_prob, loc_pred, anchor, clip=True, threshold=0.01, background_id=0,

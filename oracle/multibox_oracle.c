@@ -115,6 +115,29 @@ static void encode_loc(const float *anchor, const float *gt, float *dst,
   dst[4] = (float)((double)gz / 0.1);
 }
 
+/* operator/multibox_target.cc:218-232: softmax probability of the background class of anchor j: float, sequential sum.
+ * pred = one sample's (Cp1, A) logits. */
+static float background_prob(const float *pred, int j, int A, int Cp1) {
+  float max_val = pred[j];
+  for (int k = 1; k < Cp1; ++k) {
+    float t = pred[j + (size_t)A * k];
+    if (t > max_val) max_val = t;
+  }
+  float sum = 0.f;
+  for (int k = 0; k < Cp1; ++k) sum += expf(pred[j + (size_t)A * k] - max_val);
+  return expf(pred[j] - max_val) / sum;
+}
+
+/* The background probabilities exactly as the mining loop ranks them, for every anchor of every sample (the tests build
+ * their radix-select cases from these keys).  cls_preds (B,Cp1,A) -> out (B,A). */
+int dspn_oracle_bg_prob(const float *cls_preds, int B, int A, int Cp1, float *out) {
+  if (B <= 0 || A <= 0 || Cp1 <= 0) return -1;
+  for (int nb = 0; nb < B; ++nb)
+    for (int j = 0; j < A; ++j)
+      out[(size_t)nb * A + j] = background_prob(cls_preds + (size_t)nb * Cp1 * A, j, A, Cp1);
+  return 0;
+}
+
 typedef struct { float value; int index; } sort_elem;
 /* std::stable_sort with operator< == (value > other.value) on elements pushed
  * in ascending index order  ==  total order (value desc, index asc). */
@@ -127,7 +150,7 @@ static int cmp_desc(const void *pa, const void *pb) {
 
 /* operator/multibox_target-inl.h:89-171 (output init + IoU) and
  * operator/multibox_target.cc:73-284 (matching, mining, target write). */
-int dspn_oracle_multibox_target(const float *anchors /* (A,4) */,
+static int multibox_target_impl(const float *anchors /* (A,4) */,
                                 const float *labels  /* (B,L,label_w) */,
                                 const float *cls_preds /* (B,Cp1,A) */,
                                 int B, int A, int L, int label_w, int Cp1,
@@ -138,18 +161,23 @@ int dspn_oracle_multibox_target(const float *anchors /* (A,4) */,
                                 const float variances[4],
                                 float *loc_target /* (B,A*5) */,
                                 float *loc_mask   /* (B,A*5) */,
-                                float *cls_target /* (B,A)   */) {
+                                float *cls_target /* (B,A)   */,
+                                int *matched /* (B,A) or NULL: ground truth of each positive, -1 elsewhere */) {
   (void)minimum_negative_samples;
   if (B <= 0 || A <= 0 || L <= 0 || label_w < 6 || Cp1 <= 0) return -1;
   /* .cc:185 CHECK_GT(negative_mining_thresh, 0), inside `if (negative_mining_ratio > 0)`: the reference aborts there for the
    * first sample that has a valid ground truth.  Rejected as an argument here -- as the HIP entry does (multibox.hip) -- so
    * the checker is never laxer than the product; a batch WITHOUT any ground truth is the one input the reference lets pass. */
   if (negative_mining_ratio > 0 && !(negative_mining_thresh > 0)) return -1;
+  /* no reference CHECK: with an infinite ratio and no positive, 0 * inf = NaN reaches the float-to-int conversion below.
+   * Rejected as an argument, as the HIP entry does. */
+  if (!isfinite(negative_mining_ratio)) return -1;
   int rc = 0;
   /* -inl.h:121-123 */
   memset(loc_target, 0, sizeof(float) * (size_t)B * A * 5);
   memset(loc_mask, 0, sizeof(float) * (size_t)B * A * 5);
   for (long i = 0; i < (long)B * A; ++i) cls_target[i] = ignore_label;
+  if (matched) for (long i = 0; i < (long)B * A; ++i) matched[i] = -1;
 
   float *overlaps = (float *)malloc(sizeof(float) * (size_t)A * L);
   float *match_iou = (float *)malloc(sizeof(float) * A);
@@ -223,8 +251,11 @@ int dspn_oracle_multibox_target(const float *anchors /* (A,4) */,
 
     /* .cc:182-249 negatives */
     if (negative_mining_ratio > 0) {
-      int num_negative = (int)(num_positive * negative_mining_ratio);
-      if (num_negative > A - num_positive) num_negative = A - num_positive;
+      /* .cc:190-191 is `static_cast<int>(num_positive * ratio)`, then the clamp to A - num_positive: undefined once the
+       * product reaches 2^31 (x86 yields INT_MIN: no negatives at all).  Here and in multibox.hip the clamp comes first, in
+       * float, so no out-of-range conversion is ever made: a product at or above A - num_positive asks for all of them. */
+      float want = num_positive * negative_mining_ratio;
+      int num_negative = !(want < (float)(A - num_positive)) ? A - num_positive : (int)want;
       if (num_negative > 0) {
         int nc = 0;
         for (int j = 0; j < A; ++j) {
@@ -239,15 +270,7 @@ int dspn_oracle_multibox_target(const float *anchors /* (A,4) */,
             if (best_gt != -1) { match_iou[j] = max_iou; match_gt[j] = best_gt; }
           }
           if (match_iou[j] < negative_mining_thresh && aflag[j] == -1) {
-            /* .cc:218-232: softmax probability of background, float, sequential sum */
-            float max_val = pred[j];
-            for (int k = 1; k < Cp1; ++k) {
-              float t = pred[j + (size_t)A * k];
-              if (t > max_val) max_val = t;
-            }
-            float sum = 0.f;
-            for (int k = 0; k < Cp1; ++k) sum += expf(pred[j + (size_t)A * k] - max_val);
-            float prob = expf(pred[j] - max_val) / sum;
+            float prob = background_prob(pred, j, A, Cp1);   /* .cc:218-232 */
             cand[nc].value = -prob; cand[nc].index = j; ++nc;
           }
         }
@@ -267,6 +290,7 @@ int dspn_oracle_multibox_target(const float *anchors /* (A,4) */,
       if (aflag[j] == 1) {
         const float *g = lab + label_w * match_gt[j];
         ct[j] = g[0] + 1;
+        if (matched) matched[(size_t)nb * A + j] = match_gt[j];
         for (int q = 0; q < 5; ++q) lm[j * 5 + q] = 1;
         encode_loc(anchors + 4 * j, g + 1, lt + j * 5,
                    variances[0], variances[1], variances[2], variances[3]);
@@ -278,6 +302,34 @@ int dspn_oracle_multibox_target(const float *anchors /* (A,4) */,
   }
   free(overlaps); free(match_iou); free(match_gt); free(aflag); free(gflag); free(cand);
   return rc;
+}
+
+int dspn_oracle_multibox_target(const float *anchors, const float *labels, const float *cls_preds,
+                                int B, int A, int L, int label_w, int Cp1,
+                                float overlap_threshold, float ignore_label, float negative_mining_ratio,
+                                float negative_mining_thresh, int minimum_negative_samples, const float variances[4],
+                                float *loc_target, float *loc_mask, float *cls_target) {
+  return multibox_target_impl(anchors, labels, cls_preds, B, A, L, label_w, Cp1, overlap_threshold, ignore_label,
+                              negative_mining_ratio, negative_mining_thresh, minimum_negative_samples, variances,
+                              loc_target, loc_mask, cls_target, NULL);
+}
+
+/* The same, and which ground truth each positive anchor encodes: what the tests need to restate the two log() columns of
+ * loc_target in double precision. */
+int dspn_oracle_multibox_target_matched(const float *anchors, const float *labels, const float *cls_preds,
+                                        int B, int A, int L, int label_w, int Cp1,
+                                        float overlap_threshold, float ignore_label, float negative_mining_ratio,
+                                        float negative_mining_thresh, int minimum_negative_samples,
+                                        const float variances[4],
+                                        float *loc_target, float *loc_mask, float *cls_target, int *matched) {
+  return multibox_target_impl(anchors, labels, cls_preds, B, A, L, label_w, Cp1, overlap_threshold, ignore_label,
+                              negative_mining_ratio, negative_mining_thresh, minimum_negative_samples, variances,
+                              loc_target, loc_mask, cls_target, matched);
+}
+
+/* libm's logf as encode_loc calls it, element by element (the glibc cross-check of the log columns) */
+void dspn_oracle_logf(const float *x, long n, float *out) {
+  for (long i = 0; i < n; ++i) out[i] = logf(x[i]);
 }
 
 /* ------------------------------------------------------------------ */

@@ -13,6 +13,13 @@ int dspn_oracle_multibox_target(const float *anchors, const float *labels, const
                                 int Cp1, float overlap_threshold, float ignore_label, float negative_mining_ratio,
                                 float negative_mining_thresh, int minimum_negative_samples, const float variances[4],
                                 float *loc_target, float *loc_mask, float *cls_target);
+int dspn_oracle_multibox_target_matched(const float *anchors, const float *labels, const float *cls_preds, int B, int A, int L,
+                                        int label_w, int Cp1, float overlap_threshold, float ignore_label,
+                                        float negative_mining_ratio, float negative_mining_thresh, int minimum_negative_samples,
+                                        const float variances[4], float *loc_target, float *loc_mask, float *cls_target,
+                                        int *matched);
+int dspn_oracle_bg_prob(const float *cls_preds, int B, int A, int Cp1, float *out);
+void dspn_oracle_logf(const float *x, long n, float *out);
 int dspn_oracle_multibox_detection(const float *cls_prob, const float *loc_pred, const float *anchors, int B, int A, int Cp1,
                                    float threshold, int clip, const float variances[4], float nms_threshold, int force_suppress,
                                    int nms_topk, float *out);
@@ -49,6 +56,17 @@ static int run_case(int B, int H, int W, int L, int Cp1, int mode, int topk) {
   /* -2 / -3 are the reference's CHECK failures recorded as codes (the operator still fills its outputs); -1 = bad shapes */
   int rc = dspn_oracle_multibox_target(anchors, labels, cls, B, A, L, 6, Cp1, 0.5f, -1.f, 3.f, 0.5f, 0, var, lt, lm, ct);
   bad |= rc == -1;
+  /* positives x ratio far past 2^31 (the count is clamped in float, never converted out of range), with the matched ground
+   * truths; then the two helper entries the tests use */
+  int *matched = malloc(sizeof(int) * (size_t)B * A);
+  rc = dspn_oracle_multibox_target_matched(anchors, labels, cls, B, A, L, 6, Cp1, 0.5f, -1.f, 1e9f, 0.5f, 0, var, lt, lm, ct, matched);
+  bad |= rc == -1;
+  for (size_t i = 0; i < (size_t)B * A; ++i) bad |= matched[i] < -1 || matched[i] >= L;
+  bad |= dspn_oracle_multibox_target(anchors, labels, cls, B, A, L, 6, Cp1, 0.5f, -1.f, 1.f / 0.f, 0.5f, 0, var, lt, lm, ct) != -1;
+  float *bg = malloc(sizeof(float) * (size_t)B * A);
+  bad |= dspn_oracle_bg_prob(cls, B, A, Cp1, bg) != 0;
+  dspn_oracle_logf(bg, (long)B * A, bg);
+  free(matched); free(bg);
   rc = dspn_oracle_multibox_detection(cls, loc, anchors, B, A, Cp1, 0.01f, 1, var, 0.5f, mode & 1, topk, det);
   bad |= rc == -1;
   double sum = 0;

@@ -135,7 +135,7 @@ def test_forward_backward_matches_cpu_restatement(gpu_device, conv_math):
                    net.target.cls_target.cpu().numpy()]
     # operators inside the graph: bit-exact against the C oracle on the device's own inputs
     np.testing.assert_array_equal(anchors, mc.r50_anchors(256, 256))
-    mc.assert_target_equal(dev_targets, om.multibox_target(anchors, lab, cls_preds_dev, negative_mining_ratio=3))
+    assert mc.assert_target_parity(dev_targets, anchors, lab, cls_preds_dev, negative_mining_ratio=3) == 0
     outs = [o.cpu().numpy() for o in net.outputs()]
     np.testing.assert_array_equal(outs[3], om.multibox_detection(outs[0], net.loc_preds.data.cpu().numpy(), anchors,
                                                                  nms_threshold=.5, nms_topk=400))
@@ -1096,8 +1096,7 @@ def test_other_backbone_graphs_match_cpu_restatement(gpu_device, conv_math, netw
     anchors = net.anchors.cpu().numpy()
     dev_targets = [net.target.loc_target.cpu().numpy(), net.target.loc_mask.cpu().numpy(),
                    net.target.cls_target.cpu().numpy()]
-    mc.assert_target_equal(dev_targets, om.multibox_target(anchors, lab, net.target.cls_preds.data.cpu().numpy(),
-                                                           negative_mining_ratio=3))
+    assert mc.assert_target_parity(dev_targets, anchors, lab, net.target.cls_preds.data.cpu().numpy(), negative_mining_ratio=3) == 0
     ref = ot.forward_loss(ot.export_params(net.g), data, lab, seg, num_classes=classes, dtype=torch.float64,
                           targets=dev_targets, config=cfg, with_seg=(kind != "det"))
     np.testing.assert_array_equal(ref["anchors"], anchors)
@@ -1208,8 +1207,7 @@ def test_inceptionv3_bf16_1024x512_matches_cpu_restatement(gpu_device):
         dev_targets = [net.target.loc_target.cpu().numpy(), net.target.loc_mask.cpu().numpy(),
                        net.target.cls_target.cpu().numpy()]
         # the operators inside the graph stay bit-exact against the C oracle on the device's own (bf16-produced) inputs
-        mc.assert_target_equal(dev_targets, om.multibox_target(anchors, lab, net.target.cls_preds.data.cpu().numpy(),
-                                                               negative_mining_ratio=3))
+        assert mc.assert_target_parity(dev_targets, anchors, lab, net.target.cls_preds.data.cpu().numpy(), negative_mining_ratio=3) == 0
         devq, c32 = bf16_parity_report(net, data, lab, seg, cfg)
         print("bf16 inceptionv3 512x1024 vs bf16-operand oracle: device", devq, "| oracle fp32 vs fp64", c32)
         assert_within_yardstick(devq, c32)

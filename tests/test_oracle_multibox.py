@@ -70,11 +70,11 @@ def test_prior_geometry(h, w):
 def test_target_matches_numpy_reading(seed, ratio, thr):
     anc = mc.small_anchors(6, 7)
     lab, pred = mc.target_inputs(anc, batch=3, num_labels=12, num_classes=4, max_gt=8, seed=seed)
-    got = om.multibox_target(anc, lab, pred, overlap_threshold=thr, negative_mining_ratio=ratio,
-                             negative_mining_thresh=0.5)
+    got, _, matched = om.multibox_target(anc, lab, pred, overlap_threshold=thr, negative_mining_ratio=ratio,
+                                         negative_mining_thresh=0.5, return_matched=True)
     exp = rn.target(anc, lab, pred, overlap_threshold=thr, negative_mining_ratio=ratio,
                     negative_mining_thresh=0.5)
-    mc.assert_target_equal(got, exp)
+    mc.assert_target_equal(got, exp, anc, lab, matched, libm=True)
 
 
 @pytest.mark.parametrize("seed", [1, 2])
