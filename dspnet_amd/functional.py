@@ -1557,3 +1557,49 @@ def sgd_momentum_segments(w, grad, mom, table, lr, momentum, wd, rescale):
     dev, nseg, total4 = table
     check(L().dspn_sgd_momentum_segments_f32(ptr(w), ptr(grad), ptr(mom), ptr(dev), nseg, total4, lr, momentum, wd,
                                              rescale, stream()), "sgd_momentum_segments")
+
+
+# ------------------------------------------------------------------ polygon rasteriser (include/dspn_polygon.h)
+_lib.register({
+    "dspn_polygon_wave_entries": (_i, []),
+    "dspn_polygon_rasterize": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _ll, _vp, _i, _i, _i, _vp, _vp]),
+    "dspn_polygon_resolve": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+})
+
+
+def polygon_wave_entries():
+    """entries of one (polygon, row) job that the in-LDS route of the rasteriser holds; a larger job spills"""
+    return int(L().dspn_polygon_wave_entries())
+
+
+def polygon_rasterize(edges, polys, jobs, scratch_floats, B, H, W, owner=None, spill_count=None):
+    """edges (E, 8), polys (P, 4), jobs (J, 5) int32 device tables of include/dspn_polygon.h -> owner (B, H, W) int32:
+    per pixel the largest order among the polygons that cover it, 0 where none does.  scratch_floats: what the jobs'
+    offsets address (0 when no job spills).  spill_count: optional device int32 (1,), incremented once per job that
+    took the spill route."""
+    dev = jobs.device
+    for t, cols in ((edges, 8), (polys, 4), (jobs, 5)):
+        assert t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == cols and t.is_contiguous(), (t.dtype, tuple(t.shape))
+    if owner is None:
+        owner = torch.zeros(B, H, W, dtype=torch.int32, device=dev)
+    assert owner.dtype == torch.int32 and tuple(owner.shape) == (B, H, W) and owner.is_contiguous()
+    scratch = _scratch(4 * int(scratch_floats), dev, tag="polygon") if scratch_floats else None
+    check(L().dspn_polygon_rasterize(ptr(edges), edges.shape[0], ptr(polys), polys.shape[0], ptr(jobs), jobs.shape[0],
+                                     ptr(scratch), int(scratch_floats), ptr(owner), B, H, W, ptr(spill_count), stream()),
+          "polygon_rasterize")
+    return owner
+
+
+def polygon_resolve(owner, table, table_offset):
+    """owner (B, H, W) int32, table (T, 4) int32 rows [labelId, labelTrainId, instanceId, instanceTrainId], table_offset
+    (B,) int32 (row of each image's background) -> (labelIds, labelTrainIds) uint8 and (instanceIds, instanceTrainIds)
+    int32, all (B, H, W)"""
+    B, H, W = owner.shape
+    assert table.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == 4 and table.is_contiguous()
+    assert table_offset.dtype == torch.int32 and table_offset.numel() == B
+    dev = owner.device
+    lab, lab_t = (torch.zeros(B, H, W, dtype=torch.uint8, device=dev) for _ in range(2))
+    inst, inst_t = (torch.zeros(B, H, W, dtype=torch.int32, device=dev) for _ in range(2))
+    check(L().dspn_polygon_resolve(ptr(owner), B, H, W, ptr(table), table.shape[0], ptr(table_offset), ptr(lab), ptr(lab_t),
+                                   ptr(inst), ptr(inst_t), stream()), "polygon_resolve")
+    return lab, lab_t, inst, inst_t
