@@ -4,7 +4,8 @@ five interpolations drawn per image, mirror -- and ListImdb, the database of an 
 
 Division of labour, as in MultiTaskRecordIter:
   host   file read, decode on a thread pool into one pinned pool (with device_jpeg=True only the entropy pass of a
-         baseline JPEG stays here, dataset/jpeg.py, with Pillow for everything else), the samplers and the box
+         baseline JPEG stays here, dataset/jpeg.py, with device_png=True only the inflate of a PNG, dataset/png.py, with
+         Pillow for everything else), the samplers and the box
          arithmetic, the window (`crop_window`) and the resize tap tables (`resize_taps`): pure functions;
   device ONE upload of the pixels, ONE upload of descriptors and tables, ONE launch (dspn_det_augment_batch_u8,
          include/dspn_det_augment.h) that does crop / pad + resize + mirror + mean + planes for the whole batch.  The
@@ -41,9 +42,10 @@ from ..detect.render import nearest_tables
 from . import colour_jitter
 from . import iterator as _iterator  # noqa: F401  (registers dspn_det_augment_batch_u8 beside dspn_augment_batch_u8)
 from . import jpeg
+from . import png
 from .im2rec import read_list
 from .rand_sampler import RandSampler
-from .staging import HostPools
+from .staging import HostPools, upload_decoded
 
 # the reference's list order (:281-282)
 LINEAR, CUBIC, AREA, NEAREST, LANCZOS4 = range(5)
@@ -314,6 +316,14 @@ class ListImdb(object):
 
 
 # ---- the iterator ---------------------------------------------------------------------------------------------------
+def _decode_image(im, dst, coef_dst, raw_dst):
+    """worker thread: one image's host half -> "jpeg" or "png" when that format's launch finishes the image, False when
+    Pillow's pixels are in dst"""
+    if isinstance(im, png.CodedRgb):
+        return "png" if png.decode_rgb(im, dst, raw_dst) else False
+    return "jpeg" if jpeg.decode_image(im, dst, coef_dst) else False
+
+
 class DataBatch(object):
     def __init__(self, data, label, pad=0, index=None):
         self.data, self.label, self.pad, self.index = data, label, pad, index
@@ -347,13 +357,17 @@ class DetIter(object):
     device_jpeg=True: baseline JPEGs are Huffman-decoded on the host and reconstructed on the device in front of the
     augmentation (same pixels as Pillow's, byte for byte); any other file takes the Pillow path, counted in
     `jpeg_fallbacks`.
+    device_png=True: PNG files of every non-interlaced format but 16-bit greyscale are inflated on the host and turned into
+    RGB on the device in front of the augmentation (same pixels as Pillow's convert("RGB"), byte for byte); a PNG file that
+    is unsupported, malformed or does not inflate takes the Pillow path, counted in `png_fallbacks`.  With both switches on,
+    an image the device decodes in either format is no fallback of the other.
     color_jitter: a colour_jitter.ColorJitter (or a dict with its keys); when training and some probability in it is not
     zero, every batch draws per-sample parameters from np.random.RandomState(jitter_seed) and one launch jitters the
     decoded pixels in front of the crop.  None, or all probabilities zero: no draw, no launch."""
 
     def __init__(self, imdb, batch_size, data_shape, mean_pixels=[128, 128, 128], rand_samplers=[], rand_mirror=False,
                  shuffle=False, rand_seed=None, is_train=True, max_crop_trial=50, device=None, decode_threads=8,
-                 device_jpeg=False, color_jitter=None, jitter_seed=0):
+                 device_jpeg=False, color_jitter=None, jitter_seed=0, device_png=False):
         self._imdb = imdb
         self.batch_size = batch_size
         if isinstance(data_shape, int):
@@ -382,6 +396,7 @@ class DetIter(object):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(decode_threads)))
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
+        self.device_png, self.png_fallbacks = bool(device_png), 0
         self._pools = HostPools(self.device.type == "cuda")
         self._jitter = colour_jitter.config(color_jitter) if is_train else None
         self._jitter_rs = np.random.RandomState(jitter_seed) if self._jitter is not None else None
@@ -394,7 +409,7 @@ class DetIter(object):
         self._label = None
         self.batch_indices = []
         self._get_batch()                                      # :179
-        self.jpeg_fallbacks = 0                                # that batch was not delivered
+        self.jpeg_fallbacks = self.png_fallbacks = 0           # that batch was not delivered
 
     @property
     def provide_data(self):
@@ -468,7 +483,7 @@ class DetIter(object):
     def _prepare(self):
         """host phase: indices, files, draws, decode, descriptors and tables"""
         B, (H, W) = self.batch_size, self._data_shape
-        opened, plans, labels, indices = [], [], [], []
+        opened, plans, labels, indices, is_png = [], [], [], [], []
         offset = 0
         for i in range(B):
             if (self._current + i) >= self._size:
@@ -479,7 +494,11 @@ class DetIter(object):
             else:
                 index = self._index[self._current + i]
             with open(self._imdb.image_path_from_index(index), "rb") as fp:
-                im = jpeg.open_image(fp.read(), self.device_jpeg)    # sizes before any pixel is decoded
+                content = fp.read()
+            is_png.append(content[:8] == png.SIGNATURE)
+            im = png.open_rgb(content) if self.device_png else None
+            if im is None:
+                im = jpeg.open_image(content, self.device_jpeg)      # sizes before any pixel is decoded
             width, height = im.size
             gt = self._imdb.label_from_index(index).copy() if self.is_train else None
             window, method, mirror, label = self._plan(width, height, gt)
@@ -493,33 +512,45 @@ class DetIter(object):
         jitter = colour_jitter.draw(self._jitter, len(plans), self._jitter_rs) if self._jitter is not None else None
         jbatch = jpeg.CodedBatch([im.info if isinstance(im, jpeg.Coded) else None for im in opened],
                                  [p["img_offset"] for p in plans])
+        pbatch = png.RgbBatch([im.info if isinstance(im, png.CodedRgb) else None for im in opened],
+                              [p["img_offset"] for p in plans])
         pixels = self._pools.take("pixels", offset, torch.uint8)
         coefs = self._pools.take("coefs", jbatch.count, torch.int16, floor=jbatch.FLOOR)
+        raw = self._pools.take("raw", pbatch.count, torch.uint8, floor=pbatch.FLOOR)
         pnp = pixels.numpy()
         dsts = [pnp[p["img_offset"]:p["img_offset"] + p["src_w"] * p["src_h"] * 3].reshape(p["src_h"], p["src_w"], 3)
                 for p in plans]
-        jbatch.answered(list(self._pool.map(jpeg.decode_image, opened, dsts, jbatch.slices(coefs.numpy()))))
+        answers = list(self._pool.map(_decode_image, opened, dsts, jbatch.slices(coefs.numpy()), pbatch.slices(raw.numpy())))
+        # per format: True -- its launch finishes the image; None -- the other format's does; False -- the host decoded it
+        jbatch.answered([a == "jpeg" or (None if a else False) for a in answers])
+        pbatch.answered([a == "png" or (None if a else False) for a in answers])
         return {"count": len(plans), "pixels": pixels, "pixel_bytes": offset, "samples": samples, "tables": tables,
-                "labels": labels, "indices": indices, "coefs": coefs, "jpeg": jbatch, "jitter": jitter}
+                "labels": labels, "indices": indices, "coefs": coefs, "jpeg": jbatch, "jitter": jitter, "raw": raw,
+                "png": pbatch, "png_on_host": sum(1 for a, f in zip(answers, is_png) if f and not a)}
 
     def _device_batch(self, prep):
         """device phase: one upload of pixels (or coefficients), one of descriptors and tables, one launch
         -> (B, 3, H, W) float32; slots past the samples of `prep` stay zero"""
         B, (H, W), dev = self.batch_size, self._data_shape, self.device
-        n, jbatch = prep["count"], prep["jpeg"]
+        n, jbatch, pbatch = prep["count"], prep["jpeg"], prep["png"]
         data = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if n == B else \
             torch.zeros(B, 3, H, W, dtype=torch.float32, device=dev)
         if n == 0:
             return data
         # pool copies, then the pools' event, then descriptors and launches: the reason is in dataset/staging.py
-        img_dev = jbatch.upload(prep["coefs"], dev, prep["pixels"][:max(prep["pixel_bytes"], 1)])
+        jbatch.upload(prep["coefs"], dev)
+        pbatch.upload(prep["raw"], dev)
+        img_dev = upload_decoded(prep["pixels"][:max(prep["pixel_bytes"], 1)], dev, jbatch.on_device + pbatch.on_device,
+                                 jbatch.fallbacks)
         self._pools.uploaded(torch.cuda.current_stream(dev))
         desc = np.concatenate([prep["samples"].view(np.uint8).reshape(-1), prep["tables"].view(np.uint8)])
         desc_dev = torch.from_numpy(desc).to(dev)              # descriptors and tables in one upload (56 B each: 4-aligned)
         ndesc = n * SAMPLE.itemsize
-        keep = jbatch.launch(img_dev)
+        keep = jbatch.launch(img_dev) + pbatch.launch(img_dev)
         if self.device_jpeg:
             self.jpeg_fallbacks += jbatch.fallbacks
+        if self.device_png:
+            self.png_fallbacks += prep["png_on_host"]
         if prep["jitter"] is not None:                         # on the decoded pixels, in front of the crop
             s = prep["samples"]
             keep += colour_jitter.apply(img_dev, prep["jitter"], s["img_offset"], np.stack([s["src_h"], s["src_w"]], axis=1))

@@ -1,5 +1,7 @@
 """Record files from an image list: the database half of the reference's `tools/im2rec.py` (reading `<prefix>.lst` and
-writing `<prefix>.rec` / `<prefix>.idx`), with the JPEG encode on the device.
+writing `<prefix>.rec` / `<prefix>.idx`), with the JPEG encode on the device, and the decode of the source files too
+where they are baseline JPEGs (dataset/jpeg.py) or non-interlaced PNGs other than 16-bit greyscale (dataset/png.py: the
+host inflates, the device undoes the row filters and makes the RGB bytes); Pillow decodes the rest.
 
     .lst   one image per line, tab-separated: integer index, one or more float label columns, path relative to `root`
 
@@ -15,8 +17,10 @@ import os
 import numpy as np
 import torch
 
+from .._lib import DspnError
 from . import jpeg as _jpeg
 from . import jpeg_encode, recordio
+from . import png as _png
 
 
 def read_list(path):
@@ -44,30 +48,38 @@ def _header(index, labels, pack_label):
 
 
 def _decode(payloads, device):
-    """encoded files -> (h, w, 3) RGB uint8 device tensors: baseline JPEGs of the supported set through the device decode,
-    everything else through Pillow; both give the pixels Pillow gives"""
+    """encoded files -> (h, w, 3) RGB uint8 device tensors: baseline JPEGs and PNGs of the supported sets through the device
+    decodes, everything else through Pillow; all give the pixels Pillow's convert("RGB") gives"""
     from PIL import Image
-    out, on_device = [None] * len(payloads), []
+    out, jpegs, pngs = [None] * len(payloads), [], []
     for k, data in enumerate(payloads):
-        supported = False
         if data[:2] == b"\xff\xd8":
             rc, info = _jpeg.probe_info(data)
-            supported = rc == 0 and bool(info["supported"])
-        if supported:
-            on_device.append(k)
-        else:
+            if rc == 0 and bool(info["supported"]):
+                jpegs.append(k)
+        elif _png.open_rgb(data) is not None:
+            pngs.append(k)
+    if jpegs:
+        for k, t in zip(jpegs, _jpeg.decode_batch([payloads[k] for k in jpegs], device)):
+            out[k] = t
+    if pngs:
+        try:
+            decoded = _png.decode_rgb_batch([payloads[k] for k in pngs], device)
+        except DspnError:
+            decoded = ()                                        # IDAT data that does not inflate: Pillow decodes or raises, as before
+        for k, t in zip(pngs, decoded):
+            out[k] = t
+    for k, data in enumerate(payloads):
+        if out[k] is None:
             rgb = np.array(Image.open(io.BytesIO(data)).convert("RGB"))
             out[k] = torch.from_numpy(rgb).to(device)
-    if on_device:
-        for k, t in zip(on_device, _jpeg.decode_batch([payloads[k] for k in on_device], device)):
-            out[k] = t
     return out
 
 
 def write_records(prefix, root, quality=95, pack_label=True, pass_through=False, batch=16, device=None):
     """reads `prefix`.lst and writes `prefix`.rec / `prefix`.idx through MXIndexedRecordIO, one record per line, keyed by
     the line's index, in list order.  pass_through: the file's bytes are packed as they are.  Otherwise each image is decoded
-    to three channels (on the device where it is a JPEG the device decode supports, with Pillow otherwise) and re-encoded on
+    to three channels (on the device where it is a JPEG or PNG a device decode supports, with Pillow otherwise) and re-encoded on
     the device, `batch` images per call, as `recordio.pack_img(header, image, quality)` would encode it.  An unreadable
     file is an error (the reference prints and skips it).  No resizing and no cropping (see the module text).  -> the
     number of records written."""

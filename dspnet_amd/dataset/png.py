@@ -7,7 +7,13 @@ greyscale 16-bit, not interlaced, without tRNS and without animation.
 
 `probe` and `decode_batch` are the public use (ground-truth id maps, instance-id maps, disparity maps held as PNG bytes);
 MultiTaskRecordIter(device_png=True) goes through `open_label`, `decode_label` and `CodedBatch` with its own pools
-(dataset/staging.py)."""
+(dataset/staging.py).
+
+Colour images: `probe_rgb` and `decode_rgb_batch` give the bytes of Pillow's `Image.open(...).convert("RGB")` for every
+non-interlaced format but 16-bit greyscale (which convert("RGB") clips; it stays with `decode_batch`): RGB, RGBA and
+grey + alpha at 8 and 16 bits, greyscale and palette at 1, 2, 4 and 8 bits, with or without tRNS (convert("RGB") ignores
+it).  The device reconstructs the rows at the format's stride and then makes the RGB bytes (dspn_png_rgb_batch).
+im2rec's `_decode` uses `decode_rgb_batch`; DetIter(device_png=True) goes through `open_rgb`, `decode_rgb` and `RgbBatch`."""
 import ctypes as _c
 import io
 import struct
@@ -26,6 +32,17 @@ assert SAMPLE.itemsize == 32
 REASONS = ("ok", "bit depth below 8", "colour type is RGB, RGBA or grey + alpha", "Adam7 interlace", "tRNS chunk",
            "acTL chunk (APNG)", "not a bit depth / colour type / method of the PNG specification")
 OK, LOW_DEPTH, COLOUR, INTERLACE, TRNS, APNG, NONSTANDARD = range(7)
+# dspn_png_rgb_sample
+RGB_SAMPLE = np.dtype([("raw_offset", "<i8"), ("recon_offset", "<i8"), ("out_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
+                       ("bit_depth", "<i4"), ("colour_type", "<i4"), ("palette_index", "<i4"), ("skip", "<i4")])
+assert RGB_SAMPLE.itemsize == 48
+PALETTE_BYTES = 768
+# probe_rgb's reasons (REASONS above is probe's alone)
+RGB_REASONS = ("ok", "16-bit greyscale (convert(\"RGB\") clips it; decode_batch keeps the 16 bits)", "Adam7 interlace",
+               "acTL chunk (APNG)", "not a bit depth / colour type / method of the PNG specification",
+               "palette image without a PLTE chunk of 1 to 256 entries before IDAT")
+RGB_OK, RGB_GREY16, RGB_INTERLACE, RGB_APNG, RGB_NONSTANDARD, RGB_NO_PLTE = range(6)
+_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _CRITICAL = (b"IHDR", b"PLTE", b"IDAT", b"IEND")
 _DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}      # colour type -> legal bit depths
@@ -40,6 +57,9 @@ _lib.register({
     "dspn_png_filter_workspace_bytes": (_c.c_size_t, [_c.c_int]),
     "dspn_png_filter_batch": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_longlong,
                                          _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "dspn_png_rgb_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int]),
+    "dspn_png_rgb_batch": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                      _c.c_longlong, _c.c_void_p, _c.c_longlong, _c.c_void_p]),
 })
 
 
@@ -47,17 +67,15 @@ def _malformed(what):
     return _lib.DspnError("png_probe: " + what)
 
 
-def probe(payload):
-    """what the chunk list says, before any pixel work: a dict with width, height, bit_depth, colour_type, interlace,
-    bytes_per_pixel, row_bytes, raw_bytes (= height * (row_bytes + 1), the inflated size), supported, reason (text),
-    reason_code and idat (the (offset, length) of every IDAT chunk's data, for inflate_into).  The CRC of every critical
-    chunk is checked.  Raises DspnError on a malformed stream: bad signature, bad CRC on a critical chunk, a chunk running
-    past the end, no IHDR / IDAT / IEND, zero width or height."""
+def _walk(payload):
+    """the chunk list of a stream -> (the IHDR fields, the (offset, length) of every IDAT chunk's data, the set of tRNS / acTL
+    seen, the (offset, length) of the first PLTE chunk's data if it comes before IDAT, else None).  The CRC of every critical
+    chunk is checked.  Raises DspnError on a malformed stream."""
     data = memoryview(payload)
     n = len(data)
     if n < 8 or bytes(data[:8]) != SIGNATURE:
         raise _malformed("bad signature")
-    at, ihdr, idat, flags, ended = 8, None, [], set(), False
+    at, ihdr, idat, flags, plte, ended = 8, None, [], set(), None, False
     while not ended:
         if n - at < 12:
             raise _malformed("a chunk header runs past the end (no IEND)" if n > at else "no IEND chunk")
@@ -79,14 +97,31 @@ def probe(payload):
             ended = True
         elif kind in (b"tRNS", b"acTL"):
             flags.add(kind)
+        elif kind == b"PLTE" and plte is None and not idat:
+            plte = (body, length)
         at = body + length + 4
     if not idat:
         raise _malformed("no IDAT chunk")
-    width, height, depth, colour, compression, filtering, interlace = ihdr
-    if width == 0 or height == 0:
+    if ihdr[0] == 0 or ihdr[1] == 0:
         raise _malformed("zero width or height")
-    if colour not in _DEPTHS or depth not in _DEPTHS[colour] or compression or filtering or interlace > 1 or \
-            width > 0x7fffffff or height > 0x7fffffff:
+    return ihdr, idat, flags, plte
+
+
+def _standard(ihdr):
+    width, height, depth, colour, compression, filtering, interlace = ihdr
+    return colour in _DEPTHS and depth in _DEPTHS[colour] and not compression and not filtering and interlace <= 1 and \
+        width <= 0x7fffffff and height <= 0x7fffffff
+
+
+def probe(payload):
+    """what the chunk list says, before any pixel work: a dict with width, height, bit_depth, colour_type, interlace,
+    bytes_per_pixel, row_bytes, raw_bytes (= height * (row_bytes + 1), the inflated size), supported, reason (text),
+    reason_code and idat (the (offset, length) of every IDAT chunk's data, for inflate_into).  The CRC of every critical
+    chunk is checked.  Raises DspnError on a malformed stream: bad signature, bad CRC on a critical chunk, a chunk running
+    past the end, no IHDR / IDAT / IEND, zero width or height."""
+    ihdr, idat, flags, _ = _walk(payload)
+    width, height, depth, colour, compression, filtering, interlace = ihdr
+    if not _standard(ihdr):
         code = NONSTANDARD
     elif colour in (2, 4, 6):
         code = COLOUR
@@ -106,9 +141,36 @@ def probe(payload):
             "supported": code == OK, "reason": REASONS[code], "reason_code": code, "idat": idat}
 
 
+def probe_rgb(payload):
+    """`probe` for the RGB path (decode_rgb_batch): the same dict, classified by RGB_REASONS, with bytes_per_pixel the
+    filter stride (1 for the packed depths), row_bytes = ceil(width * channels * bit_depth / 8), and one more entry,
+    `palette`: the PLTE chunk's data of a supported palette image (else None).  Raises DspnError as `probe` does."""
+    ihdr, idat, flags, plte = _walk(payload)
+    width, height, depth, colour, compression, filtering, interlace = ihdr
+    if not _standard(ihdr):
+        code = RGB_NONSTANDARD
+    elif colour == 0 and depth == 16:
+        code = RGB_GREY16
+    elif interlace:
+        code = RGB_INTERLACE
+    elif b"acTL" in flags:
+        code = RGB_APNG
+    elif colour == 3 and (plte is None or plte[1] == 0 or plte[1] % 3 or plte[1] > PALETTE_BYTES):
+        code = RGB_NO_PLTE
+    else:
+        code = RGB_OK
+    ok = code == RGB_OK
+    bits = _CHANNELS[colour] * depth if ok else 0
+    row_bytes = (width * bits + 7) // 8
+    palette = bytes(memoryview(payload)[plte[0]:plte[0] + plte[1]]) if ok and colour == 3 else None
+    return {"width": width, "height": height, "bit_depth": depth, "colour_type": colour, "interlace": interlace,
+            "bytes_per_pixel": max(1, bits // 8) if ok else 0, "row_bytes": row_bytes, "raw_bytes": height * (row_bytes + 1) if ok else 0,
+            "supported": ok, "reason": RGB_REASONS[code], "reason_code": code, "idat": idat, "palette": palette}
+
+
 def inflate_into(payload, info, dst):
-    """inflate the concatenated IDAT data of a probed, supported stream into the uint8 array dst (info["raw_bytes"] bytes);
-    every row keeps its filter-type byte in front.  -> 0, or a non-zero status (never an exception) on a zlib error, an
+    """inflate the concatenated IDAT data of a probed (`probe` or `probe_rgb`), supported stream into the uint8 array dst
+    (info["raw_bytes"] bytes); every row keeps its filter-type byte in front, info["row_bytes"] + 1 bytes from the last one.  -> 0, or a non-zero status (never an exception) on a zlib error, an
     inflated length other than raw_bytes, or a filter type above 4; dst may then hold anything, nothing around it does."""
     want = info["raw_bytes"]
     assert info["supported"] and dst.dtype == np.uint8 and dst.ndim == 1 and dst.size == want
@@ -227,3 +289,115 @@ def decode_batch(payloads, device):
         img = pool[o:o + h * info["row_bytes"]]
         out.append((img.view(torch.uint16) if info["bytes_per_pixel"] == 2 else img).view(h, w))
     return out
+
+
+# ---- colour images to RGB (dspn_png_rgb_batch) ------------------------------------------------------------------------------
+def rgb_workspace_bytes(samples):
+    """dspn_png_rgb_workspace_bytes of an RGB_SAMPLE array on the host (no HIP call)"""
+    samples = np.ascontiguousarray(samples, RGB_SAMPLE)
+    return int(_lib.lib().dspn_png_rgb_workspace_bytes(samples.ctypes.data, samples.size))
+
+
+def to_rgb(raw_dev, samples_dev, palettes_dev, out_dev, ws_dev, stream=None):
+    """dspn_png_rgb_batch: raw_dev the uint8 device pool of inflated rows, samples_dev a uint8 device tensor of descriptors,
+    palettes_dev a uint8 device tensor of 768-byte tables (may be empty), out_dev the uint8 device pool the RGB bytes go
+    to, ws_dev the uint8 device scratch (may be empty)"""
+    dev = raw_dev.device
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().dspn_png_rgb_batch(raw_dev.data_ptr(), raw_dev.numel(), samples_dev.data_ptr(),
+                                             samples_dev.numel() // RGB_SAMPLE.itemsize,
+                                             palettes_dev.data_ptr() if palettes_dev.numel() else None,
+                                             palettes_dev.numel() // PALETTE_BYTES, out_dev.data_ptr(), out_dev.numel(),
+                                             ws_dev.data_ptr() if ws_dev.numel() else None, ws_dev.numel(), st), "png_rgb")
+
+
+class RgbBatch(staging.CodedBatch):
+    """staging.CodedBatch over dspn_png_rgb_sample: inflated rows with their filter bytes in, (h, w, 3) RGB bytes out.  The
+    palettes travel behind the descriptors, in the same upload; the reconstructed rows of everything but RGB 8-bit pass
+    through a device workspace laid out here (every image 16-byte aligned)."""
+    SAMPLE, FLOOR = RGB_SAMPLE, 1
+
+    def __init__(self, infos, out_offsets):
+        self._palettes, self._recon = [], 0
+        super().__init__(infos, out_offsets)
+
+    def _describe(self, s, info, raw_offset, out_offset):
+        s["raw_offset"], s["recon_offset"], s["out_offset"] = raw_offset, self._recon, out_offset
+        s["width"], s["height"], s["bit_depth"], s["colour_type"] = info["width"], info["height"], info["bit_depth"], info["colour_type"]
+        if info["colour_type"] == 3:
+            s["palette_index"] = len(self._palettes)
+            self._palettes.append(info["palette"].ljust(PALETTE_BYTES, b"\0"))
+        if not (info["colour_type"] == 2 and info["bit_depth"] == 8):
+            self._recon += -(-info["height"] * info["row_bytes"] // 16) * 16
+        return info["raw_bytes"]
+
+    def _descriptors(self):
+        return np.concatenate([self.samples.view(np.uint8).reshape(-1), np.frombuffer(b"".join(self._palettes), np.uint8)])
+
+    def _launch(self, raw_dev, desc_dev, out_dev):
+        n = self.samples.size * RGB_SAMPLE.itemsize
+        ws = torch.empty(rgb_workspace_bytes(self.samples), dtype=torch.uint8, device=out_dev.device)
+        to_rgb(raw_dev, desc_dev[:n], desc_dev[n:], out_dev, ws)
+        return (ws,)
+
+
+def decode_rgb_batch(payloads, device):
+    """decode a list of PNG byte strings -> list of (h, w, 3) torch.uint8 RGB tensors on `device`, views of one pool: the
+    bytes of np.array(Image.open(p).convert("RGB")).  ValueError (naming the reason and the stream) for a stream `probe_rgb`
+    does not support, DspnError for a malformed one or one that does not inflate."""
+    infos = []
+    for i, p in enumerate(payloads):
+        try:
+            info = probe_rgb(p)
+        except _lib.DspnError as e:
+            raise _lib.DspnError("%s (stream %d)" % (e, i)) from None
+        if not info["supported"]:
+            raise ValueError("stream %d is not decodable to RGB on the device: %s" % (i, info["reason"]))
+        infos.append(info)
+    if not infos:
+        return []
+    sizes = [i["height"] * i["width"] * 3 for i in infos]
+    batch = RgbBatch(infos, np.cumsum([0] + sizes[:-1]))
+    raw = torch.empty(batch.count, dtype=torch.uint8).pin_memory()
+    for k, (p, info, dst) in enumerate(zip(payloads, infos, batch.slices(raw.numpy()))):
+        status = inflate_into(p, info, dst)
+        if status:
+            raise _lib.DspnError("png_inflate (stream %d): %s" % (k, ("", "zlib error", "inflated length is not height * "
+                                 "(row_bytes + 1)", "filter type above 4")[status]))
+    batch.answered([True] * len(infos))
+    pool = torch.empty(sum(sizes), dtype=torch.uint8, device=device)
+    batch.upload(raw, device)
+    batch.launch(pool)
+    torch.cuda.current_stream(device).synchronize()             # the pinned buffer and the workspace go out of scope here
+    return [img.view(i["height"], i["width"], 3) for img, i in zip(pool.split(sizes), infos)]
+
+
+class CodedRgb(object):
+    """a colour PNG the device will turn into RGB: the probed chunk list, with the `size` a batch layout reads from a PIL
+    image"""
+
+    def __init__(self, payload, info):
+        self.payload, self.info = payload, info
+        self.size = (info["width"], info["height"])
+
+
+def open_rgb(content):
+    """-> a CodedRgb for a PNG stream `probe_rgb` supports; None for anything else (also a malformed PNG: whoever opens it
+    next decodes it or raises as it always did)"""
+    if content[:8] != SIGNATURE:
+        return None
+    try:
+        info = probe_rgb(content)
+    except _lib.DspnError:
+        return None
+    return CodedRgb(content, info) if info["supported"] else None
+
+
+def decode_rgb(im, dst, raw_dst):
+    """worker thread: the filtered rows of a CodedRgb into raw_dst -> True (the device finishes the image); when they do not
+    inflate, Pillow's pixels (or its exception) into the (h, w, 3) array dst -> False"""
+    if inflate_into(im.payload, im.info, raw_dst) == 0:
+        return True
+    from PIL import Image
+    dst[...] = np.asarray(Image.open(io.BytesIO(im.payload)).convert("RGB"))
+    return False

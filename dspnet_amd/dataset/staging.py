@@ -85,16 +85,27 @@ class CodedBatch(object):
             self._coded_dev = coded[:max(self.count, self.FLOOR)].to(device, non_blocking=True)
         if decoded is None:
             return None
-        if not self.on_device:
-            return decoded.to(device, non_blocking=True)
-        out = torch.empty(decoded.numel(), dtype=decoded.dtype, device=device)
-        if self.fallbacks:
-            out.copy_(decoded, non_blocking=True)
-        return out
+        return upload_decoded(decoded, device, self.on_device, self.fallbacks)
+
+    def _descriptors(self):
+        """the bytes of the descriptor upload: the samples, and behind them whatever tables a subclass's launch reads"""
+        return self.samples.view(np.uint8).reshape(-1)
 
     def launch(self, out_dev):
         """step 3 of the module note -> what must stay alive until the stream has run the launch"""
         if not self.on_device:
             return ()
-        desc_dev = torch.from_numpy(self.samples.view(np.uint8).reshape(-1)).to(out_dev.device)
+        desc_dev = torch.from_numpy(self._descriptors()).to(out_dev.device)
         return (self._coded_dev, desc_dev) + tuple(self._launch(self._coded_dev, desc_dev, out_dev))
+
+
+def upload_decoded(decoded, device, on_device, on_host):
+    """the device output pool of a batch of which `on_device` samples are finished by launches and `on_host` were decoded
+    into the host pool `decoded`: with nothing for the device the host's pool goes up as it is; otherwise the host's bytes go
+    up only if there are any"""
+    if not on_device:
+        return decoded.to(device, non_blocking=True)
+    out = torch.empty(decoded.numel(), dtype=decoded.dtype, device=device)
+    if on_host:
+        out.copy_(decoded, non_blocking=True)
+    return out
