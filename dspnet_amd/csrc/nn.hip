@@ -1980,13 +1980,16 @@ static void bn_group_tiles(hipStream_t s, BnTiles &t, int C, void *scratch, size
 
 // The finalize of a BatchNorm backward over a table of sums, described once (bn_final_job.h): launched by bn_final_launch or
 // parked as it is.  The last four (piece planes only): what the bound of dx is formed from and where it goes
-static dspn::BnFinalJob bn_final_job(const float *table, int tiles, int C, long long rows, const float *mean, const float *rstd,
-                                     const float *gamma, float *coef, float *dgamma, float *dbeta, const float *dy_absmax = nullptr,
+// fixed_stats: mean / rstd are not the batch's (the moving statistics of a DSPN_BN_GLOBAL forward), so dx has no term through
+// them -- inv_rows = 0 turns the finalize arithmetic into a = gamma rstd, c1 = c0 = 0 (dbeta = S, dgamma = SS as ever)
+static dspn::BnFinalJob bn_final_job(const float *table, int tiles, int C, long long rows, int fixed_stats, const float *mean,
+                                     const float *rstd, const float *gamma, float *coef, float *dgamma, float *dbeta,
+                                     const float *dy_absmax = nullptr,
                                      const float *x_minmax = nullptr, float *dx_bound = nullptr, float *dx_bound_min = nullptr) {
   dspn::BnFinalJob j;
   j.tile_sums = table; j.tiles = tiles; j.C = C;
   j.blocks = (C + dspn::kBnJobChannels - 1) / dspn::kBnJobChannels;
-  j.inv_rows = 1.0 / (double)rows; j.mean = mean; j.rstd = rstd; j.gamma = gamma; j.coef = coef; j.dgamma = dgamma; j.dbeta = dbeta;
+  j.inv_rows = fixed_stats ? 0.0 : 1.0 / (double)rows; j.mean = mean; j.rstd = rstd; j.gamma = gamma; j.coef = coef; j.dgamma = dgamma; j.dbeta = dbeta;
   j.dy_absmax = dy_absmax; j.x_minmax = x_minmax;
   j.dx_bound = reinterpret_cast<unsigned *>(dx_bound); j.dx_bound_min = reinterpret_cast<unsigned *>(dx_bound_min);
   return j;
@@ -2156,11 +2159,12 @@ int dspn_absmax_affine_bound_f32(const float *scale, const float *shift, int C, 
 }
 #endif
 
-int DSPN_FN(dspn_bn_backward)(const st_t *x, const float *scale, const float *shift, const st_t *dy,
-                         const float *mean, const float *rstd, const float *gamma, st_t *dx,
-                         float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
-                         float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream) {
+int DSPN_FN(dspn_bn_backward_ex)(const st_t *x, const float *scale, const float *shift, const st_t *dy,
+                            const float *mean, const float *rstd, const float *gamma, st_t *dx,
+                            float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
+                            float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream, int fixed_stats) {
   DSPN_REQUIRE(x && dy && mean && rstd && workspace, "bn_backward: null pointer");
+  DSPN_REQUIRE(fixed_stats == 0 || fixed_stats == 1, "bn_backward: fixed_stats must be 0 or 1");
   DSPN_REQUIRE(!relu || (scale && shift), "bn_backward: relu needs the forward scale/shift");
   DSPN_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, "bn_backward: C must be a positive multiple of 4");
   if (workspace_bytes < bn_workspace_bytes(rows, C))
@@ -2172,17 +2176,26 @@ int DSPN_FN(dspn_bn_backward)(const st_t *x, const float *scale, const float *sh
                      sizeof(float4) * 2 * kT, S_(stream), CA4Ptr(x),
                      reinterpret_cast<const float4 *>(scale), reinterpret_cast<const float4 *>(shift),
                      CA4Ptr(dy), mean, rstd, rows, C4, CL, relu, partial, slab_rows_for(rows), PoolGrad{});
-  bn_final_launch(S_(stream), bn_final_job(partial, ns, C, rows, mean, rstd, gamma, coef, dgamma, dbeta));
+  bn_final_launch(S_(stream), bn_final_job(partial, ns, C, rows, fixed_stats, mean, rstd, gamma, coef, dgamma, dbeta));
   if (!dx) return dspn::check_launch("bn_backward (parameters only)");     // dx == NULL: the reductions and the finalize alone
   return bn_bwd_apply_launch(S_(stream), x, scale, shift, dy, coef, dx, rows, C, relu, accumulate, dx_absmax, "bn_backward");
 }
+int DSPN_FN(dspn_bn_backward)(const st_t *x, const float *scale, const float *shift, const st_t *dy,
+                         const float *mean, const float *rstd, const float *gamma, st_t *dx,
+                         float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
+                         float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream) {
+  return DSPN_FN(dspn_bn_backward_ex)(x, scale, shift, dy, mean, rstd, gamma, dx, dgamma, dbeta, rows, C, relu, accumulate, dx_absmax,
+                                      workspace, workspace_bytes, stream, 0);
+}
 
 #ifndef DSPN_HALF
-int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float *shift, const float *dy_pool,
-                                 const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
-                                 int Wo, const float *mean, const float *rstd, const float *gamma, float *dx, float *dgamma,
-                                 float *dbeta, int relu, float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream) {
+int dspn_bn_backward_maxpool_ex_f32(const float *x, const float *scale, const float *shift, const float *dy_pool,
+                                    const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
+                                    int Wo, const float *mean, const float *rstd, const float *gamma, float *dx, float *dgamma,
+                                    float *dbeta, int relu, float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream,
+                                    int fixed_stats) {
   DSPN_REQUIRE(x && dy_pool && argmax && mean && rstd && workspace, "bn_backward_maxpool: null pointer");
+  DSPN_REQUIRE(fixed_stats == 0 || fixed_stats == 1, "bn_backward_maxpool: fixed_stats must be 0 or 1");
   DSPN_REQUIRE(!relu || (scale && shift), "bn_backward_maxpool: relu needs the forward scale/shift");
   DSPN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && k > 0 && k * k <= 255 && stride > 0 && pad >= 0 && Ho > 0 && Wo > 0,
                "bn_backward_maxpool: bad geometry (C %% 4 == 0, k * k <= 255)");
@@ -2197,7 +2210,7 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
   hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3(ns, (C4 + CL - 1) / CL), dim3(kT), sizeof(float4) * 2 * kT, S_(stream),
                      CA4Ptr(x), reinterpret_cast<const float4 *>(scale), reinterpret_cast<const float4 *>(shift),
                      CA4Ptr(x), mean, rstd, rows, C4, CL, relu, partial, slab_rows_for(rows), pool);
-  bn_final_launch(S_(stream), bn_final_job(partial, ns, C, rows, mean, rstd, gamma, coef, dgamma, dbeta));
+  bn_final_launch(S_(stream), bn_final_job(partial, ns, C, rows, fixed_stats, mean, rstd, gamma, coef, dgamma, dbeta));
   if (!dx) return dspn::check_launch("bn_backward_maxpool (parameters only)");
   const long long n4 = rows * C4;
   hipLaunchKernelGGL(bn_bwd_apply_pool_kernel, dim3(grid_for(n4)), dim3(256), 0, S_(stream), reinterpret_cast<const float4 *>(x),
@@ -2205,6 +2218,13 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
                      reinterpret_cast<const float4 *>(coef), reinterpret_cast<float4 *>(dx), n4, C4, relu,
                      reinterpret_cast<unsigned *>(dx_absmax), pool);
   return dspn::check_launch("bn_backward_maxpool");
+}
+int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float *shift, const float *dy_pool,
+                                 const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
+                                 int Wo, const float *mean, const float *rstd, const float *gamma, float *dx, float *dgamma,
+                                 float *dbeta, int relu, float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream) {
+  return dspn_bn_backward_maxpool_ex_f32(x, scale, shift, dy_pool, argmax, N, H, W, C, k, stride, pad, Ho, Wo, mean, rstd, gamma, dx,
+                                         dgamma, dbeta, relu, dx_absmax, workspace, workspace_bytes, stream, 0);
 }
 #endif
 
@@ -2231,16 +2251,20 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
                                    int tiles, st_t *dx, float *dgamma, float *dbeta, long long rows, int C, int relu,
                                    int accumulate, float *dx_absmax, float *dx_absmin, const float *dy_absmax, const float *x_chan_minmax,
                                    int flags, void *workspace, size_t workspace_bytes, void *stream) {
-  // the flag word (DSPN_BN_SUMS_*, include/dspn_nn.h): dx as piece planes; which half of the call runs (0: both); parked
+  // the flag word (DSPN_BN_SUMS_*, include/dspn_nn.h): dx as piece planes; which half of the call runs (0: both); parked;
+  // fixed statistics (the finalize's business alone: the apply half reads coefficients)
   const int planes = flags & DSPN_BN_SUMS_PLANES, half = flags & (DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY),
-            parked = flags & DSPN_BN_SUMS_PARKED;
-  DSPN_REQUIRE((flags & ~(DSPN_BN_SUMS_PLANES | DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY | DSPN_BN_SUMS_PARKED)) == 0 &&
+            parked = flags & DSPN_BN_SUMS_PARKED, fixed_stats = (flags & DSPN_BN_SUMS_FIXED_STATS) != 0;
+  DSPN_REQUIRE((flags & ~(DSPN_BN_SUMS_PLANES | DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY | DSPN_BN_SUMS_PARKED |
+                          DSPN_BN_SUMS_FIXED_STATS)) == 0 &&
                    half != (DSPN_BN_SUMS_FINALIZE_ONLY | DSPN_BN_SUMS_APPLY_ONLY) && (!parked || half == DSPN_BN_SUMS_FINALIZE_ONLY),
-               "bn_backward_from_sums: flag word = dx_planes | 2 (finalize only, | 8: parked for the next weight gradient) | 4 (apply only)");
+               "bn_backward_from_sums: flag word = dx_planes | 2 (finalize only, | 8: parked for the next weight gradient) | 4 (apply only) "
+               "| 16 (fixed statistics)");
   // (the finalize reads no dy: a caller whose data gradient stored none -- dspn_conv2d_dgrad_bn_sums -- passes NULL with flag 2)
   DSPN_REQUIRE(x && (dy || half == DSPN_BN_SUMS_FINALIZE_ONLY) && mean && rstd && workspace && tile_sums && tiles > 0, "bn_backward_from_sums: null pointer");
   // dx == NULL (parameters only): the finalize alone, nothing parked -- no apply half follows
-  DSPN_REQUIRE(dx || flags == DSPN_BN_SUMS_FINALIZE_ONLY, "bn_backward_from_sums: dx == NULL needs the finalize-only flag word 2");
+  DSPN_REQUIRE(dx || (flags & ~DSPN_BN_SUMS_FIXED_STATS) == DSPN_BN_SUMS_FINALIZE_ONLY,
+               "bn_backward_from_sums: dx == NULL needs the finalize-only flag word 2");
   DSPN_REQUIRE(!planes || (!dspn::kHalf && !accumulate && C % 32 == 0 && dx_absmax && dy_absmax && x_chan_minmax &&
                            static_cast<const void *>(dx) != static_cast<const void *>(dy) && static_cast<const void *>(dx) != static_cast<const void *>(x)),
                "bn_backward_from_sums: dx as piece planes needs float tensors, C %% 32 == 0, no accumulation, dx apart from x and dy, "
@@ -2257,7 +2281,7 @@ int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const
     // a long table is grouped by a launch of its own, now, also where the rest is parked (that level needs hundreds of workgroups)
     BnTiles t{tile_sums, tiles, 1, tiles, nullptr};
     bn_group_tiles<1>(S_(stream), t, C, coef + 3 * (size_t)C, workspace_bytes - coef_bytes);
-    const dspn::BnFinalJob job = bn_final_job(t.table, t.tiles, C, rows, mean, rstd, gamma, coef, dgamma, dbeta,
+    const dspn::BnFinalJob job = bn_final_job(t.table, t.tiles, C, rows, fixed_stats, mean, rstd, gamma, coef, dgamma, dbeta,
                                               planes ? dy_absmax : nullptr, planes ? x_chan_minmax : nullptr,
                                               planes ? dx_absmax : nullptr, planes ? dx_absmin : nullptr);
     if (parked) {      // for the next weight-gradient launch on this stream (bn_final_job.h)

@@ -780,6 +780,27 @@ class Graph:
             p.data.copy_(torch.from_numpy(dev))
             self.frozen_stale = self.frozen_stale or p.fixed
 
+    def set_global_stats(self, names_or_pattern):
+        """Switch BatchNorm nodes to their moving statistics -- mx.sym.BatchNorm(use_global_stats=True):
+        the forward normalises with moving_mean / moving_var and leaves them alone, the backward treats them as constants.
+        names_or_pattern: a regular expression matched (re.match) against the BatchNorm names of bn_nodes, or an iterable of
+        names.  Before finalize().  -> the names switched, in graph order; a pattern or name without a BatchNorm raises"""
+        if self.arena is not None:
+            raise RuntimeError("set_global_stats: call it before finalize()")
+        if isinstance(names_or_pattern, str):
+            rx = re.compile(names_or_pattern)
+            names = [n for n in self.bn_nodes if rx.match(n)]
+            if not names:
+                raise ValueError("set_global_stats: pattern %r matches no BatchNorm" % names_or_pattern)
+        else:
+            names = list(names_or_pattern)
+            unknown = [n for n in names if n not in self.bn_nodes]
+            if unknown:
+                raise ValueError("set_global_stats: no BatchNorm named " + ", ".join(unknown[:8]))
+        for n in names:
+            self.bn_nodes[n].use_global_stats = True
+        return names
+
     def get_aux(self):
         """-> the moving statistics in the reference's aux-state names and shapes: '<bn>_moving_mean' / '<bn>_moving_var'
         -> (channels,) float32 numpy arrays, pad channels dropped"""
@@ -906,7 +927,10 @@ class BatchNorm(Node):
     Moving statistics (MXNet's aux states): moving_mean / moving_var (C device floats, 0 / 1 at creation, pad lanes stay
     so) advance with `momentum` in the statistics finalize of a forward that the solver runs for a parameter update
     (Graph.bn_track); with Graph.bn_global the node normalises with them instead of the batch's (use_global_stats: the
-    finalize folds them into scale / shift, no statistics pass).  include/dspn_nn.h dspn_bn_moving."""
+    finalize folds them into scale / shift, no statistics pass).  include/dspn_nn.h dspn_bn_moving.
+    A use_global_stats node of a TRAINING graph (Graph.set_global_stats, the training builders'
+    global_stats_pattern) keeps its moving statistics through a step and runs the fixed-statistics backward:
+    dx = gamma rstd dy', dgamma / dbeta the usual sums against the moving statistics."""
 
     def __init__(self, g, x, name, fix_gamma=False, eps=2e-5, relu=False, beta_grad_from_consumer=False,
                  defer_apply=False):
@@ -1062,6 +1086,10 @@ class BatchNorm(Node):
         # frozen gamma / beta: not computed (NULL to the kernels); dgamma stays None where there is no gamma (fix_gamma)
         dgam = None if self.gamma is None else (fn.NO_OUTPUT if self.gamma.fixed else self.gamma.grad)
         dbet = fn.NO_OUTPUT if self.beta.fixed else self.beta.grad
+        # use_global_stats under training: mean / rstd are the moving statistics the forward finalize wrote, so dx has no term
+        # through them (include/dspn_nn.h DSPN_BN_SUMS_FIXED_STATS).  Every route below takes the mode; the kw dict of
+        # _from_sums carries it into the parked finalize and the finalize in front of a recomputed data gradient
+        fixed = self.use_global_stats
         if self.x.requires_grad:
             dx, acc = self.x.grad_target()
             # "f16x2" math: dx is the output gradient of the convolution that produced x; when this call completes it (a
@@ -1078,7 +1106,7 @@ class BatchNorm(Node):
             if not acc:
                 fn.bn_backward_maxpool(self.x.data, self.scale, self.shift, dyp, argmax, k, s, p, self.mean, self.rstd,
                                        None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx,
-                                       dgamma=dgam, dbeta=dbet, dx_absmax=am)
+                                       dgamma=dgam, dbeta=dbet, dx_absmax=am, fixed_stats=fixed)
                 return
             # (a second writer of x's gradient: materialise the pooling backward after all)
             fn.maxpool_backward_argmax(argmax, dyp, self.out.shape, k, s, p, dx=self.out.own_grad())
@@ -1091,19 +1119,19 @@ class BatchNorm(Node):
                                      None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
                             dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=False, dx_absmax=am,
                                  dy_absmax=g.mag.block(self.am_dyin), x_chan_minmax=self.x_ext, dx_planes=True,
-                                 dx_absmin=g.mag.min_view(prod.am_dy) if g.guard["enabled"] else None))
+                                 dx_absmin=g.mag.min_view(prod.am_dy) if g.guard["enabled"] else None, fixed_stats=fixed))
             self.x.grad_planes = True
             return
         if self.bwd_sums_ready:      # the two reductions came out of the data-gradient kernel's epilogue
             self.bwd_sums_ready = False
             self._from_sums(beside, (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
                                      None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
-                            dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=acc, dx_absmax=am))
+                            dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=acc, dx_absmax=am, fixed_stats=fixed))
             return
         assert not beside, "finalize_beside() without the data gradient's sums"
         fn.bn_backward(self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
                        None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet,
-                       accumulate=acc, dx_absmax=am)
+                       accumulate=acc, dx_absmax=am, fixed_stats=fixed)
 
 
 # round 6: the weight gradients of the step's stream on a stream of their own (Graph.wgrad_beside): nothing on the critical

@@ -73,6 +73,8 @@ _lib.register({
     "dspn_absmax_affine_bound_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "dspn_bn_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _sz,
                                   _vp]),
+    "dspn_bn_backward_ex_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _sz,
+                                     _vp, _i]),
     "dspn_add_f32": (_i, [_vp, _vp, _vp, _ll, _vp]),
     "dspn_relu_backward_f32": (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
     "dspn_fill_f32": (_i, [_vp, _f, _ll, _vp]),
@@ -99,6 +101,8 @@ _lib.register({
     "dspn_maxpool_backward_argmax_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dspn_bn_backward_maxpool_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _i, _vp, _vp, _sz, _vp]),
+    "dspn_bn_backward_maxpool_ex_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "dspn_maxpool_backward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dspn_avgpool_forward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dspn_avgpool_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -130,7 +134,7 @@ _lib.register({
 # the bfloat16-tensor twins (include/dspn_nn.h): same argument lists as the *_f32 entries
 for _name in ("dspn_conv2d_forward_bn", "dspn_conv2d_dgrad_bn", "dspn_conv2d_dgrad_bn_sadd", "dspn_conv2d_dgrad_bn_sums",
               "dspn_conv2d_dgrad_bn_apply", "dspn_conv2d_wgrad_bn", "dspn_conv2d_wgrad_slabs",
-              "dspn_conv2d_input_sum_grad", "dspn_bn_stats", "dspn_bn_apply", "dspn_bn_backward",
+              "dspn_conv2d_input_sum_grad", "dspn_bn_stats", "dspn_bn_apply", "dspn_bn_backward", "dspn_bn_backward_ex",
               "dspn_bn_backward_from_sums", "dspn_add", "dspn_relu_backward", "dspn_relu_backward_colsum", "dspn_colsum",
               "dspn_nchw_to_nhwc", "dspn_copy_block", "dspn_tap_sum", "dspn_tap_spread", "dspn_maxpool_forward", "dspn_maxpool_forward_bn",
               "dspn_maxpool_backward_argmax", "dspn_maxpool_backward", "dspn_avgpool_forward", "dspn_avgpool_backward",
@@ -569,7 +573,7 @@ def conv_dgrad_bn_tiles(x_shape, stride):
 MATH_DY_PLANES = 0x200       # include/dspn_nn.h DSPN_MATH_DY_PLANES
 MATH_X_PLANES = 0x400        # include/dspn_nn.h DSPN_MATH_X_PLANES
 # the flag word of dspn_bn_backward_from_sums_* (include/dspn_nn.h DSPN_BN_SUMS_*)
-BN_SUMS_PLANES, BN_SUMS_FINALIZE_ONLY, BN_SUMS_APPLY_ONLY, BN_SUMS_PARKED = 1, 2, 4, 8
+BN_SUMS_PLANES, BN_SUMS_FINALIZE_ONLY, BN_SUMS_APPLY_ONLY, BN_SUMS_PARKED, BN_SUMS_FIXED_STATS = 1, 2, 4, 8, 16
 
 
 def conv2d_dgrad_addend_route(x_shape, ldy, dy_planes):
@@ -834,38 +838,40 @@ def _bn_outputs(x, gamma, dx, dgamma, dbeta):
 
 
 def bn_backward(x, scale, shift, dy, mean, rstd, gamma, relu=False, dx=None, dgamma=None, dbeta=None,
-                accumulate=False, dx_absmax=None):
+                accumulate=False, dx_absmax=None, fixed_stats=False):
     """dx_absmax: 64-float magnitude block that receives the partial maxima of |dx| as stored (see absmax).
-    dx / dgamma / dbeta = NO_OUTPUT: not computed (dx: reductions and finalize only, dgamma / dbeta bit-identical)"""
+    dx / dgamma / dbeta = NO_OUTPUT: not computed (dx: reductions and finalize only, dgamma / dbeta bit-identical).
+    fixed_stats: mean / rstd are not the batch's (a forward under BN_GLOBAL): dx (+)= gamma rstd dy', the same dgamma / dbeta"""
     C = x.shape[-1]
     rows = _rows(x)
     dx, dgamma, dbeta = _bn_outputs(x, gamma, dx, dgamma, dbeta)
     ws = workspace(L().dspn_bn_workspace_bytes(rows, C), x.device, "bn")
     assert dy.dtype == x.dtype
-    check(_f("dspn_bn_backward", x)(ptr(x), ptr(scale), ptr(shift), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
-                                   ptr(dgamma), ptr(dbeta), rows, C, int(relu), int(accumulate), ptr(dx_absmax), ptr(ws),
-                                   ws.numel(), stream()), "bn_backward")
+    check(_f("dspn_bn_backward_ex", x)(ptr(x), ptr(scale), ptr(shift), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
+                                      ptr(dgamma), ptr(dbeta), rows, C, int(relu), int(accumulate), ptr(dx_absmax), ptr(ws),
+                                      ws.numel(), stream(), int(bool(fixed_stats))), "bn_backward")
     return dx, dgamma, dbeta
 
 
 def bn_backward_maxpool(x, scale, shift, dy_pool, argmax, k, stride, pad, mean, rstd, gamma, relu=False, dx=None, dgamma=None,
-                        dbeta=None, dx_absmax=None):
+                        dbeta=None, dx_absmax=None, fixed_stats=False):
     """bn_backward whose output gradient is the max-pooling backward of dy_pool (argmax record), formed on the fly: the
-    BatchNorm(+ReLU) -> max pooling pair of the resnet stem without the dense gradient tensor in between (float32)"""
+    BatchNorm(+ReLU) -> max pooling pair of the resnet stem without the dense gradient tensor in between (float32).
+    fixed_stats: as bn_backward"""
     N, H, W, C = x.shape
     assert x.dtype == dy_pool.dtype == torch.float32 and argmax.dtype == torch.uint8 and argmax.shape == dy_pool.shape
     dx, dgamma, dbeta = _bn_outputs(x, gamma, dx, dgamma, dbeta)
     ws = workspace(L().dspn_bn_workspace_bytes(N * H * W, C), x.device, "bn")
-    check(L().dspn_bn_backward_maxpool_f32(ptr(x), ptr(scale), ptr(shift), ptr(dy_pool), ptr(argmax), N, H, W, C, k, stride, pad,
-                                           dy_pool.shape[1], dy_pool.shape[2], ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
-                                           ptr(dgamma), ptr(dbeta), int(relu), ptr(dx_absmax), ptr(ws), ws.numel(), stream()),
-          "bn_backward_maxpool")
+    check(L().dspn_bn_backward_maxpool_ex_f32(ptr(x), ptr(scale), ptr(shift), ptr(dy_pool), ptr(argmax), N, H, W, C, k, stride,
+                                              pad, dy_pool.shape[1], dy_pool.shape[2], ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
+                                              ptr(dgamma), ptr(dbeta), int(relu), ptr(dx_absmax), ptr(ws), ws.numel(), stream(),
+                                              int(bool(fixed_stats))), "bn_backward_maxpool")
     return dx, dgamma, dbeta
 
 
 def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, relu=False, dx=None, dgamma=None,
                           dbeta=None, accumulate=False, dx_absmax=None, dy_absmax=None, x_chan_minmax=None, dx_planes=False,
-                          dx_absmin=None, phase=0, park=False, workspace=None):
+                          dx_absmin=None, phase=0, park=False, workspace=None, fixed_stats=False):
     """bn_backward with the two reductions already gathered per row tile (conv2d_dgrad(bn_bwd=...)).
     dx_planes ("f16x2" math): dx is written as fp16 piece planes (same bytes, same buffer shape) cut by the power of two of a
     BOUND of |dx| that is formed from dy_absmax (the magnitude block of dy, conv2d_dgrad's bn_dy_absmax) and x_chan_minmax
@@ -876,7 +882,9 @@ def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, r
     it on its own if no weight gradient came by.
     workspace: a bn_from_sums_workspace(tiles, C) buffer of the caller's.  Phases 1 and 2 hand the coefficients over in it, so a
     caller with several BatchNorms between their two halves gives each its own (engine.BatchNorm.bwd_ws); without one, a
-    scratch buffer of this function's that the next call without one overwrites"""
+    scratch buffer of this function's that the next call without one overwrites.
+    fixed_stats: as bn_backward -- the flag bit BN_SUMS_FIXED_STATS in every phase (the finalize's business; phase 2 reads
+    coefficients and ignores it)"""
     assert phase in (0, 1, 2) and (not park or phase == 1)
     C = x.shape[-1]
     rows = _rows(x)
@@ -885,7 +893,7 @@ def bn_backward_from_sums(x, scale, shift, dy, mean, rstd, gamma, sums, tiles, r
         assert phase == 0 and not park and not dx_planes, "dx=NO_OUTPUT is a whole call"
         phase = 1
     flags = ((BN_SUMS_PLANES if dx_planes else 0) | {0: 0, 1: BN_SUMS_FINALIZE_ONLY, 2: BN_SUMS_APPLY_ONLY}[phase] |
-             (BN_SUMS_PARKED if park else 0))
+             (BN_SUMS_PARKED if park else 0) | (BN_SUMS_FIXED_STATS if fixed_stats else 0))
     if workspace is None:
         workspace = _scratch(12 * C + L().dspn_bn_tiles_workspace_bytes(tiles, C), x.device, "bn_from_sums")
     assert (dy is None and phase == 1) or dy.dtype == x.dtype      # (the finalize alone reads no dy)

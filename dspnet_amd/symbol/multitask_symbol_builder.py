@@ -270,22 +270,37 @@ class MultiTaskNet:
         return outs if self.seg_out is None else outs + [self.seg_out.nchw()]
 
 
+# the BatchNorms the reference's `use_global_stats` flag reaches: those of the segmentation decoder
+# (symbol/multitask_symbol_builder.py:275-315), as a global_stats_pattern of the training builders
+DECODER_GLOBAL_STATS_PATTERN = r"(res[345]_reduced2?|score2_pool[124]|score3_conv)_bn$"
+EVERY_BATCHNORM_PATTERN = r".*"      # ... and every BatchNorm of the graph
+
+
 def get_multi_symbol_train(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                            normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                            nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), num_labels=200, device=None,
                            num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False,
-                           fixed_param_names=None, freeze_pattern=None,
+                           fixed_param_names=None, freeze_pattern=None, global_stats_pattern=None,
                            **kwargs):
     """symbol/multitask_symbol_builder.py:442-593.
     fixed_param_names / freeze_pattern (every training builder): the parameters to freeze, as mx.mod.Module's
     fixed_param_names -- the names given plus every argument name freeze_pattern matches (re.match, train_multitask.py:
     196-200).  A frozen parameter keeps its value and momentum, and backward skips what only it needed (engine.Graph.set_freeze).
     A name the graph does not know raises ValueError; the `_gamma` of a fix_gamma BatchNorm and the graph inputs are known
-    arguments without effect."""
+    arguments without effect.
+    global_stats_pattern (every training builder): mx.sym.BatchNorm(use_global_stats=True) under training for the BatchNorms
+    whose name it matches (re.match, as freeze_pattern) -- the node normalises with its moving statistics (Graph.set_aux / a
+    checkpoint's aux states; train.solver.recalibrate_bn_stats where those are the 0 / 1 placeholders), a step leaves them
+    as they are, and its backward treats them as constants.  A pattern that matches no BatchNorm raises ValueError.  The
+    reference's own configuration (its module flag reaches the BatchNorms of the segmentation decoder only,
+    symbol/multitask_symbol_builder.py:6, 275-315) is DECODER_GLOBAL_STATS_PATTERN; every BatchNorm is
+    EVERY_BATCHNORM_PATTERN.  The keyword use_global_stats=True itself stays what it was on a training builder, a
+    ValueError (it now names global_stats_pattern): callers and tests rely on that refusal."""
     return _build(True, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios, normalizations,
                   steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape, num_labels, device,
                   num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats,
-                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern)
+                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern,
+                  global_stats_pattern=global_stats_pattern)
 
 
 def get_multi_symbol(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
@@ -309,14 +324,15 @@ def get_det_symbol_train(network, num_classes, from_layers, num_filters, strides
                          normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5, force_suppress=False,
                          nms_topk=400, batch_size=1, data_shape=(3, 300, 300), num_labels=200, device=None,
                          num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False,
-                         fixed_param_names=None, freeze_pattern=None,
+                         fixed_param_names=None, freeze_pattern=None, global_stats_pattern=None,
                          **kwargs):
     """Detection + depth only, symbol/multitask_symbol_builder.py:20-121: outputs [cls_prob, loc_loss, cls_label,
     det_out]; the same graph without the segmentation decoder."""
     return _build(True, False, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
                   num_labels, device, num_layers, seed, bn_mom=bn_mom, use_global_stats=use_global_stats,
-                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern)
+                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern,
+                  global_stats_pattern=global_stats_pattern)
 
 
 def get_det_symbol(network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
@@ -333,7 +349,7 @@ def get_seg_symbol_train(network, num_classes, from_layers, num_filters=None, st
                          ratios=None, normalizations=-1, steps=(), min_filter=128, nms_thresh=0.5,
                          force_suppress=False, nms_topk=400, batch_size=1, data_shape=(3, 512, 1024), device=None,
                          num_layers=50, seed=0, bn_mom=0.9, use_global_stats=False,
-                         fixed_param_names=None, freeze_pattern=None,
+                         fixed_param_names=None, freeze_pattern=None, global_stats_pattern=None,
                          **kwargs):
     """Segmentation only, symbol/multitask_symbol_builder.py:211-323: backbone -> pyramid decoder ->
     SoftmaxOutput(grad_scale=4, ignore 255); output [seg_out].  The SSD arguments are accepted and unused, as
@@ -341,7 +357,8 @@ def get_seg_symbol_train(network, num_classes, from_layers, num_filters=None, st
     return _build(True, True, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios,
                   normalizations, steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape,
                   0, device, num_layers, seed, with_det=False, bn_mom=bn_mom, use_global_stats=use_global_stats,
-                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern)
+                  fixed_param_names=fixed_param_names, freeze_pattern=freeze_pattern,
+                  global_stats_pattern=global_stats_pattern)
 
 
 def get_seg_symbol(network, num_classes, from_layers, num_filters=None, strides=None, pads=None, sizes=None,
@@ -403,16 +420,19 @@ def _check_fixed_names(g, fixed_param_names):
 
 def _build(train, with_seg, network, num_classes, from_layers, num_filters, strides, pads, sizes, ratios, normalizations,
            steps, min_filter, nms_thresh, force_suppress, nms_topk, batch_size, data_shape, num_labels, device,
-           num_layers, seed, with_det=True, bn_mom=0.9, use_global_stats=False, fixed_param_names=None, freeze_pattern=None):
+           num_layers, seed, with_det=True, bn_mom=0.9, use_global_stats=False, fixed_param_names=None, freeze_pattern=None,
+           global_stats_pattern=None):
     assert network in ("resnet", "vgg16_reduced", "inceptionv3"), "backbones: resnet, vgg16_reduced, inceptionv3"
     if train and use_global_stats:
-        raise ValueError("use_global_stats=True is for the test graphs (get_multi_symbol / get_det_symbol / get_seg_symbol): "
-                         "training with fixed BatchNorm statistics (its backward) is not implemented")
+        raise ValueError("use_global_stats=True is the keyword of the test graphs (get_multi_symbol / get_det_symbol / "
+                         "get_seg_symbol); a training graph fixes the statistics of the BatchNorms named by global_stats_pattern "
+                         "(every BatchNorm: EVERY_BATCHNORM_PATTERN)")
     if not 0.0 <= float(bn_mom) <= 1.0:
         raise ValueError("bn_mom must be in [0, 1], got %r" % (bn_mom,))
     device = device or torch.device("cuda", torch.cuda.current_device())
     g = E.Graph(device)
-    # every BatchNorm built below: moving statistics with momentum bn_mom; use_global_stats normalises with them (inference)
+    # every BatchNorm built below: moving statistics with momentum bn_mom; use_global_stats normalises with them (inference);
+    # global_stats_pattern switches the nodes it names once they are all there (training with fixed statistics)
     g.bn_momentum, g.bn_global = float(bn_mom), bool(use_global_stats)
     if isinstance(fixed_param_names, str):
         fixed_param_names = [fixed_param_names]
@@ -448,6 +468,8 @@ def _build(train, with_seg, network, num_classes, from_layers, num_filters, stri
 
     if not with_seg:
         _check_fixed_names(g, fixed_param_names)
+        if global_stats_pattern is not None:
+            g.set_global_stats(global_stats_pattern)
         g.finalize(seed)
         return MultiTaskNet(g, data, label, None,
                             dict(target=target, cls_out=cls_out, loc_loss=loc_loss, det=det, seg_out=None,
@@ -517,6 +539,8 @@ def _build(train, with_seg, network, num_classes, from_layers, num_filters, stri
         # reader is the caller, through det.join()
         g.set_side_segment(det_first, g.nodes.index(det))
     _check_fixed_names(g, fixed_param_names)
+    if global_stats_pattern is not None:
+        g.set_global_stats(global_stats_pattern)
     g.finalize(seed)
     return MultiTaskNet(g, data, label, seg_label,
                         dict(target=target, cls_out=cls_out, loc_loss=loc_loss, det=det, seg_out=seg_out,

@@ -74,7 +74,10 @@ def get_config(network, data_shape, **kwargs):
 
 
 def get_multi_symbol_train(network, data_shape, **kwargs):
-    """symbol/multitask_symbol_factory.py:188-205.  data_shape: int (square) or (C, H, W)."""
+    """symbol/multitask_symbol_factory.py:188-205.  data_shape: int (square) or (C, H, W).
+    Keyword arguments go to the builder, for every training factory here: fixed_param_names / freeze_pattern, and
+    global_stats_pattern (training with fixed BatchNorm statistics; the reference's configuration is
+    builder.DECODER_GLOBAL_STATS_PATTERN, every BatchNorm builder.EVERY_BATCHNORM_PATTERN)."""
     if isinstance(data_shape, int):
         data_shape = (3, data_shape, data_shape)
     config = get_config(network, data_shape, **kwargs)

@@ -16,7 +16,10 @@ BatchNorm moving statistics (MXNet's aux states): with track_bn_stats they advan
 in the forward of an eager step(), of a recorded step and of every warmup step that updates -- and never in the range
 guard's calibration pass, a bare forward(), or an evaluation pass.  Under data parallelism every rank keeps the
 statistics of its own shard (MXNet keeps one set per device); they are not averaged across ranks, and rank 0 writes
-its own to a checkpoint.
+its own to a checkpoint.  A BatchNorm built with fixed statistics (the training builders'
+global_stats_pattern) normalises with its moving statistics and never advances them; the finalize reads them from device
+memory in every forward, so set_aux / load_checkpoint take effect on the next replay of a recorded step
+(recalibrate_bn_stats below gives such a node statistics worth fixing).
 """
 from .. import functional as fn
 
@@ -453,6 +456,43 @@ class MultiTaskSolver:
         self._graph = graph
         self._graph_hyper = (self.lr, self.momentum, self.wd)
         return True
+
+
+def recalibrate_bn_stats(net, batches):
+    """Set the moving statistics of EVERY BatchNorm of `net` to the plain average of the batch statistics over `batches`:
+    forward-only passes, eager, with every node tracking (DSPN_BN_TRACK, also the fixed-statistics nodes, which normalise
+    with the batch's statistics for these passes) and momentum 1 - 1/k on the k-th batch, so that after K batches
+    moving_mean = mean_k(batch mean) and moving_var = mean_k(unbiased batch variance).  The momentum goes to the finalize
+    kernel by value: no recording is involved and none is invalidated (the buffers keep their addresses).
+    For training with fixed statistics (global_stats_pattern) from a checkpoint whose aux states are the
+    0 / 1 placeholders -- the reference zeroes them (multi_solver.py:212) -- where normalising with them would be
+    meaningless.  batches: an iterable of `data` tensors (B,3,H,W) or of (data, label_det, label_seg) tuples as
+    MultiTaskSolver.set_batch takes them (labels do not enter the statistics; None leaves the buffer as it is).
+    Parameters, every node's momentum and mode, and Graph.bn_momentum are as before on return.  -> the number of batches"""
+    g = net.g
+    nodes = list(g.bn_nodes.values())
+    saved = [(n.momentum, n.use_global_stats) for n in nodes]
+    track, k = g.bn_track, 0
+    try:
+        g.bn_track = True
+        for batch in batches:
+            data, label_det, label_seg = batch if isinstance(batch, (tuple, list)) else (batch, None, None)
+            net.data.data.copy_(data)
+            if net.label_det is not None and label_det is not None:
+                net.label_det.data.copy_(label_det)
+            if net.label_seg is not None and label_seg is not None:
+                net.label_seg.data.copy_(label_seg)
+            k += 1
+            for n in nodes:
+                n.momentum, n.use_global_stats = 1.0 - 1.0 / k, False
+            g.forward()
+    finally:
+        g.bn_track = track
+        for n, (momentum, use_global_stats) in zip(nodes, saved):
+            n.momentum, n.use_global_stats = momentum, use_global_stats
+    if k == 0:
+        raise ValueError("recalibrate_bn_stats: no batches")
+    return k
 
 
 class BatchEndParam(object):

@@ -501,6 +501,22 @@ int dspn_bn_backward_from_sums_f32(const float *x, const float *scale, const flo
 #define DSPN_BN_SUMS_FINALIZE_ONLY 2
 #define DSPN_BN_SUMS_APPLY_ONLY 4
 #define DSPN_BN_SUMS_PARKED 8
+/* | FIXED_STATS = the backward of a BatchNorm whose forward ran with fixed statistics (DSPN_BN_GLOBAL above, under training:
+ * MXNet's use_global_stats with is_train): mean / rstd are the moving statistics the forward wrote, not functions of x, so
+ *   dx (+)= gamma * rstd * dy',  dbeta = sum dy',  dgamma = sum dy' * (x - mean) * rstd.
+ * The sums are those of the batch mode, taken against the mean / rstd handed in (dgamma / dbeta: the same bits); the finalize
+ * forms a = gamma * rstd, c1 = c0 = 0 -- the batch-mode arithmetic with 1 / rows replaced by 0 -- and every apply form
+ * (this call's, the planes form, dspn_conv2d_dgrad_bn_apply_*) reads coefficients, so no kernel knows the mode; the planes
+ * bound is |a| D.  Combines with 0, PLANES, FINALIZE_ONLY and PARKED; with APPLY_ONLY it is accepted and has no effect.
+ * One consequence of the shared arithmetic: a NON-FINITE sum makes c1 / c0 NaN (inf * 0) and with them dx, exactly as it
+ * does in batch mode; dgamma / dbeta are then non-finite too.
+ * dspn_bn_backward_ex_* and dspn_bn_backward_maxpool_ex_f32 take the arguments of the entry point of the same name plus a
+ * trailing `int fixed_stats` (0 or 1) with the same meaning; 0 is exactly the entry point without `_ex`. */
+#define DSPN_BN_SUMS_FIXED_STATS 16
+int dspn_bn_backward_ex_f32(const float *x, const float *scale, const float *shift, const float *dy,
+                            const float *mean, const float *rstd, const float *gamma, float *dx,
+                            float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
+                            float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream, int fixed_stats);
 /* dx_absmin (optional, with DSPN_BN_SUMS_PLANES; round 5): ONE float, preset to +inf by the caller, that receives the smallest non-zero
  * per-channel bound of |dx| -- with dx_absmax, the span of channel magnitudes the planes are cut over (the range guard of
  * DSPN_MATH_F32_F16X2 reads it; elements more than 2^17 below the tensor's largest magnitude lose relative accuracy). */
@@ -583,6 +599,12 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
                                  const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
                                  int Wo, const float *mean, const float *rstd, const float *gamma, float *dx, float *dgamma,
                                  float *dbeta, int relu, float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream);
+/* ... with fixed statistics (fixed_stats = 1: DSPN_BN_SUMS_FIXED_STATS above; 0: the call above) */
+int dspn_bn_backward_maxpool_ex_f32(const float *x, const float *scale, const float *shift, const float *dy_pool,
+                                    const unsigned char *argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
+                                    int Wo, const float *mean, const float *rstd, const float *gamma, float *dx, float *dgamma,
+                                    float *dbeta, int relu, float *dx_absmax, void *workspace, size_t workspace_bytes, void *stream,
+                                    int fixed_stats);
 /* gradient goes to the first maximum of each window in (h, w) scan order; from the argmax record ... */
 int dspn_maxpool_backward_argmax_f32(const unsigned char *argmax, const float *dy, float *dx, int N, int H,
                                      int W, int C, int k, int stride, int pad, int Ho, int Wo, void *stream);
@@ -773,6 +795,10 @@ int dspn_bn_backward_bf16(const dspn_bf16 *x, const float *scale, const float *s
                          const float *mean, const float *rstd, const float *gamma, dspn_bf16 *dx,
                          float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
                          float *dx_absmax_unused, void *workspace, size_t workspace_bytes, void *stream);
+int dspn_bn_backward_ex_bf16(const dspn_bf16 *x, const float *scale, const float *shift, const dspn_bf16 *dy,
+                            const float *mean, const float *rstd, const float *gamma, dspn_bf16 *dx,
+                            float *dgamma, float *dbeta, long long rows, int C, int relu, int accumulate,
+                            float *dx_absmax_unused, void *workspace, size_t workspace_bytes, void *stream, int fixed_stats);
 int dspn_bn_backward_from_sums_bf16(const dspn_bf16 *x, const float *scale, const float *shift, const dspn_bf16 *dy,
                                    const float *mean, const float *rstd, const float *gamma, const float *tile_sums,
                                    int tiles, dspn_bf16 *dx, float *dgamma, float *dbeta, long long rows, int C, int relu,
