@@ -4,7 +4,8 @@
 // through a two-line wrapper `<name>_h.hip` that defines DSPN_HALF and includes it again (bfloat16 tensors, entry
 // points `*_bf16`).  Arithmetic is fp32 in both: a bf16 element is widened on load and rounded to nearest even on
 // store.  Parameters, BatchNorm statistics, per-channel coefficient vectors, split-K slabs, loss inputs and the
-// optimizer state are float in both builds.
+// optimizer state are float in both builds.  Float-only operators (resize, evaluation read-outs, losses, SGD, float
+// layout helpers) live in files compiled once (nn_resize_eval.hip, nn_float_ops.hip), not in a twinned file.
 //
 // The proxies below give the bf16 build the `p[i]` / `p[i] = v` syntax of a float4 / float pointer, so one kernel body
 // serves both storage types.

@@ -1,6 +1,6 @@
-// HBM-bound kernels of the DSPNet multi-task step on MI355X (gfx950): batch-stat
-// BatchNorm (+ReLU) forward/backward, pooling, bilinear sampler, losses, SGD and
-// layout helpers.  C ABI in include/dspn_nn.h.
+// HBM-bound kernels of the DSPNet multi-task step on MI355X (gfx950) that touch activation tensors: batch-stat
+// BatchNorm (+ReLU) forward/backward, pooling, element-wise, column sums, block copies, tap sums and softmax.
+// C ABI in include/dspn_nn.h.
 //
 // All tensors are NHWC fp32 with a physical channel count that is a multiple of
 // 4, so every streaming access is a 16-byte-per-lane float4 with consecutive
@@ -8,6 +8,7 @@
 // in a caller workspace, then a fixed-order finalize in double), never float
 // atomics, so every result is bitwise reproducible run to run.
 #include "dspn_common.h"
+#include "nn_launch.h"
 #include "bn_final_job.h"
 #include "dspn_store.h"
 #include "dspn_pieces.h"
@@ -16,6 +17,8 @@
 // Compiled twice (dspn_store.h): float activations -> `*_f32`, and through nn_h.hip with DSPN_HALF -> bfloat16
 // activations -> `*_bf16` (element proxies CA4Ptr / A4Ptr / CA1Ptr / A1Ptr widen on load and round on store; all
 // arithmetic and every reduction stays fp32 / double).  Entry points that never touch an activation tensor exist once.
+// Float-only code stays here only where it shares a helper, kernel template or struct with the twinned code (the BatchNorm
+// and column-sum pieces); every other float-only operator goes to nn_resize_eval.hip / nn_float_ops.hip, compiled once.
 using dspn::st_t;
 using dspn::A1Ptr;
 using dspn::A4Ptr;
@@ -26,17 +29,14 @@ using dspn::CA4Ptr;
 
 namespace {
 
-constexpr int kT = 256;
+// From nn_launch.h, shared with the once-compiled files: the workgroup size `constexpr int kT = 256;` and the capped grid of a
+// grid-stride launch, `inline int grid_for(long long n, int per_block = kT, int cap = 8192)`.
+
 // rows per slab of the two-stage reductions: 512 on the large tensors; small ones (inceptionv3 at batch 8: 15 k rows)
 // are cut finer so that a reduction still spreads over ~1000 workgroups instead of 29 (2.5 ms per step went there)
 inline int slab_rows_for(long long rows) {
   const long long want = (rows + 1023) / 1024;
   return (int)std::min<long long>(512, std::max<long long>(32, (want + 7) / 8 * 8));
-}
-
-inline int grid_for(long long n, int per_block = kT, int cap = 8192) {
-  long long b = (n + per_block - 1) / per_block;
-  return (int)std::max<long long>(1, std::min<long long>(b, cap));
 }
 
 // grid of a chunked streaming kernel (U x kT consecutive elements per workgroup and step) over n elements of `groups`
@@ -846,13 +846,6 @@ __global__ void relu_bwd_kernel(const CA1Ptr y, const CA1Ptr dy, const A1Ptr dx,
     dx[i] = v;
   }
 }
-#ifndef DSPN_HALF
-__global__ void fill_kernel(float *p, float v, long long n) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x)
-    p[i] = v;
-}
-#endif
 
 // column sums, two stage
 __global__ __launch_bounds__(kT) void colsum_partial_kernel(const CA1Ptr a,
@@ -948,18 +941,6 @@ __global__ void nchw_to_nhwc_kernel(const float *__restrict__ src, const A1Ptr d
       dst[p * Cp + c] = c < C ? src[(n * C + c) * HW + hw] : 0.f;
   }
 }
-#ifndef DSPN_HALF
-__global__ void nhwc_to_nchw_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                    int C, long long HW, long long total, int Cp) {
-  // thread per dst element, hw fastest
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long hw = i % HW, nc = i / HW;
-    const long long n = nc / C; const int c = (int)(nc - n * C);
-    dst[i] = src[(n * HW + hw) * Cp + c];
-  }
-}
-#endif
 // SRC / DST: element pointers of either storage type (the SSD head packing converts bf16 maps into the float
 // (B, N*5) / (B, N*(C+1)) tensors the losses and the multibox operators read, and their gradients back)
 template <typename SRC, typename DST>
@@ -991,42 +972,6 @@ __global__ void copy_block_vec_kernel(const dspn::u32x4_t *__restrict__ src, dsp
     dst[s * dss + rr * ldd + doff + c] = src[s * sss + rr * lds + soff + c];
   }
 }
-#ifndef DSPN_HALF
-// many block copies in ONE launch (the SSD head packing: six small maps per pass): rows sorted by `begin`, the first
-// element of the row's range in the launch's flat index space, found by binary search (as slab_reduce_batch_kernel)
-struct CopyDesc { const float *src; float *dst; long long rows_per_sample, sss, dss; int C, lds, soff, ldd, doff, accumulate; long long begin; };
-static_assert(sizeof(CopyDesc) == 72, "copy_block_batch table row (dspnet_amd/functional.py copy_block_table)");
-__global__ void copy_block_batch_kernel(const CopyDesc *__restrict__ d, int n, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (d[mid].begin <= i) lo = mid; else hi = mid - 1;
-    }
-    const CopyDesc e = d[lo];
-    const long long j = i - e.begin;
-    const int c = (int)(j % e.C);
-    const long long r = j / e.C;
-    const long long sm = r / e.rows_per_sample, rr = r - sm * e.rows_per_sample;
-    const float v = e.src[sm * e.sss + rr * e.lds + e.soff + c];
-    const long long di = sm * e.dss + rr * e.ldd + e.doff + c;
-    e.dst[di] = e.accumulate ? e.dst[di] + v : v;
-  }
-}
-__global__ void transpose_bnc_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                     int N, int C, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int n = (int)(i % N);
-    const long long bc = i / N;
-    const int c = (int)(bc % C);
-    const long long b = bc / C;
-    dst[i] = src[(b * N + n) * C + c];
-  }
-}
-#endif
-
 
 // ------------------------------------------------------------------ tap-expanded convolution
 // A stride-1 RxS convolution with very few output channels (score3_conv: 3328 -> 19) starves the
@@ -1317,458 +1262,6 @@ __global__ void avgpool2d_bwd_kernel(const CA4Ptr dy, const A4Ptr dx, int H, int
   }
 }
 
-#ifndef DSPN_HALF   // plain resize (identity grid) and the evaluation read-outs: float tensors only
-// ------------------------------------------------------------------ bilinear sampler
-// GridGenerator(affine identity, target (Ho,Wo)) + BilinearSampler: normalised target coordinate
-// g = -1 + o*2/(O-1); source coordinate s = (g+1)*(I-1)/2; corners outside [0,I-1] contribute 0.
-__device__ __forceinline__ float src_coord(int o, int O, int I) {
-  const float g = O > 1 ? -1.f + (float)o * (2.f / (float)(O - 1)) : 0.f;
-  return (g + 1.f) * (float)(I - 1) / 2.f;
-}
-template <bool ACC>   // ACC: y += resize(x) (sum of several resized maps in a fixed order)
-__global__ void bilinear_fwd_kernel(const float4 *__restrict__ x, float *__restrict__ y, int Hin,
-                                    int Win, int C4, int Ho, int Wo, int ldo, int coff, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % C4);
-    long long t = i / C4;
-    const int wo = (int)(t % Wo); t /= Wo;
-    const int ho = (int)(t % Ho);
-    const long long n = t / Ho;
-    const float ys = src_coord(ho, Ho, Hin), xs = src_coord(wo, Wo, Win);
-    const int y0 = (int)floorf(ys), x0 = (int)floorf(xs);
-    const float wy0 = 1.f - (ys - (float)y0), wx0 = 1.f - (xs - (float)x0);
-    float4 acc = make_float4(0, 0, 0, 0);
-#pragma unroll
-    for (int dyy = 0; dyy < 2; ++dyy)
-#pragma unroll
-      for (int dxx = 0; dxx < 2; ++dxx) {
-        const int yy = y0 + dyy, xx = x0 + dxx;
-        if ((unsigned)yy >= (unsigned)Hin || (unsigned)xx >= (unsigned)Win) continue;
-        const float wgt = (dyy ? 1.f - wy0 : wy0) * (dxx ? 1.f - wx0 : wx0);
-        const float4 v = x[((n * Hin + yy) * Win + xx) * C4 + c4];
-        acc.x += wgt * v.x; acc.y += wgt * v.y; acc.z += wgt * v.z; acc.w += wgt * v.w;
-      }
-    float4 *o = reinterpret_cast<float4 *>(y + ((n * Ho + ho) * Wo + wo) * (long long)ldo + coff + c4 * 4);
-    if (ACC) { const float4 p = *o; acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w; }
-    *o = acc;
-  }
-}
-// gather form of the backward: every source pixel collects from the target pixels that touch it
-__global__ void bilinear_bwd_kernel(const float *__restrict__ dy, float4 *__restrict__ dx, int Hin,
-                                    int Win, int C4, int Ho, int Wo, int ldo, int coff, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % C4);
-    long long t = i / C4;
-    const int w = (int)(t % Win); t /= Win;
-    const int h = (int)(t % Hin);
-    const long long n = t / Hin;
-    // candidate target range: |s(o) - h| < 1  (s is monotone in o); widen by one and test exactly
-    const float sy = Hin > 1 ? (float)(Ho - 1) / (float)(Hin - 1) : 0.f;
-    const float sx = Win > 1 ? (float)(Wo - 1) / (float)(Win - 1) : 0.f;
-    int ho_lo = Hin > 1 ? (int)floorf((float)(h - 1) * sy) - 1 : 0;
-    int ho_hi = Hin > 1 ? (int)ceilf((float)(h + 1) * sy) + 1 : Ho - 1;
-    int wo_lo = Win > 1 ? (int)floorf((float)(w - 1) * sx) - 1 : 0;
-    int wo_hi = Win > 1 ? (int)ceilf((float)(w + 1) * sx) + 1 : Wo - 1;
-    ho_lo = max(ho_lo, 0); wo_lo = max(wo_lo, 0); ho_hi = min(ho_hi, Ho - 1); wo_hi = min(wo_hi, Wo - 1);
-    float4 acc = make_float4(0, 0, 0, 0);
-    for (int ho = ho_lo; ho <= ho_hi; ++ho) {
-      const float ys = src_coord(ho, Ho, Hin);
-      const int y0 = (int)floorf(ys);
-      float wy;
-      if (y0 == h) wy = 1.f - (ys - (float)y0);
-      else if (y0 + 1 == h) wy = ys - (float)y0;
-      else continue;
-      for (int wo = wo_lo; wo <= wo_hi; ++wo) {
-        const float xs = src_coord(wo, Wo, Win);
-        const int x0 = (int)floorf(xs);
-        float wx;
-        if (x0 == w) wx = 1.f - (xs - (float)x0);
-        else if (x0 + 1 == w) wx = xs - (float)x0;
-        else continue;
-        const float wgt = wy * wx;
-        const float4 v = *reinterpret_cast<const float4 *>(
-            dy + ((n * Ho + ho) * Wo + wo) * (long long)ldo + coff + c4 * 4);
-        acc.x += wgt * v.x; acc.y += wgt * v.y; acc.z += wgt * v.z; acc.w += wgt * v.w;
-      }
-    }
-    dx[i] = acc;
-  }
-}
-
-// Separable form of the same backward pass (the bilinear weights factor into wy * wx): first along W into a
-// (N, Ho, Win, C) scratch tensor, then along H.  A source pixel of a map upsampled by s collects from ~2s targets per
-// pass instead of ~(2s)^2 (the 4x4 pyramid level upsampled to 64x64: 84 loads instead of 1764), and the first pass
-// has N*Ho*Win*C/4 threads however small the source map is.
-__device__ __forceinline__ void bl_range(int i, int I, int O, int &lo, int &hi) {
-  const float s = I > 1 ? (float)(O - 1) / (float)(I - 1) : 0.f;
-  lo = I > 1 ? (int)floorf((float)(i - 1) * s) - 1 : 0;
-  hi = I > 1 ? (int)ceilf((float)(i + 1) * s) + 1 : O - 1;
-  lo = max(lo, 0); hi = min(hi, O - 1);
-}
-__device__ __forceinline__ bool bl_weight(int o, int O, int I, int i, float &wgt) {
-  const float ss = src_coord(o, O, I);
-  const int i0 = (int)floorf(ss);
-  if (i0 == i) { wgt = 1.f - (ss - (float)i0); return true; }
-  if (i0 + 1 == i) { wgt = ss - (float)i0; return true; }
-  return false;
-}
-__global__ void bilinear_bwd_w_kernel(const float *__restrict__ dy, float4 *__restrict__ tmp, int Win, int C4,
-                                      int Ho, int Wo, int ldo, int coff, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % C4);
-    long long t = i / C4;
-    const int w = (int)(t % Win); t /= Win;          // t = n * Ho + ho
-    int lo, hi;
-    bl_range(w, Win, Wo, lo, hi);
-    float4 acc = make_float4(0, 0, 0, 0);
-    for (int wo = lo; wo <= hi; ++wo) {
-      float wx;
-      if (!bl_weight(wo, Wo, Win, w, wx)) continue;
-      const float4 v = *reinterpret_cast<const float4 *>(dy + (t * Wo + wo) * (long long)ldo + coff + c4 * 4);
-      acc.x += wx * v.x; acc.y += wx * v.y; acc.z += wx * v.z; acc.w += wx * v.w;
-    }
-    tmp[i] = acc;
-  }
-}
-__global__ void bilinear_bwd_h_kernel(const float4 *__restrict__ tmp, float4 *__restrict__ dx, int Hin, int Win,
-                                      int C4, int Ho, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % C4);
-    long long t = i / C4;
-    const int w = (int)(t % Win); t /= Win;
-    const int h = (int)(t % Hin);
-    const long long n = t / Hin;
-    int lo, hi;
-    bl_range(h, Hin, Ho, lo, hi);
-    float4 acc = make_float4(0, 0, 0, 0);
-    for (int ho = lo; ho <= hi; ++ho) {
-      float wy;
-      if (!bl_weight(ho, Ho, Hin, h, wy)) continue;
-      const float4 v = tmp[((n * Ho + ho) * Win + w) * C4 + c4];
-      acc.x += wy * v.x; acc.y += wy * v.y; acc.z += wy * v.z; acc.w += wy * v.w;
-    }
-    dx[i] = acc;
-  }
-}
-
-// ------------------------------------------------------------------ segmentation readouts
-// Counts behind CustomAccuracyMetric (train/metric.py:100-133) and IoUMetric (evaluate/eval_metric.py:359-384):
-// pred = argmax over the class axis (first maximum), counts[0*C + c] = #(label == c & pred == c),
-// counts[1*C + c] = #(pred == c), counts[2*C + c] = #(label == c), counts[3*C] = #(pred == label) -- integer
-// atomics (order independent).  scores: rows x ld floats, classes [0, C); label: rows floats (any value, e.g. 255).
-constexpr int kMaxSegC = 64;
-__global__ __launch_bounds__(kT) void seg_counts_kernel(const float *__restrict__ scores, const float *__restrict__ label,
-                                                       long long rows, int C, int ld,
-                                                       unsigned long long *__restrict__ counts) {
-  __shared__ unsigned int h[3 * kMaxSegC + 1];
-  for (int i = threadIdx.x; i < 3 * C + 1; i += kT) h[i] = 0;
-  __syncthreads();
-  for (long long r = blockIdx.x * (long long)kT + threadIdx.x; r < rows; r += (long long)gridDim.x * kT) {
-    const float *p = scores + r * ld;
-    int best = 0;
-    float bv = p[0];
-    for (int c = 1; c < C; ++c) {
-      const float v = p[c];
-      if (v > bv) { bv = v; best = c; }
-    }
-    const int lab = (int)label[r];
-    atomicAdd(&h[C + best], 1u);
-    if (lab >= 0 && lab < C) atomicAdd(&h[2 * C + lab], 1u);
-    if (lab == best) { atomicAdd(&h[best], 1u); atomicAdd(&h[3 * C], 1u); }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * C + 1; i += kT)
-    if (h[i]) atomicAdd(&counts[i < 3 * C ? i : 3 * C], (unsigned long long)h[i]);
-}
-
-// Segmentation read-out at full resolution (multi_eval.py:28-34, prob_upsampling): BilinearSampler of the class
-// probabilities onto an identity-affine grid of Ho x Wo followed by argmax over classes -- fused, the (C, Ho, Wo)
-// probability volume (19 x 1024 x 2048 floats per image) is never written.  Each thread produces 4 neighbouring
-// output pixels (one 4-byte store); the <= 4 x 2 source pixels they touch are L1/L2 hits for the whole 8x8 patch.
-// Arithmetic order per class follows the sampler: tl*wy*wx + tr*wy*(1-wx) + bl*(1-wy)*wx + br*(1-wy)*(1-wx),
-// corners outside the map contribute 0; ties keep the lowest class (argmax).
-// (separate, uncontracted multiplies and adds: the class map is compared bit for bit with the CPU restatement)
-__device__ __forceinline__ float src_coord_exact(int o, int O, int I) {
-#pragma clang fp contract(off)
-  const float step = 2.f / (float)(O - 1);
-  const float prod = (float)o * step;
-  const float g = O > 1 ? -1.f + prod : 0.f;
-  return (g + 1.f) * (float)(I - 1) / 2.f;
-}
-// The two source rows of output row ho and the weight of the upper one
-struct SegRows {
-  const float *r0, *r1;
-  bool vy0, vy1;
-  float wy;
-};
-__device__ __forceinline__ SegRows seg_rows(const float *__restrict__ prob, long long n, int ho, int Ho, int Hin, int Win, int ld) {
-#pragma clang fp contract(off)
-  SegRows r;
-  const float ys = src_coord_exact(ho, Ho, Hin);
-  const int y0 = (int)floorf(ys);
-  r.wy = 1.f - (ys - (float)y0);
-  r.vy0 = (unsigned)y0 < (unsigned)Hin; r.vy1 = (unsigned)(y0 + 1) < (unsigned)Hin;
-  r.r0 = prob + ((n * Hin + (r.vy0 ? y0 : 0)) * Win) * (long long)ld;
-  r.r1 = prob + ((n * Hin + (r.vy1 ? y0 + 1 : 0)) * Win) * (long long)ld;
-  return r;
-}
-// argmax over the classes of output pixel (row r, column wo): the one definition both read-outs below share
-template <bool VEC>   // VEC: ld % 4 == 0, the class vectors of the four corners are read as float4
-__device__ __forceinline__ int seg_pixel_argmax(const SegRows &r, int wo, int Wo, int Win, int C, int ld) {
-#pragma clang fp contract(off)
-  const float wy = r.wy;
-  const bool vy0 = r.vy0, vy1 = r.vy1;
-  const float xs = src_coord_exact(wo, Wo, Win);
-  const int x0 = (int)floorf(xs);
-  const float wx = 1.f - (xs - (float)x0);
-  const bool vx0 = (unsigned)x0 < (unsigned)Win, vx1 = (unsigned)(x0 + 1) < (unsigned)Win;
-  const float *tl = r.r0 + (long long)(vx0 ? x0 : 0) * ld, *tr = r.r0 + (long long)(vx1 ? x0 + 1 : 0) * ld;
-  const float *bl = r.r1 + (long long)(vx0 ? x0 : 0) * ld, *br = r.r1 + (long long)(vx1 ? x0 + 1 : 0) * ld;
-  // a corner outside the map contributes 0: its weight product is applied to a zero value
-  const float mtl = (vy0 && vx0) ? 1.f : 0.f, mtr = (vy0 && vx1) ? 1.f : 0.f;
-  const float mbl = (vy1 && vx0) ? 1.f : 0.f, mbr = (vy1 && vx1) ? 1.f : 0.f;
-  const float wx1 = 1.f - wx, wy1 = 1.f - wy;
-  float bv = -INFINITY;
-  int best = 0;
-  auto consider = [&](const int c, float a, float b, float d, float f) __attribute__((always_inline)) {
-    a = mtl != 0.f ? a : 0.f; b = mtr != 0.f ? b : 0.f; d = mbl != 0.f ? d : 0.f; f = mbr != 0.f ? f : 0.f;
-    const float v = a * wy * wx + b * wy * wx1 + d * wy1 * wx + f * wy1 * wx1;
-    if (c < C && (v > bv || c == 0)) { bv = v; best = c; }
-  };
-  if constexpr (VEC) {
-    for (int c = 0; c < C; c += 4) {
-      const float4 a = *reinterpret_cast<const float4 *>(tl + c), b = *reinterpret_cast<const float4 *>(tr + c);
-      const float4 d = *reinterpret_cast<const float4 *>(bl + c), f = *reinterpret_cast<const float4 *>(br + c);
-      consider(c, a.x, b.x, d.x, f.x);
-      consider(c + 1, a.y, b.y, d.y, f.y);
-      consider(c + 2, a.z, b.z, d.z, f.z);
-      consider(c + 3, a.w, b.w, d.w, f.w);
-    }
-  } else {
-    for (int c = 0; c < C; ++c) consider(c, tl[c], tr[c], bl[c], br[c]);
-  }
-  return best;
-}
-template <bool VEC>
-__global__ __launch_bounds__(kT) void seg_upsample_argmax_kernel(const float *__restrict__ prob, unsigned char *__restrict__ out,
-                                                                int Hin, int Win, int C, int ld, int Ho, int Wo,
-                                                                long long total) {
-  const int Wq = (Wo + 3) / 4;
-  for (long long i = blockIdx.x * (long long)kT + threadIdx.x; i < total; i += (long long)gridDim.x * kT) {
-    const int wq = (int)(i % Wq);
-    long long t = i / Wq;
-    const int ho = (int)(t % Ho);
-    const long long n = t / Ho;
-    const SegRows rows = seg_rows(prob, n, ho, Ho, Hin, Win, ld);
-    unsigned char res[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int wo = wq * 4 + e;
-      if (wo >= Wo) break;
-      res[e] = (unsigned char)seg_pixel_argmax<VEC>(rows, wo, Wo, Win, C, ld);
-    }
-    unsigned char *o = out + (n * Ho + ho) * (long long)Wo + wq * 4;
-    if (wq * 4 + 3 < Wo && (Wo & 3) == 0) {
-      *reinterpret_cast<uchar4 *>(o) = make_uchar4(res[0], res[1], res[2], res[3]);
-    } else {
-      for (int e = 0; e < 4 && wq * 4 + e < Wo; ++e) o[e] = res[e];
-    }
-  }
-}
-
-// ------------------------------------------------------------------ Cityscapes pixel-level evaluation counts
-// (data/cityscapes/Scripts/evaluation/evalPixelLevelSemanticLabeling.py evaluatePair, :583-635): one pass over the
-// pixels gives the confusion matrix and, per ground-truth instance, its size and the pixels predicted as its label /
-// as a label of its category.  Every output is an integer and is added with atomics: the order does not matter.
-// Layout of the tables: include/dspn_nn.h.
-constexpr int kCsLabels = DSPN_CITYSCAPES_LABELS;                         // labelIds 0..33
-constexpr int kCsInstLabel0 = DSPN_CITYSCAPES_INST_LABEL0;                // labels 24..33 have instances
-constexpr int kCsInstLabels = DSPN_CITYSCAPES_INST_LABELS;
-constexpr int kCsInstPerLabel = DSPN_CITYSCAPES_INST_PER_LABEL;           // inst = labelId * 1000 + k
-constexpr int kCsInstPerImage = kCsInstLabels * kCsInstPerLabel;
-constexpr int kCsMaxImages = 0x7fffffff / kCsInstPerImage;                // instance keys are ints
-
-struct CsShared {
-  unsigned int conf[kCsLabels * kCsLabels];
-  unsigned int errors;
-  unsigned char category[256], label_of[256];
-};
-__device__ __forceinline__ void cs_shared_init(CsShared &s, const unsigned char *__restrict__ category,
-                                               const unsigned char *__restrict__ label_of) {
-  for (int i = threadIdx.x; i < kCsLabels * kCsLabels; i += kT) s.conf[i] = 0;
-  if (threadIdx.x == 0) s.errors = 0;
-  for (int i = threadIdx.x; i < 256; i += kT) { s.category[i] = category[i]; s.label_of[i] = label_of ? label_of[i] : 0; }
-  __syncthreads();
-}
-__device__ __forceinline__ void cs_shared_flush(CsShared &s, unsigned long long *__restrict__ conf,
-                                                unsigned long long *__restrict__ errors) {
-  __syncthreads();
-  for (int i = threadIdx.x; i < kCsLabels * kCsLabels; i += kT)
-    if (s.conf[i]) atomicAdd(&conf[i], (unsigned long long)s.conf[i]);
-  if (threadIdx.x == 0 && s.errors) atomicAdd(errors, (unsigned long long)s.errors);
-}
-// The four pixels of a thread (cnt of them inside the image; image n) -> the tables.  Called by WHOLE waves (lanes without
-// pixels pass cnt = 0).  Most of a wave's 256 neighbouring pixels share one confusion cell and one or two instances, so equal
-// keys are first added up across the wave (a ballot per pixel slot and distinct key) and ONE lane issues the atomic.
-__device__ __forceinline__ void cs_accumulate(CsShared &s, unsigned int *__restrict__ inst, long long n, int cnt,
-                                              const unsigned char (&pred)[4], const unsigned char (&gt)[4], const int (&id)[4]) {
-  const int lane = threadIdx.x & 63;
-  int ck[4], ik[4];                 // confusion cell / instance entry of each pixel, -1: none
-  unsigned long long tp[4], ct[4];  // lanes whose pixel e is predicted as the instance's label / category
-  int nerr = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const bool have = e < cnt;
-    const int g = gt[e], p = pred[e];
-    bool bad = g >= kCsLabels || p >= kCsLabels;
-    ck[e] = have && !bad ? g * kCsLabels + p : -1;
-    ik[e] = -1;
-    bool is_tp = false, is_ct = false;
-    if (have && id[e] > 1000) {     // a value < 1000 is a bare labelId (no instance), 1000 itself is none either (:601)
-      const int lab = id[e] / 1000, k = id[e] - lab * 1000;
-      if (lab >= kCsInstLabel0 && lab < kCsInstLabel0 + kCsInstLabels) {
-        ik[e] = (int)n * kCsInstPerImage + (lab - kCsInstLabel0) * kCsInstPerLabel + k;
-        const unsigned char c = s.category[lab];
-        is_tp = p == lab;
-        is_ct = c != 0 && s.category[p] == c;
-      } else {
-        bad = true;
-      }
-    }
-    nerr += have && bad;
-    tp[e] = __ballot(is_tp);
-    ct[e] = __ballot(is_ct);
-  }
-  if (nerr) atomicAdd(&s.errors, (unsigned)nerr);
-  auto pick = [](const int (&v)[4], int e) { return e == 0 ? v[0] : e == 1 ? v[1] : e == 2 ? v[2] : v[3]; };
-  unsigned long long todo[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) todo[e] = __ballot(ck[e] >= 0);
-  while (todo[0] | todo[1] | todo[2] | todo[3]) {
-    const int le = todo[0] ? 0 : todo[1] ? 1 : todo[2] ? 2 : 3;
-    const int leader = __ffsll((long long)(le == 0 ? todo[0] : le == 1 ? todo[1] : le == 2 ? todo[2] : todo[3])) - 1;
-    const int key = __shfl(pick(ck, le), leader, 64);
-    unsigned total = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const unsigned long long m = __ballot(ck[e] == key);
-      total += (unsigned)__popcll(m);
-      todo[e] &= ~m;
-    }
-    if (lane == leader) atomicAdd(&s.conf[key], total);
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) todo[e] = __ballot(ik[e] >= 0);
-  while (todo[0] | todo[1] | todo[2] | todo[3]) {
-    const int le = todo[0] ? 0 : todo[1] ? 1 : todo[2] ? 2 : 3;
-    const int leader = __ffsll((long long)(le == 0 ? todo[0] : le == 1 ? todo[1] : le == 2 ? todo[2] : todo[3])) - 1;
-    const int key = __shfl(pick(ik, le), leader, 64);
-    unsigned size = 0, ntp = 0, nct = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const unsigned long long m = __ballot(ik[e] == key);
-      size += (unsigned)__popcll(m);
-      ntp += (unsigned)__popcll(m & tp[e]);
-      nct += (unsigned)__popcll(m & ct[e]);
-      todo[e] &= ~m;
-    }
-    if (lane == leader) {
-      unsigned int *o = inst + (size_t)key * 3;
-      atomicAdd(o, size);
-      if (ntp) atomicAdd(o + 1, ntp);
-      if (nct) atomicAdd(o + 2, nct);
-    }
-  }
-}
-// ground truth of the four pixels of a thread: one uchar4 and one int4 where the rows allow it
-__device__ __forceinline__ void cs_load_gt(const unsigned char *__restrict__ gt_label, const int *__restrict__ gt_inst,
-                                           long long at, int cnt, bool vec, unsigned char (&gt)[4], int (&id)[4]) {
-  if (vec) {
-    const uchar4 g = *reinterpret_cast<const uchar4 *>(gt_label + at);
-    const int4 v = *reinterpret_cast<const int4 *>(gt_inst + at);
-    gt[0] = g.x; gt[1] = g.y; gt[2] = g.z; gt[3] = g.w;
-    id[0] = v.x; id[1] = v.y; id[2] = v.z; id[3] = v.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gt[e] = e < cnt ? gt_label[at + e] : 0; id[e] = e < cnt ? gt_inst[at + e] : 0; }
-  }
-}
-// vec: W % 4 == 0 and the three maps are aligned for 4-pixel accesses.  The loop runs per WAVE (the ballots need every lane).
-__global__ __launch_bounds__(kT) void cityscapes_counts_kernel(const unsigned char *__restrict__ pred_map,
-                                                              const unsigned char *__restrict__ gt_label, const int *__restrict__ gt_inst,
-                                                              int H, int W, long long total, bool vec,
-                                                              const unsigned char *__restrict__ category,
-                                                              unsigned long long *__restrict__ conf, unsigned int *__restrict__ inst,
-                                                              unsigned long long *__restrict__ errors) {
-  __shared__ CsShared s;
-  cs_shared_init(s, category, nullptr);
-  const int Wq = (W + 3) / 4, lane = threadIdx.x & 63;
-  for (long long base = blockIdx.x * (long long)kT + (threadIdx.x - lane); base < total; base += (long long)gridDim.x * kT) {
-    const long long i = base + lane;
-    unsigned char pred[4] = {0, 0, 0, 0}, gt[4] = {0, 0, 0, 0};
-    int id[4] = {0, 0, 0, 0}, cnt = 0;
-    long long n = 0;
-    if (i < total) {
-      const int wq = (int)(i % Wq);
-      long long t = i / Wq;
-      const int h = (int)(t % H);
-      n = t / H;
-      cnt = min(4, W - wq * 4);
-      const long long at = (n * H + h) * (long long)W + wq * 4;
-      cs_load_gt(gt_label, gt_inst, at, cnt, vec, gt, id);
-      if (vec) {
-        const uchar4 p = *reinterpret_cast<const uchar4 *>(pred_map + at);
-        pred[0] = p.x; pred[1] = p.y; pred[2] = p.z; pred[3] = p.w;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pred[e] = e < cnt ? pred_map[at + e] : 0;
-      }
-    }
-    cs_accumulate(s, inst, n, cnt, pred, gt, id);
-  }
-  cs_shared_flush(s, conf, errors);
-}
-// The same counts straight from the class probabilities: the prediction of a pixel is seg_upsample_argmax_kernel's class
-// (seg_pixel_argmax) sent through the trainId -> labelId table; the class map is never written.
-template <bool VEC>
-__global__ __launch_bounds__(kT) void cityscapes_counts_prob_kernel(const float *__restrict__ prob, int Hin, int Win, int C, int ld,
-                                                                   const unsigned char *__restrict__ label_of,
-                                                                   const unsigned char *__restrict__ gt_label, const int *__restrict__ gt_inst,
-                                                                   int Ho, int Wo, long long total, bool vec,
-                                                                   const unsigned char *__restrict__ category,
-                                                                   unsigned long long *__restrict__ conf, unsigned int *__restrict__ inst,
-                                                                   unsigned long long *__restrict__ errors) {
-  __shared__ CsShared s;
-  cs_shared_init(s, category, label_of);
-  const int Wq = (Wo + 3) / 4, lane = threadIdx.x & 63;
-  for (long long base = blockIdx.x * (long long)kT + (threadIdx.x - lane); base < total; base += (long long)gridDim.x * kT) {
-    const long long i = base + lane;
-    unsigned char pred[4] = {0, 0, 0, 0}, gt[4] = {0, 0, 0, 0};
-    int id[4] = {0, 0, 0, 0}, cnt = 0;
-    long long n = 0;
-    if (i < total) {
-      const int wq = (int)(i % Wq);
-      long long t = i / Wq;
-      const int ho = (int)(t % Ho);
-      n = t / Ho;
-      cnt = min(4, Wo - wq * 4);
-      cs_load_gt(gt_label, gt_inst, (n * Ho + ho) * (long long)Wo + wq * 4, cnt, vec, gt, id);
-      const SegRows rows = seg_rows(prob, n, ho, Ho, Hin, Win, ld);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < cnt) pred[e] = s.label_of[seg_pixel_argmax<VEC>(rows, wq * 4 + e, Wo, Win, C, ld)];
-    }
-    cs_accumulate(s, inst, n, cnt, pred, gt, id);
-  }
-  cs_shared_flush(s, conf, errors);
-}
-
-#endif   // !DSPN_HALF
-
 // ------------------------------------------------------------------ losses
 // logits and their gradient are activations (storage type); the probabilities are a float output
 constexpr int kMaxSoftmaxC = 64;
@@ -1811,144 +1304,10 @@ __global__ void softmax_output_kernel(const CA1Ptr logits, const float *__restri
     }
   }
 }
-#ifndef DSPN_HALF
-__global__ void count_kernel(const float *__restrict__ a, long long n, int mode, float ref, float *out) {
-  float c = 0.f;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x)
-    c += (mode == 0 ? (a[i] != ref) : (a[i] > ref)) ? 1.f : 0.f;
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-  // integer-valued float adds below 2^24 are exact, hence order independent
-  if ((threadIdx.x & 63) == 0 && c != 0.f) atomicAdd(out, c);
-}
-__device__ __forceinline__ float smooth_l1(float x) {
-  const float ax = fabsf(x);
-  return ax < 1.f ? 0.5f * x * x : ax - 0.5f;
-}
-__global__ void smooth_l1_fwd_kernel(const float *pred, const float *target, const float *mask,
-                                     float *loss, long long n) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x)
-    loss[i] = smooth_l1(mask[i] * (pred[i] - target[i]));
-}
-__global__ void smooth_l1_bwd_kernel(const float *pred, const float *target, const float *mask,
-                                     float *grad, long long n, float grad_scale, const float *valid_count) {
-  const float sc = grad_scale / fmaxf(1.f, *valid_count);
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const float m = mask[i];
-    const float x = m * (pred[i] - target[i]);
-    const float d = fabsf(x) < 1.f ? x : (x > 0.f ? 1.f : -1.f);
-    grad[i] = sc * m * d;
-  }
-}
-// single-block deterministic reductions for the (tiny) metric readouts
-__global__ __launch_bounds__(1024) void ce_sum_kernel(const float *prob, const float *label, long long rows,
-                                                      int C, int ld, float ignore_label, float eps,
-                                                      float *out2) {
-  __shared__ double s_a[1024];
-  __shared__ double s_b[1024];
-  double a = 0, b = 0;
-  for (long long r = threadIdx.x; r < rows; r += 1024) {
-    const float lab = label[r];
-    if (lab == ignore_label) continue;
-    const int li = (int)lab;
-    if (li < 0 || li >= C) continue;
-    a += -log((double)(prob[r * ld + li] + eps));
-    b += 1.0;
-  }
-  s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 512; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) { s_a[threadIdx.x] += s_a[threadIdx.x + s]; s_b[threadIdx.x] += s_b[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out2[0] = (float)s_a[0]; out2[1] = (float)s_b[0]; }
-}
-__global__ __launch_bounds__(1024) void sum_kernel(const float *a, long long n, float *out) {
-  __shared__ double s_a[1024];
-  double v = 0;
-  for (long long i = threadIdx.x; i < n; i += 1024) v += a[i];
-  s_a[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 512; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) s_a[threadIdx.x] += s_a[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)s_a[0];
-}
-
-__global__ void sgd_kernel(float4 *__restrict__ w, const float4 *__restrict__ g, float4 *__restrict__ m,
-                           long long n4, float lr, float mu, float wd, float rescale) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
-       i += (long long)gridDim.x * blockDim.x) {
-    float4 wv = w[i]; const float4 gv = g[i]; float4 mv = m[i];
-    mv.x = mu * mv.x - lr * (rescale * gv.x + wd * wv.x); wv.x += mv.x;
-    mv.y = mu * mv.y - lr * (rescale * gv.y + wd * wv.y); wv.y += mv.y;
-    mv.z = mu * mv.z - lr * (rescale * gv.z + wd * wv.z); wv.z += mv.z;
-    mv.w = mu * mv.w - lr * (rescale * gv.w + wd * wv.w); wv.w += mv.w;
-    w[i] = wv; m[i] = mv;
-  }
-}
-
-// Segmented SGD (dspn_sgd_momentum_segments_f32): the rows of `seg` cover disjoint, sorted float4 ranges of the arena; the
-// launch walks the CONCATENATION of those ranges (total4 float4 in all).  Every block first forms the inclusive prefix of the
-// row lengths in LDS (one scan of nseg values), then each thread finds the row of its first float4 by binary search and
-// follows the rows forward.  Elements outside every row are never touched.  Per element the arithmetic is sgd_kernel's with
-// lr * lr_mult and wd * wd_mult formed in float32 (multipliers 1.0 give sgd_kernel's bits).
-constexpr int kSgdPer = 8;                // float4 per thread: one block covers kT * kSgdPer consecutive float4 of the rows
-__global__ void __launch_bounds__(kT) sgd_segments_kernel(float4 *__restrict__ w, const float4 *__restrict__ g,
-                                                          float4 *__restrict__ m, const dspn_sgd_segment *__restrict__ seg,
-                                                          int nseg, long long total4, float lr, float mu, float wd,
-                                                          float rescale) {
-  extern __shared__ long long s_end[];    // s_end[r] = float4 in rows 0 .. r (inclusive prefix)
-  __shared__ long long s_part[kT];
-  const int t = threadIdx.x;
-  const int per = (nseg + kT - 1) / kT;   // rows per thread in the scan
-  long long acc = 0;
-  for (int r = t * per; r < nseg && r < (t + 1) * per; ++r) { acc += seg[r].length >> 2; s_end[r] = acc; }
-  s_part[t] = acc;
-  __syncthreads();
-  for (int d = 1; d < kT; d <<= 1) {     // inclusive scan of the per-thread sums (Hillis-Steele)
-    const long long v = t >= d ? s_part[t - d] : 0;
-    __syncthreads();
-    s_part[t] += v;
-    __syncthreads();
-  }
-  const long long before = t > 0 ? s_part[t - 1] : 0;
-  for (int r = t * per; r < nseg && r < (t + 1) * per; ++r) s_end[r] += before;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * (kT * kSgdPer);
-  long long j = base + t;
-  if (j >= total4) return;
-  int lo = 0, hi = nseg - 1;              // the first row whose end lies beyond j
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (s_end[mid] > j) hi = mid; else lo = mid + 1;
-  }
-  int r = lo;
-  for (int it = 0; it < kSgdPer && j < total4; ++it, j += kT) {
-    while (r < nseg && s_end[r] <= j) ++r;
-    if (r == nseg) return;                // (total4 larger than the rows hold: the rest is not ours to touch)
-    const dspn_sgd_segment sr = seg[r];
-    const float lre = lr * sr.lr_mult, wde = wd * sr.wd_mult;
-    const long long i = (sr.offset >> 2) + (j - (s_end[r] - (sr.length >> 2)));
-    float4 wv = w[i]; const float4 gv = g[i]; float4 mv = m[i];
-    mv.x = mu * mv.x - lre * (rescale * gv.x + wde * wv.x); wv.x += mv.x;
-    mv.y = mu * mv.y - lre * (rescale * gv.y + wde * wv.y); wv.y += mv.y;
-    mv.z = mu * mv.z - lre * (rescale * gv.z + wde * wv.z); wv.z += mv.z;
-    mv.w = mu * mv.w - lre * (rescale * gv.w + wde * wv.w); wv.w += mv.w;
-    w[i] = wv; m[i] = mv;
-  }
-}
-
-#endif   // !DSPN_HALF
 
 int bn_slabs(long long rows) { const int sr = slab_rows_for(rows); return (int)((rows + sr - 1) / sr); }
 
 }  // namespace
-
-#define S_(x) ((hipStream_t)(x))
 
 // ------------------------------------------------------------------ BatchNorm host side: one owner per launch
 static size_t bn_workspace_bytes(long long rows, int C) {
@@ -2090,8 +1449,6 @@ int DSPN_FN(dspn_bn_stats_ex)(const st_t *x, long long rows, int C, float eps, c
 
 #ifndef DSPN_HALF
 size_t dspn_bn_tiles_workspace_bytes(int tiles, int C) { return bn_tiles_workspace_bytes(tiles, C); }
-#endif
-#ifndef DSPN_HALF
 static int bn_stats_from_tiles_run(const float *tile_stats, int tiles, int tile_rows, long long rows, int C, float eps,
                                    const float *gamma, const float *beta, float *mean, float *rstd, float *scale,
                                    float *shift, const float *tile_minmax, int relu, float *out_absmax, float *out_absmin,
@@ -2226,11 +1583,7 @@ int dspn_bn_backward_maxpool_f32(const float *x, const float *scale, const float
   return dspn_bn_backward_maxpool_ex_f32(x, scale, shift, dy_pool, argmax, N, H, W, C, k, stride, pad, Ho, Wo, mean, rstd, gamma, dx,
                                          dgamma, dbeta, relu, dx_absmax, workspace, workspace_bytes, stream, 0);
 }
-#endif
 
-// BatchNorm backward whose two reductions (sum dy', sum dy' xhat) were gathered per row tile by the data-gradient
-// kernel that produced dy (bn_sums of dspn_conv2d_dgrad_bn_f32): finalize + apply only
-#ifndef DSPN_HALF
 int dspn_bn_apply_planes_f32(const float *x, const float *scale, const float *shift, void *y_planes, long long rows, int C,
                              int relu, const float *y_absmax, void *stream) {
   DSPN_REQUIRE(x && scale && shift && y_planes && y_absmax, "bn_apply_planes: null pointer (y_absmax is the block the planes are cut by)");
@@ -2246,6 +1599,8 @@ int dspn_bn_apply_planes_f32(const float *x, const float *scale, const float *sh
 }
 #endif
 
+// BatchNorm backward whose two reductions (sum dy', sum dy' xhat) were gathered per row tile by the data-gradient
+// kernel that produced dy (bn_sums of dspn_conv2d_dgrad_bn_f32): finalize + apply only
 int DSPN_FN(dspn_bn_backward_from_sums)(const st_t *x, const float *scale, const float *shift, const st_t *dy,
                                    const float *mean, const float *rstd, const float *gamma, const float *tile_sums,
                                    int tiles, st_t *dx, float *dgamma, float *dbeta, long long rows, int C, int relu,
@@ -2347,15 +1702,6 @@ int DSPN_FN(dspn_relu_backward_colsum)(const st_t *y, const st_t *dy, st_t *dx, 
 }
 
 #ifndef DSPN_HALF
-int dspn_fill_f32(float *p, float v, long long n, void *stream) {
-  DSPN_REQUIRE(p && n >= 0, "fill: bad argument");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(kT), 0, S_(stream), p, v, n);
-  return dspn::check_launch("fill");
-}
-#endif
-
-#ifndef DSPN_HALF
 size_t dspn_colsum_workspace_bytes(long long rows, int C) {
   if (rows <= 0 || C <= 0) return 0;
   const int sr = colsum_slab_rows(rows);
@@ -2381,14 +1727,6 @@ int DSPN_FN(dspn_nchw_to_nhwc)(const float *src, st_t *dst, int N, int C, int H,
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for(total)), dim3(kT), 0, S_(stream), src, A1Ptr(dst), C, HW, total, Cp);
   return dspn::check_launch("nchw_to_nhwc");
 }
-#ifndef DSPN_HALF
-int dspn_nhwc_to_nchw_f32(const float *src, float *dst, int N, int C, int H, int W, int Cp, void *stream) {
-  DSPN_REQUIRE(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && Cp >= C, "nhwc_to_nchw: bad argument");
-  const long long HW = (long long)H * W, total = HW * N * C;
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for(total)), dim3(kT), 0, S_(stream), src, dst, C, HW, total, Cp);
-  return dspn::check_launch("nhwc_to_nchw");
-}
-#endif
 
 int DSPN_FN(dspn_copy_block)(const st_t *src, st_t *dst, int samples, long long rows_per_sample, int C,
                         long long src_sample_stride, int lds, int soff, long long dst_sample_stride,
@@ -2409,14 +1747,6 @@ int DSPN_FN(dspn_copy_block)(const st_t *src, st_t *dst, int samples, long long 
                      total, accumulate);
   return dspn::check_launch("copy_block");
 }
-#ifndef DSPN_HALF
-int dspn_copy_block_batch_f32(const void *table, int n, long long total, void *stream) {
-  DSPN_REQUIRE(table && n > 0 && total > 0, "copy_block_batch: bad argument");
-  hipLaunchKernelGGL(copy_block_batch_kernel, dim3(grid_for(total)), dim3(kT), 0, S_(stream),
-                     static_cast<const CopyDesc *>(table), n, total);
-  return dspn::check_launch("copy_block_batch");
-}
-#endif
 #ifdef DSPN_HALF
 /* the same strided block copy between storage types: bf16 -> float (SSD head maps into the float loss inputs) and
  * float -> bf16 (their gradients back into the per-map gradient tensors) */
@@ -2439,15 +1769,6 @@ int dspn_copy_block_f32_bf16(const float *src, st_t *dst, int samples, long long
                      A1Ptr(dst), rows_per_sample, C, src_sample_stride, lds, soff, dst_sample_stride, ldd, doff, total,
                      accumulate);
   return dspn::check_launch("copy_block");
-}
-#endif
-
-#ifndef DSPN_HALF
-int dspn_transpose_bnc_f32(const float *src, float *dst, int B, int N, int C, void *stream) {
-  DSPN_REQUIRE(src && dst && B > 0 && N > 0 && C > 0, "transpose_bnc: bad argument");
-  const long long total = (long long)B * N * C;
-  hipLaunchKernelGGL(transpose_bnc_kernel, dim3(grid_for(total)), dim3(kT), 0, S_(stream), src, dst, N, C, total);
-  return dspn::check_launch("transpose_bnc");
 }
 #endif
 
@@ -2562,133 +1883,6 @@ int DSPN_FN(dspn_avgpool2d_backward)(const st_t *dy, st_t *dx, int N, int H, int
   return dspn::check_launch("avgpool2d_backward");
 }
 
-#ifndef DSPN_HALF
-int dspn_bilinear_forward_f32(const float *x, float *y, int N, int Hin, int Win, int C, int Ho, int Wo,
-                              int ldo, int coff, void *stream) {
-  DSPN_REQUIRE(x && y && C % 4 == 0 && ldo % 4 == 0 && coff % 4 == 0 && coff + C <= ldo, "bilinear_forward: bad argument");
-  const long long total = (long long)N * Ho * Wo * (C / 4);
-  hipLaunchKernelGGL(bilinear_fwd_kernel<false>, dim3(grid_for(total)), dim3(kT), 0, S_(stream),
-                     reinterpret_cast<const float4 *>(x), y, Hin, Win, C / 4, Ho, Wo, ldo, coff, total);
-  return dspn::check_launch("bilinear_forward");
-}
-#endif
-#ifndef DSPN_HALF
-int dspn_bilinear_forward_acc_f32(const float *x, float *y, int N, int Hin, int Win, int C, int Ho, int Wo,
-                                  int ldo, int coff, void *stream) {
-  DSPN_REQUIRE(x && y && C % 4 == 0 && ldo % 4 == 0 && coff % 4 == 0 && coff + C <= ldo, "bilinear_forward_acc: bad argument");
-  const long long total = (long long)N * Ho * Wo * (C / 4);
-  hipLaunchKernelGGL(bilinear_fwd_kernel<true>, dim3(grid_for(total)), dim3(kT), 0, S_(stream),
-                     reinterpret_cast<const float4 *>(x), y, Hin, Win, C / 4, Ho, Wo, ldo, coff, total);
-  return dspn::check_launch("bilinear_forward_acc");
-}
-#endif
-#ifndef DSPN_HALF
-int dspn_bilinear_backward_f32(const float *dy, float *dx, int N, int Hin, int Win, int C, int Ho, int Wo,
-                               int ldo, int coff, void *stream) {
-  DSPN_REQUIRE(dy && dx && C % 4 == 0 && ldo % 4 == 0 && coff % 4 == 0 && coff + C <= ldo, "bilinear_backward: bad argument");
-  const long long total = (long long)N * Hin * Win * (C / 4);
-  hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(grid_for(total)), dim3(kT), 0, S_(stream), dy,
-                     reinterpret_cast<float4 *>(dx), Hin, Win, C / 4, Ho, Wo, ldo, coff, total);
-  return dspn::check_launch("bilinear_backward");
-}
-#endif
-
-#ifndef DSPN_HALF
-size_t dspn_bilinear_backward_workspace_bytes(int N, int Win, int C, int Ho) {
-  if (N <= 0 || Win <= 0 || C <= 0 || Ho <= 0) return 0;
-  return sizeof(float) * (size_t)N * Ho * Win * C;
-}
-#endif
-#ifndef DSPN_HALF
-/* separable two-pass backward (needs dspn_bilinear_backward_workspace_bytes of scratch) */
-int dspn_bilinear_backward_ws_f32(const float *dy, float *dx, int N, int Hin, int Win, int C, int Ho, int Wo,
-                                  int ldo, int coff, void *workspace, size_t workspace_bytes, void *stream) {
-  DSPN_REQUIRE(dy && dx && workspace && C % 4 == 0 && ldo % 4 == 0 && coff % 4 == 0 && coff + C <= ldo,
-               "bilinear_backward: bad argument");
-  if (workspace_bytes < dspn_bilinear_backward_workspace_bytes(N, Win, C, Ho))
-    return dspn::fail(DSPN_ERR_WORKSPACE_, "bilinear_backward: workspace too small");
-  const long long t1 = (long long)N * Ho * Win * (C / 4), t2 = (long long)N * Hin * Win * (C / 4);
-  hipLaunchKernelGGL(bilinear_bwd_w_kernel, dim3(grid_for(t1, kT, 65535)), dim3(kT), 0, S_(stream), dy,
-                     static_cast<float4 *>(workspace), Win, C / 4, Ho, Wo, ldo, coff, t1);
-  hipLaunchKernelGGL(bilinear_bwd_h_kernel, dim3(grid_for(t2, kT, 65535)), dim3(kT), 0, S_(stream),
-                     static_cast<const float4 *>(workspace), reinterpret_cast<float4 *>(dx), Hin, Win, C / 4, Ho, t2);
-  return dspn::check_launch("bilinear_backward_ws");
-}
-#endif
-
-#ifndef DSPN_HALF
-int dspn_seg_counts_f32(const float *scores, const float *label, long long rows, int C, int ld,
-                        unsigned long long *counts, void *stream) {
-  DSPN_REQUIRE(scores && label && counts && rows > 0 && C > 0 && C <= kMaxSegC && ld >= C, "seg_counts: bad argument (C <= 64)");
-  (void)hipMemsetAsync(counts, 0, sizeof(unsigned long long) * (3 * C + 1), S_(stream));
-  hipLaunchKernelGGL(seg_counts_kernel, dim3(grid_for(rows, kT, 2048)), dim3(kT), 0, S_(stream), scores, label, rows, C, ld,
-                     counts);
-  return dspn::check_launch("seg_counts");
-}
-#endif
-
-#ifndef DSPN_HALF
-int dspn_seg_upsample_argmax_f32(const float *prob, unsigned char *out, int N, int Hin, int Win, int C, int ld,
-                                 int Ho, int Wo, void *stream) {
-  DSPN_REQUIRE(prob && out && N > 0 && Hin > 0 && Win > 0 && Ho > 0 && Wo > 0 && C > 0 && C <= 256 && ld >= C,
-               "seg_upsample_argmax: bad argument (0 < C <= 256, ld >= C)");
-  const long long total = (long long)N * Ho * ((Wo + 3) / 4);
-  // float4 reads of the class vectors need 16-byte aligned rows that hold the rounded-up channel count
-  const bool vec = ld % 4 == 0 && (C + 3) / 4 * 4 <= ld && reinterpret_cast<uintptr_t>(prob) % 16 == 0;
-  if (vec)
-    hipLaunchKernelGGL(seg_upsample_argmax_kernel<true>, dim3(grid_for(total, kT, 65535)), dim3(kT), 0, S_(stream), prob, out,
-                       Hin, Win, C, ld, Ho, Wo, total);
-  else
-    hipLaunchKernelGGL(seg_upsample_argmax_kernel<false>, dim3(grid_for(total, kT, 65535)), dim3(kT), 0, S_(stream), prob, out,
-                       Hin, Win, C, ld, Ho, Wo, total);
-  return dspn::check_launch("seg_upsample_argmax");
-}
-
-// 4-pixel accesses of the ground-truth maps: whole groups of four per row, bases aligned for a uchar4 / an int4
-static bool cs_vec_ok(int W, const void *bytes_a, const void *bytes_b, const int *gt_inst) {
-  return W % 4 == 0 && reinterpret_cast<uintptr_t>(bytes_a) % 4 == 0 && reinterpret_cast<uintptr_t>(bytes_b) % 4 == 0 &&
-         reinterpret_cast<uintptr_t>(gt_inst) % 16 == 0;
-}
-// Workgroups of the Cityscapes count kernels: every one of them ends with an atomic per non-empty cell of its confusion
-// matrix, so the grid is a few workgroups per compute unit that walk the image, not one per 1024 pixels.
-constexpr int kCsGridCap = 2048;
-
-int dspn_cityscapes_counts_u8(const unsigned char *pred, const unsigned char *gt_label, const int *gt_inst, int N, int H,
-                              int W, const unsigned char *category, unsigned long long *conf, unsigned int *inst,
-                              unsigned long long *errors, void *stream) {
-  DSPN_REQUIRE(pred && gt_label && gt_inst && category && conf && inst && errors, "cityscapes_counts: null pointer");
-  DSPN_REQUIRE(N > 0 && N <= kCsMaxImages && H > 0 && W > 0 && (long long)H * W < (1ll << 32) && (long long)N * H * W <= (1ll << 40),
-               "cityscapes_counts: bad argument (0 < N <= %d, 0 < H * W < 2^32, N * H * W <= 2^40)", kCsMaxImages);
-  const long long total = (long long)N * H * ((W + 3) / 4);
-  hipLaunchKernelGGL(cityscapes_counts_kernel, dim3(grid_for(total, kT, kCsGridCap)), dim3(kT), 0, S_(stream), pred, gt_label,
-                     gt_inst, H, W, total, cs_vec_ok(W, pred, gt_label, gt_inst), category, conf, inst, errors);
-  return dspn::check_launch("cityscapes_counts");
-}
-
-int dspn_cityscapes_counts_prob_f32(const float *prob, int N, int Hin, int Win, int C, int ld,
-                                    const unsigned char *label_of_train_id, const unsigned char *gt_label,
-                                    const int *gt_inst, int Ho, int Wo, const unsigned char *category,
-                                    unsigned long long *conf, unsigned int *inst, unsigned long long *errors, void *stream) {
-  DSPN_REQUIRE(prob && label_of_train_id && gt_label && gt_inst && category && conf && inst && errors,
-               "cityscapes_counts_prob: null pointer");
-  DSPN_REQUIRE(N > 0 && N <= kCsMaxImages && Hin > 0 && Win > 0 && Ho > 0 && Wo > 0 && (long long)Ho * Wo < (1ll << 32) &&
-               (long long)N * Ho * Wo <= (1ll << 40) && C > 0 && C <= 256 && ld >= C,
-               "cityscapes_counts_prob: bad argument (0 < N <= %d, 0 < Ho * Wo < 2^32, N * Ho * Wo <= 2^40, 0 < C <= 256, ld >= C)",
-               kCsMaxImages);
-  const long long total = (long long)N * Ho * ((Wo + 3) / 4);
-  const bool vec = cs_vec_ok(Wo, gt_label, gt_label, gt_inst);
-  // float4 reads of the class vectors: as in dspn_seg_upsample_argmax_f32
-  const bool vec_prob = ld % 4 == 0 && (C + 3) / 4 * 4 <= ld && reinterpret_cast<uintptr_t>(prob) % 16 == 0;
-  if (vec_prob)
-    hipLaunchKernelGGL(cityscapes_counts_prob_kernel<true>, dim3(grid_for(total, kT, kCsGridCap)), dim3(kT), 0, S_(stream), prob,
-                       Hin, Win, C, ld, label_of_train_id, gt_label, gt_inst, Ho, Wo, total, vec, category, conf, inst, errors);
-  else
-    hipLaunchKernelGGL(cityscapes_counts_prob_kernel<false>, dim3(grid_for(total, kT, kCsGridCap)), dim3(kT), 0, S_(stream), prob,
-                       Hin, Win, C, ld, label_of_train_id, gt_label, gt_inst, Ho, Wo, total, vec, category, conf, inst, errors);
-  return dspn::check_launch("cityscapes_counts_prob");
-}
-#endif
-
 int DSPN_FN(dspn_softmax_output)(const st_t *logits, const float *label, float *prob, st_t *grad,
                             long long rows, int C, int ld, float ignore_label, float grad_scale,
                             const float *valid_count, void *stream) {
@@ -2700,70 +1894,5 @@ int DSPN_FN(dspn_softmax_output)(const st_t *logits, const float *label, float *
                      prob, A1Ptr(grad), rows, C, ld, ignore_label, grad_scale, valid_count);
   return dspn::check_launch("softmax_output");
 }
-#ifndef DSPN_HALF
-int dspn_count_f32(const float *a, long long n, int mode, float ref, float *out, void *stream) {
-  DSPN_REQUIRE(a && out && n > 0 && n < (1ll << 24), "count: n must be in (0, 2^24)");
-  hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, S_(stream), out, 0.f, 1ll);
-  hipLaunchKernelGGL(count_kernel, dim3(grid_for(n, kT, 1024)), dim3(kT), 0, S_(stream), a, n, mode, ref, out);
-  return dspn::check_launch("count");
-}
-#endif
-#ifndef DSPN_HALF
-int dspn_smooth_l1_forward_f32(const float *pred, const float *target, const float *mask, float *loss,
-                               long long n, void *stream) {
-  DSPN_REQUIRE(pred && target && mask && loss && n > 0, "smooth_l1_forward: bad argument");
-  hipLaunchKernelGGL(smooth_l1_fwd_kernel, dim3(grid_for(n)), dim3(kT), 0, S_(stream), pred, target, mask, loss, n);
-  return dspn::check_launch("smooth_l1_forward");
-}
-#endif
-#ifndef DSPN_HALF
-int dspn_smooth_l1_backward_f32(const float *pred, const float *target, const float *mask, float *grad,
-                                long long n, float grad_scale, const float *valid_count, void *stream) {
-  DSPN_REQUIRE(pred && target && mask && grad && valid_count && n > 0, "smooth_l1_backward: bad argument");
-  hipLaunchKernelGGL(smooth_l1_bwd_kernel, dim3(grid_for(n)), dim3(kT), 0, S_(stream), pred, target, mask, grad,
-                     n, grad_scale, valid_count);
-  return dspn::check_launch("smooth_l1_backward");
-}
-#endif
-#ifndef DSPN_HALF
-int dspn_cross_entropy_sum_f32(const float *prob, const float *label, long long rows, int C, int ld,
-                               float ignore_label, float eps, float *out2, void *stream) {
-  DSPN_REQUIRE(prob && label && out2 && rows > 0 && C > 0 && ld >= C, "cross_entropy_sum: bad argument");
-  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(1024), 0, S_(stream), prob, label, rows, C, ld, ignore_label, eps, out2);
-  return dspn::check_launch("cross_entropy_sum");
-}
-#endif
-#ifndef DSPN_HALF
-int dspn_sum_f32(const float *a, long long n, float *out, void *stream) {
-  DSPN_REQUIRE(a && out && n > 0, "sum: bad argument");
-  hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, S_(stream), a, n, out);
-  return dspn::check_launch("sum");
-}
-#endif
-
-#ifndef DSPN_HALF
-int dspn_sgd_momentum_f32(float *w, const float *grad, float *mom, long long n, float lr, float momentum,
-                          float wd, float rescale, void *stream) {
-  DSPN_REQUIRE(w && grad && mom && n > 0 && n % 4 == 0, "sgd_momentum: n must be a positive multiple of 4");
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4)), dim3(kT), 0, S_(stream), reinterpret_cast<float4 *>(w),
-                     reinterpret_cast<const float4 *>(grad), reinterpret_cast<float4 *>(mom), n / 4, lr,
-                     momentum, wd, rescale);
-  return dspn::check_launch("sgd_momentum");
-}
-#endif
-
-#ifndef DSPN_HALF
-int dspn_sgd_momentum_segments_f32(float *w, const float *grad, float *mom, const dspn_sgd_segment *segments, int nseg,
-                                   long long total4, float lr, float momentum, float wd, float rescale, void *stream) {
-  DSPN_REQUIRE(w && grad && mom && segments && nseg > 0 && nseg <= DSPN_SGD_MAX_SEGMENTS && total4 > 0,
-               "sgd_momentum_segments: need w, grad, mom, a segment table of 1 .. DSPN_SGD_MAX_SEGMENTS rows and total4 > 0");
-  const long long blocks = (total4 + (long long)kT * kSgdPer - 1) / ((long long)kT * kSgdPer);
-  DSPN_REQUIRE(blocks <= 0x7fffffffLL, "sgd_momentum_segments: total4 too large");
-  hipLaunchKernelGGL(sgd_segments_kernel, dim3((unsigned)blocks), dim3(kT), sizeof(long long) * (size_t)nseg, S_(stream),
-                     reinterpret_cast<float4 *>(w), reinterpret_cast<const float4 *>(grad), reinterpret_cast<float4 *>(mom),
-                     segments, nseg, total4, lr, momentum, wd, rescale);
-  return dspn::check_launch("sgd_momentum_segments");
-}
-#endif
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 //   d out / d x_real = (1-fy) (v01 - v00) + fy (v11 - v10)   (out-of-image neighbours are 0),
 //   d L / d theta = sum over target pixels of [dL/dx_src * (x_t, y_t, 1), dL/dy_src * (x_t, y_t, 1)].
 // With theta = (1,0,0,0,1,0) every product above is exact, so the identity case reproduces the plain
-// align-corners resize of nn.hip bit for bit.
+// align-corners resize of nn_resize_eval.hip bit for bit.
 //
 // Forward: one thread per (pixel, float4 column) of the destination sums every source that covers the
 // column (a concat writes disjoint slices, the per-level evaluation of score3_conv sums six maps in one
@@ -29,7 +29,7 @@ using dspn::st_t;
 using dspn::A4Ptr;
 using dspn::CA4Ptr;
 
-#pragma clang fp contract(fast)   // as nn.hip: the identity grid then reproduces its plain resize kernel bit for bit
+#pragma clang fp contract(fast)   // as nn_resize_eval.hip: the identity grid then reproduces its plain resize kernel bit for bit
 
 namespace {
 

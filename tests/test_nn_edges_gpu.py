@@ -1,4 +1,4 @@
-"""Pooling, loss, layout, column-sum and SGD kernels of dspnet_amd/csrc/nn.hip at their edges, against plain float64
+"""Pooling, loss, layout, column-sum and SGD kernels of dspnet_amd/csrc/nn.hip and nn_float_ops.hip at their edges, against plain float64
 references written here (torch CPU / numpy; never another kernel of this library): every pooling geometry the three symbols
 use, odd and tiny maps, launches past the workgroup cap of `grid_for` (where only the grid-stride loop covers the tensor),
 the softmax dispatch boundaries, and the limits the C ABI refuses.
@@ -38,10 +38,10 @@ U = 2.0 ** -24          # unit roundoff of float32
 def _grid_cap_items():
     """work items one launch covers without its grid-stride loop, read from the source:
     `inline int grid_for(long long n, int per_block = kT, int cap = 8192)` with `constexpr int kT = 256` -> 2 097 152"""
-    src = open(os.path.join(os.path.dirname(fn.__file__), "csrc", "nn.hip")).read()
+    src = open(os.path.join(os.path.dirname(fn.__file__), "csrc", "nn_launch.h")).read()
     cap = re.search(r"inline int grid_for\(long long n, int per_block = kT, int cap = (\d+)\)", src)
     kt = re.search(r"constexpr int kT = (\d+);", src)
-    assert cap and kt, "grid_for / kT not found in nn.hip: update this reader"
+    assert cap and kt, "grid_for / kT not found in nn_launch.h: update this reader"
     return int(cap.group(1)) * int(kt.group(1))
 
 
