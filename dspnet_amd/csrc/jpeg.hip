@@ -21,6 +21,7 @@
 
 #include "dspn_common.h"
 #include "jpeg_host.h"
+#include "jpeg_huff.h"
 
 namespace {
 
@@ -35,22 +36,8 @@ struct Pools { long long coef_count, images_bytes; };
 // true when every index the kernels derive from `s` stays inside coefs / workspace (coef_count) and images_out
 __device__ bool sample_ok(const dspn_jpeg_sample &s, const Pools &pl) {
   if (s.skip) return false;
-  if (s.width < 1 || s.height < 1 || s.width > 65535 || s.height > 65535) return false;
-  if (s.ncomp != 1 && s.ncomp != 3) return false;
-  int hs = 1, vs = 1;
-  if (s.ncomp == 3) {
-    hs = s.hsamp; vs = s.vsamp;
-    if (!((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))) return false;
-  }
-  if (s.img_offset < 0 || s.img_offset > pl.images_bytes - 3LL * s.width * s.height) return false;
-  for (int c = 0; c < s.ncomp; ++c) {
-    const int cw = c ? (s.width + hs - 1) / hs : s.width, ch = c ? (s.height + vs - 1) / vs : s.height;
-    const int bw = s.blocks_w[c], bh = s.blocks_h[c];
-    if (bw < 1 || bh < 1 || bw > 8192 || bh > 8192 || bw * 8 < cw || bh * 8 < ch) return false;
-    const long long off = s.coef_offset[c];
-    if (off < 0 || (off & 63) || off > pl.coef_count - 64LL * bw * bh) return false;
-  }
-  return true;
+  if (!dspn_jpeg_huff::coef_geometry_ok(s, pl.coef_count)) return false;
+  return s.img_offset >= 0 && s.img_offset <= pl.images_bytes - 3LL * s.width * s.height;
 }
 
 // first[b] = units of samples 0 .. b - 1 (first[B] = all); units(s) is called for valid samples only
@@ -255,7 +242,133 @@ __global__ __launch_bounds__(kT) void jpeg_colour_kernel(const unsigned char *__
   }
 }
 
+// ---- entropy pass of streams with restart intervals (include/dspn_jpeg.h; the decode itself is jpeg_huff.h) -------------------
+// One restart interval per lane.  A workgroup is one wave: a chunk of kTE consecutive units is cut into runs of one sample, and
+// per run the wave builds that sample's decode tables in LDS (thread 0 checks the descriptors, one thread per table derives the
+// canonical codes, all fill the lookahead windows), then each lane decodes its interval serially.  Lanes diverge by design.
+// A lane's block is staged in LDS, dword j of lane t at word j * kTE + t (no two lanes on one bank whatever j they touch), and
+// leaves as eight 16-byte stores.  Per block: 128 B written; per interval its compressed bytes read once, a byte at a time.
+constexpr int kTE = 64;
+constexpr int kGridE = 2048;
+
+struct EntropyPools { long long bytes_count, segment_count, coef_count; };
+
+struct LdsSink {
+  unsigned *col;                           // this lane's column of the staging tile
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int j = 0; j < 32; ++j) col[j * kTE] = 0u;
+  }
+  // a position is set at most once after clear(): the decode only moves forward through the zigzag order
+  __device__ __forceinline__ void set(int at, int v) { col[(at >> 1) * kTE] |= ((unsigned)v & 0xFFFFu) << (16 * (at & 1)); }
+  __device__ __forceinline__ void store(short *dst) const {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      uint4 q;
+      q.x = col[(4 * j) * kTE]; q.y = col[(4 * j + 1) * kTE]; q.z = col[(4 * j + 2) * kTE]; q.w = col[(4 * j + 3) * kTE];
+      reinterpret_cast<uint4 *>(dst)[j] = q;
+    }
+  }
+};
+
+__global__ __launch_bounds__(kTE) void jpeg_entropy_kernel(const unsigned char *__restrict__ bytes,
+                                                           const dspn_jpeg_sample *__restrict__ samples,
+                                                           const dspn_jpeg_scan *__restrict__ scans, int B,
+                                                           const unsigned *__restrict__ segments, EntropyPools pl,
+                                                           short *__restrict__ coefs, int *__restrict__ status) {
+  namespace hf = dspn_jpeg_huff;
+  __shared__ long long first[kMaxB + 1];
+  __shared__ hf::Table tables[hf::kSlots];
+  __shared__ hf::Layout layout;
+  __shared__ int layout_ok;
+  __shared__ unsigned tile[32 * kTE];
+  __shared__ unsigned char natural[64];
+  const int tid = threadIdx.x;
+  for (int b = tid; b < B; b += kTE) {
+    hf::Layout L;
+    first[b + 1] = hf::prepare(samples[b], scans[b], pl.bytes_count, pl.segment_count, pl.coef_count, L) ? L.segments : 0;
+  }
+  if (tid == 0) hf::fill_natural(natural);
+  __syncthreads();
+  if (tid == 0) {
+    long long acc = 0;
+    first[0] = 0;
+    for (int b = 1; b <= B; ++b) { acc += first[b]; first[b] = acc; }
+  }
+  __syncthreads();
+  const long long total = first[B];
+  LdsSink sink;
+  sink.col = tile + tid;
+  for (long long base = (long long)blockIdx.x * kTE; base < total; base += (long long)gridDim.x * kTE) {
+    const long long chunk_end = base + kTE < total ? base + kTE : total;
+    long long u0 = base;
+    while (u0 < chunk_end) {               // the same for every lane: at most kTE runs
+      const int b = find_sample(first, B, u0);
+      const long long run_end = first[b + 1] < chunk_end ? first[b + 1] : chunk_end;
+      __syncthreads();                     // the run before this one has let go of layout and tables
+      if (tid == 0) layout_ok = hf::prepare(samples[b], scans[b], pl.bytes_count, pl.segment_count, pl.coef_count, layout) ? 1 : 0;
+      __syncthreads();
+      if (layout_ok) {
+        if (tid < hf::kSlots) {
+          const int t = layout.slot_table[tid];
+          if (t < 0) tables[tid].nvals = -1;
+          else hf::build_codes(tables[tid], t < 4 ? scans[b].dc_counts[t] : scans[b].ac_counts[t - 4],
+                               t < 4 ? scans[b].dc_values[t] : scans[b].ac_values[t - 4]);
+        }
+        __syncthreads();
+        for (int k = 0; k < hf::kSlots; ++k)
+          if (layout.slot_table[k] >= 0) hf::build_look(tables[k], tid, kTE);
+        __syncthreads();
+        const long long u = u0 + tid;
+        if (u < run_end) {
+          const int i = (int)(u - first[b]);
+          const int code = hf::run_segment(layout, i, bytes, segments, tables, natural, coefs, sink);
+          if (code) atomicMax(&status[b], hf::status_word(code, i));
+        }
+      }
+      u0 = run_end;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" long long dspn_jpeg_scan_segments(const dspn_jpeg_info *info) {
+  return info ? dspn_jpeg::scan_segments(*info) : 0;
+}
+
+extern "C" int dspn_jpeg_scan_index(const unsigned char *bytes, size_t n, const dspn_jpeg_info *info, dspn_jpeg_scan *scan,
+                                    unsigned int *seg_offsets, size_t seg_capacity) {
+  return dspn_jpeg::scan_index(bytes, n, info, scan, seg_offsets, seg_capacity, dspn::last_error_buf(), 512) ? DSPN_ERR_ARG_ : 0;
+}
+
+extern "C" int dspn_jpeg_entropy_decode_segments(const unsigned char *bytes, long long bytes_count, const dspn_jpeg_sample *sample,
+                                                 const dspn_jpeg_scan *scan, const unsigned int *segments, long long segment_count,
+                                                 short *coefs, long long coef_count, int *status) {
+  DSPN_REQUIRE(bytes && sample && scan && segments && coefs && status, "jpeg_entropy_decode_segments: null argument");
+  DSPN_REQUIRE(bytes_count > 0 && segment_count > 0 && coef_count > 0, "jpeg_entropy_decode_segments: bad pool sizes");
+  *status = dspn_jpeg_huff::decode_sample(bytes, bytes_count, *sample, *scan, segments, segment_count, coefs, coef_count);
+  return 0;
+}
+
+extern "C" int dspn_jpeg_entropy_decode_batch(const unsigned char *bytes, long long bytes_count, const dspn_jpeg_sample *samples,
+                                              const dspn_jpeg_scan *scans, int B, const unsigned int *segments,
+                                              long long segment_count, short *coefs, long long coef_count, int *status, void *stream) {
+  DSPN_REQUIRE(bytes && samples && scans && segments && coefs && status, "jpeg_entropy_decode_batch: null argument");
+  DSPN_REQUIRE(B > 0 && B <= kMaxB, "jpeg_entropy_decode_batch: bad batch (0 < B <= %d)", kMaxB);
+  DSPN_REQUIRE(bytes_count > 0 && segment_count > 0 && coef_count > 0 && coef_count % 64 == 0,
+               "jpeg_entropy_decode_batch: bad pool sizes");
+  DSPN_REQUIRE((reinterpret_cast<uintptr_t>(coefs) & 15) == 0 && (reinterpret_cast<uintptr_t>(samples) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(scans) & 7) == 0 && (reinterpret_cast<uintptr_t>(segments) & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+               "jpeg_entropy_decode_batch: coefs must be 16-byte aligned, samples and scans 8-byte, segments and status 4-byte");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t cleared = hipMemsetAsync(status, 0, sizeof(int) * (size_t)B, s);
+  if (cleared != hipSuccess) return dspn::fail(DSPN_ERR_LAUNCH_, "jpeg_entropy_decode_batch: %s", hipGetErrorString(cleared));
+  const EntropyPools pl = {bytes_count, segment_count, coef_count};
+  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(kGridE), dim3(kTE), 0, s, bytes, samples, scans, B, segments, pl, coefs, status);
+  return dspn::check_launch("jpeg_entropy_decode_batch");
+}
 
 extern "C" int dspn_jpeg_probe(const unsigned char *bytes, size_t n, dspn_jpeg_info *info) {
   DSPN_REQUIRE(info, "jpeg_probe: null argument");

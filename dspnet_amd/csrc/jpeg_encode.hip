@@ -252,7 +252,12 @@ extern "C" int dspn_jpeg_encode_geometry(dspn_jpeg_enc_sample *s, long long coef
 
 extern "C" int dspn_jpeg_entropy_encode(const short *coefs, const dspn_jpeg_enc_sample *s, unsigned char *out, size_t capacity,
                                         size_t *length) {
-  const int rc = dspn_jpeg_enc::entropy_encode(coefs, s, out, capacity, length, dspn::last_error_buf(), 512);
+  return dspn_jpeg_entropy_encode_restart(coefs, s, 0, out, capacity, length);
+}
+
+extern "C" int dspn_jpeg_entropy_encode_restart(const short *coefs, const dspn_jpeg_enc_sample *s, int restart_interval,
+                                                unsigned char *out, size_t capacity, size_t *length) {
+  const int rc = dspn_jpeg_enc::entropy_encode(coefs, s, restart_interval, out, capacity, length, dspn::last_error_buf(), 512);
   return rc == 0 ? 0 : (rc == dspn_jpeg_enc::kTooSmall ? DSPN_ERR_WORKSPACE_ : DSPN_ERR_ARG_);
 }
 

@@ -203,10 +203,13 @@ inline void put_dht(Out &o, int tc_th, const unsigned char *bits, const unsigned
 }
 
 // -> 0, kErr, or kTooSmall (the file needs *length > capacity bytes; out[0 .. capacity - 1] hold its beginning)
-inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, unsigned char *out, size_t capacity, size_t *length,
-                          char *err, size_t errn) {
+// restart_interval: MCUs between restart markers, 0: none (and no DRI segment)
+inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, int restart_interval, unsigned char *out,
+                          size_t capacity, size_t *length, char *err, size_t errn) {
   if (!coefs || !s || !length || (!out && capacity)) return fail(err, errn, "jpeg_entropy_encode: null argument");
   *length = 0;
+  if (restart_interval < 0 || restart_interval > 65535)
+    return fail(err, errn, "jpeg_entropy_encode: a restart interval of %d MCUs (0..65535)", restart_interval);
   Geometry g;
   if (geometry(s->width, s->height, s->ncomp, s->hsamp, s->vsamp, g, err, errn)) return kErr;
   for (int c = 0; c < g.ncomp; ++c) {
@@ -249,13 +252,25 @@ inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, u
     put_dht(o, 0x01, kDcChrBits, kDcVals);
     put_dht(o, 0x11, kAcChrBits, kAcChrVals);
   }
+  if (restart_interval) { o.put2(0xFFDD); o.put2(4); o.put2((unsigned)restart_interval); }   // where libjpeg writes it: with the scan header
   o.put2(0xFFDA); o.put2((unsigned)(6 + 2 * g.ncomp)); o.put((unsigned)g.ncomp);
   for (int c = 0; c < g.ncomp; ++c) { o.put((unsigned)(c + 1)); o.put(c ? 0x11u : 0x00u); }
   o.put(0); o.put(63); o.put(0);
 
   int pred[3] = {0, 0, 0};
+  int until_restart = restart_interval, next_rst = 0;
   for (int my = 0; my < g.mcuy; ++my)
-    for (int mx = 0; mx < g.mcux; ++mx)
+    for (int mx = 0; mx < g.mcux; ++mx) {
+      if (restart_interval) {
+        if (until_restart == 0) {                         // the partial byte padded with 1 bits, RSTn, the predictors reset
+          o.flush_ones();
+          o.put2(0xFFD0u + (unsigned)next_rst);
+          next_rst = (next_rst + 1) & 7;
+          pred[0] = pred[1] = pred[2] = 0;
+          until_restart = restart_interval;
+        }
+        --until_restart;
+      }
       for (int c = 0; c < g.ncomp; ++c) {
         const int t = c ? 1 : 0;
         const int ch = c ? 1 : g.hs, cv = c ? 1 : g.vs;
@@ -272,6 +287,7 @@ inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, u
             if (encode_block(o, dc[t], ac[t], blk, last_dc, pred[c], err, errn)) return kErr;
           }
       }
+    }
   o.flush_ones();
   o.put2(0xFFD9);
   *length = o.n;
@@ -280,6 +296,11 @@ inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, u
     return kTooSmall;
   }
   return 0;
+}
+
+inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, unsigned char *out, size_t capacity, size_t *length,
+                          char *err, size_t errn) {
+  return entropy_encode(coefs, s, 0, out, capacity, length, err, errn);
 }
 
 }  // namespace dspn_jpeg_enc

@@ -23,6 +23,7 @@ static const unsigned char kNatural[64] = {   // zigzag position -> natural (row
 struct Huff {
   bool present = false;
   int nvals = 0;
+  unsigned char counts[16] = {};    // codes per length 1..16, as the DHT segment carries them
   unsigned char vals[256];
   int maxcode[18];                  // largest code of each length, -1: none
   int valoffset[17];                // index of the first value of a length minus its first code
@@ -55,6 +56,7 @@ inline int build_huff(Huff &h, const unsigned char *bits /* [1..16] at bits[0..1
                       char *err, size_t errn) {
   h.present = true;
   h.nvals = nvals;
+  memcpy(h.counts, bits, 16);
   memcpy(h.vals, vals, (size_t)nvals);
   memset(h.look, 0, sizeof(h.look));
   int code = 0, k = 0;
@@ -326,17 +328,22 @@ inline int decode_block(BitReader &br, const Huff &dc, const Huff &ac, int &pred
   return 0;
 }
 
+// the caller's `info` against what these bytes parse to
+inline bool same_info(const dspn_jpeg_info &info, const dspn_jpeg_info &I) {
+  bool same = info.supported && info.width == I.width && info.height == I.height && info.ncomp == I.ncomp &&
+              info.coef_count == I.coef_count;
+  for (int c = 0; same && c < I.ncomp; ++c)
+    same = info.blocks_w[c] == I.blocks_w[c] && info.blocks_h[c] == I.blocks_h[c] && info.coef_offset[c] == I.coef_offset[c];
+  return same;
+}
+
 inline int entropy_decode(const unsigned char *b, size_t n, const dspn_jpeg_info *info, int16_t *out, char *err, size_t errn) {
   if (!info || !out) return fail(err, errn, "jpeg_entropy_decode: null argument");
   Parsed P;
   if (parse(b, n, P, err, errn)) return kErr;
   const dspn_jpeg_info &I = P.info;
   if (!I.supported) return fail(err, errn, "jpeg_entropy_decode: unsupported stream (reason %d)", I.reason);
-  bool same = info->supported && info->width == I.width && info->height == I.height && info->ncomp == I.ncomp &&
-              info->coef_count == I.coef_count;
-  for (int c = 0; same && c < I.ncomp; ++c)
-    same = info->blocks_w[c] == I.blocks_w[c] && info->blocks_h[c] == I.blocks_h[c] && info->coef_offset[c] == I.coef_offset[c];
-  if (!same) return fail(err, errn, "jpeg_entropy_decode: info does not describe these bytes");
+  if (!same_info(*info, I)) return fail(err, errn, "jpeg_entropy_decode: info does not describe these bytes");
   BitReader br;
   br.p = b + P.scan_pos;
   br.end = b + n;
@@ -374,6 +381,79 @@ inline int entropy_decode(const unsigned char *b, size_t n, const dspn_jpeg_info
   // and still decoded "something" ends elsewhere
   if (br.bits - br.pad >= 8 || br.p + 1 >= br.end || br.p[0] != 0xFF || br.p[1] == 0x00)
     return fail(err, errn, "jpeg: the scan does not end at a marker");
+  return 0;
+}
+
+// restart intervals of a supported scan, 0 without a restart interval
+inline long long scan_segments(const dspn_jpeg_info &I) {
+  if (!I.supported || I.restart_interval < 1 || I.hsamp[0] < 1 || I.vsamp[0] < 1) return 0;
+  const long long mcus = (long long)(I.blocks_w[0] / I.hsamp[0]) * (I.blocks_h[0] / I.vsamp[0]);
+  return (mcus + I.restart_interval - 1) / I.restart_interval;
+}
+
+// The restart intervals of the scan for the device entropy pass (dspn_jpeg_scan_index): a walk over the 0xFF bytes of the
+// entropy-coded data, no Huffman work.  Where the entropy pass above would miss a restart marker, so does this, in its words.
+inline int scan_index(const unsigned char *b, size_t n, const dspn_jpeg_info *info, dspn_jpeg_scan *scan, unsigned *seg,
+                      size_t seg_capacity, char *err, size_t errn) {
+  if (!info || !scan || !seg) return fail(err, errn, "jpeg_scan_index: null argument");
+  Parsed P;
+  if (parse(b, n, P, err, errn)) return kErr;
+  const dspn_jpeg_info &I = P.info;
+  if (!I.supported) return fail(err, errn, "jpeg_scan_index: unsupported stream (reason %d)", I.reason);
+  if (!same_info(*info, I)) return fail(err, errn, "jpeg_scan_index: info does not describe these bytes");
+  const int ri = I.restart_interval;
+  if (ri == 0) return fail(err, errn, "jpeg_scan_index: the stream has no restart interval: its entropy pass stays on the host");
+  if (ri > DSPN_JPEG_DEVICE_MAX_INTERVAL)
+    return fail(err, errn, "jpeg_scan_index: a restart interval of %d MCUs, the device pass takes up to %d: its entropy pass stays on the host",
+                ri, DSPN_JPEG_DEVICE_MAX_INTERVAL);
+  if (n - P.scan_pos > 0xFFFFFFFFull) return fail(err, errn, "jpeg_scan_index: a scan of more than 4 GiB");
+  const long long nseg = scan_segments(I);
+  if ((unsigned long long)nseg + 1 > seg_capacity)
+    return fail(err, errn, "jpeg_scan_index: %lld segment offsets, the table holds %zu", nseg + 1, seg_capacity);
+  long long count = 1;
+  int next_rst = 0;
+  size_t p = P.scan_pos, closing = 0;
+  seg[0] = 0;
+  for (;;) {
+    const unsigned char *q = p < n ? static_cast<const unsigned char *>(memchr(b + p, 0xFF, n - p)) : nullptr;
+    if (!q) return fail(err, errn, "jpeg: the scan does not end at a marker");
+    const size_t at = (size_t)(q - b);
+    size_t r = at + 1;
+    while (r < n && b[r] == 0xFF) ++r;                    // fill bytes
+    if (r >= n) return fail(err, errn, "jpeg: the scan does not end at a marker");
+    const int m = b[r];
+    if (m == 0x00 && r == at + 1) { p = r + 1; continue; }   // a stuffed 0xFF: data
+    if (m >= 0xD0 && m <= 0xD7) {
+      if (count == nseg) return fail(err, errn, "jpeg: restart marker %d behind the last restart interval", m - 0xD0);
+      if (m != 0xD0 + next_rst) return fail(err, errn, "jpeg: missing restart marker %d", next_rst);
+      seg[count++] = (unsigned)(r + 1 - P.scan_pos);
+      next_rst = (next_rst + 1) & 7;
+      p = r + 1;
+      continue;
+    }
+    // any other marker ends the scan (fill bytes in front of a stuffed zero are not a marker: the entropy pass looks for a
+    // restart marker there and misses it)
+    if (m == 0x00 || count != nseg) return fail(err, errn, "jpeg: missing restart marker %d", next_rst);
+    closing = at - P.scan_pos;
+    break;
+  }
+  seg[nseg] = (unsigned)closing;
+  memset(scan, 0, sizeof(*scan));
+  scan->data_offset = (long long)P.scan_pos;
+  scan->data_bytes = (long long)closing;
+  scan->first_segment = 0;
+  scan->segments = (int)nseg;
+  scan->restart_interval = ri;
+  scan->mcus_w = I.blocks_w[0] / I.hsamp[0];
+  scan->mcus_h = I.blocks_h[0] / I.vsamp[0];
+  for (int c = 0; c < I.ncomp; ++c) {
+    scan->dc_table[c] = (unsigned char)P.comp_td[c];
+    scan->ac_table[c] = (unsigned char)P.comp_ta[c];
+  }
+  for (int t = 0; t < 4; ++t) {
+    if (P.dc[t].present) { memcpy(scan->dc_counts[t], P.dc[t].counts, 16); memcpy(scan->dc_values[t], P.dc[t].vals, (size_t)P.dc[t].nvals); }
+    if (P.ac[t].present) { memcpy(scan->ac_counts[t], P.ac[t].counts, 16); memcpy(scan->ac_values[t], P.ac[t].vals, (size_t)P.ac[t].nvals); }
+  }
   return 0;
 }
 

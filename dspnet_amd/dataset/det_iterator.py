@@ -316,12 +316,12 @@ class ListImdb(object):
 
 
 # ---- the iterator ---------------------------------------------------------------------------------------------------
-def _decode_image(im, dst, coef_dst, raw_dst):
-    """worker thread: one image's host half -> "jpeg" or "png" when that format's launch finishes the image, False when
-    Pillow's pixels are in dst"""
+def _decode_image(im, dst, coef_dst, raw_dst, index=None):
+    """worker thread: one image's host half (with `index`, a JPEG's scan index only: jpeg.decode_image) -> "jpeg" or
+    "png" when that format's launch finishes the image, False when Pillow's pixels are in dst"""
     if isinstance(im, png.CodedRgb):
         return "png" if png.decode_rgb(im, dst, raw_dst) else False
-    return "jpeg" if jpeg.decode_image(im, dst, coef_dst) else False
+    return "jpeg" if jpeg.decode_image(im, dst, coef_dst, index) else False
 
 
 class DataBatch(object):
@@ -357,6 +357,11 @@ class DetIter(object):
     device_jpeg=True: baseline JPEGs are Huffman-decoded on the host and reconstructed on the device in front of the
     augmentation (same pixels as Pillow's, byte for byte); any other file takes the Pillow path, counted in
     `jpeg_fallbacks`.
+    device_entropy=True (with device_jpeg): JPEGs with restart intervals of at most jpeg.DEVICE_MAX_INTERVAL MCUs are
+    Huffman-decoded on the device as well -- a worker thread only indexes the scan, the compressed scan goes up instead of
+    the coefficients --, counted in `jpeg_device_entropy`.  The status words of a batch are read with one small copy before
+    it is handed out, and a scan the device could not decode raises DspnError naming the image: the host pass falls back
+    to Pillow for a corrupt scan, this pass cannot, because by then the batch is on the device.
     device_png=True: PNG files of every non-interlaced format but 16-bit greyscale are inflated on the host and turned into
     RGB on the device in front of the augmentation (same pixels as Pillow's convert("RGB"), byte for byte); a PNG file that
     is unsupported, malformed or does not inflate takes the Pillow path, counted in `png_fallbacks`.  With both switches on,
@@ -367,7 +372,9 @@ class DetIter(object):
 
     def __init__(self, imdb, batch_size, data_shape, mean_pixels=[128, 128, 128], rand_samplers=[], rand_mirror=False,
                  shuffle=False, rand_seed=None, is_train=True, max_crop_trial=50, device=None, decode_threads=8,
-                 device_jpeg=False, color_jitter=None, jitter_seed=0, device_png=False):
+                 device_jpeg=False, color_jitter=None, jitter_seed=0, device_png=False, device_entropy=False):
+        if device_entropy and not device_jpeg:
+            raise ValueError("device_entropy=True needs device_jpeg=True: it moves the rest of that decode to the device")
         self._imdb = imdb
         self.batch_size = batch_size
         if isinstance(data_shape, int):
@@ -396,6 +403,7 @@ class DetIter(object):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(decode_threads)))
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
+        self.device_entropy, self.jpeg_device_entropy = bool(device_entropy), 0
         self.device_png, self.png_fallbacks = bool(device_png), 0
         self._pools = HostPools(self.device.type == "cuda")
         self._jitter = colour_jitter.config(color_jitter) if is_train else None
@@ -409,7 +417,7 @@ class DetIter(object):
         self._label = None
         self.batch_indices = []
         self._get_batch()                                      # :179
-        self.jpeg_fallbacks = self.png_fallbacks = 0           # that batch was not delivered
+        self.jpeg_fallbacks = self.png_fallbacks = self.jpeg_device_entropy = 0    # that batch was not delivered
 
     @property
     def provide_data(self):
@@ -511,16 +519,17 @@ class DetIter(object):
         samples, tables = pack_batch(plans, H, W)
         jitter = colour_jitter.draw(self._jitter, len(plans), self._jitter_rs) if self._jitter is not None else None
         jbatch = jpeg.CodedBatch([im.info if isinstance(im, jpeg.Coded) else None for im in opened],
-                                 [p["img_offset"] for p in plans])
+                                 [p["img_offset"] for p in plans], self.device_entropy)
         pbatch = png.RgbBatch([im.info if isinstance(im, png.CodedRgb) else None for im in opened],
                               [p["img_offset"] for p in plans])
         pixels = self._pools.take("pixels", offset, torch.uint8)
-        coefs = self._pools.take("coefs", jbatch.count, torch.int16, floor=jbatch.FLOOR)
+        coefs = self._pools.take("coefs", jbatch.host_count, torch.int16, floor=jbatch.FLOOR)
         raw = self._pools.take("raw", pbatch.count, torch.uint8, floor=pbatch.FLOOR)
         pnp = pixels.numpy()
         dsts = [pnp[p["img_offset"]:p["img_offset"] + p["src_w"] * p["src_h"] * 3].reshape(p["src_h"], p["src_w"], 3)
                 for p in plans]
-        answers = list(self._pool.map(_decode_image, opened, dsts, jbatch.slices(coefs.numpy()), pbatch.slices(raw.numpy())))
+        answers = list(self._pool.map(_decode_image, opened, dsts, jbatch.slices(coefs.numpy()), pbatch.slices(raw.numpy()),
+                                      jbatch.indexers()))
         # per format: True -- its launch finishes the image; None -- the other format's does; False -- the host decoded it
         jbatch.answered([a == "jpeg" or (None if a else False) for a in answers])
         pbatch.answered([a == "png" or (None if a else False) for a in answers])
@@ -547,8 +556,10 @@ class DetIter(object):
         desc_dev = torch.from_numpy(desc).to(dev)              # descriptors and tables in one upload (56 B each: 4-aligned)
         ndesc = n * SAMPLE.itemsize
         keep = jbatch.launch(img_dev) + pbatch.launch(img_dev)
+        jbatch.check(["image %d" % i for i in prep["indices"]])     # the device entropy pass's status words, if it ran
         if self.device_jpeg:
             self.jpeg_fallbacks += jbatch.fallbacks
+            self.jpeg_device_entropy += jbatch.device_entropy
         if self.device_png:
             self.png_fallbacks += prep["png_on_host"]
         if prep["jitter"] is not None:                         # on the decoded pixels, in front of the crop

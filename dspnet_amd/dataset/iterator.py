@@ -145,6 +145,12 @@ class MultiTaskRecordIter(object):
     device_jpeg=True: baseline JPEG records are Huffman-decoded on the host and reconstructed on the device in front of
     the augmentation (same pixels as Pillow's, byte for byte); any other record takes the Pillow path, counted in
     `jpeg_fallbacks` (records of delivered batches since construction).
+    device_entropy=True (with device_jpeg): records whose JPEG carries restart intervals of at most
+    jpeg.DEVICE_MAX_INTERVAL MCUs (what im2rec writes with --restart-interval) are Huffman-decoded on the device as well: a
+    worker thread only indexes the scan, the compressed scan is uploaded instead of the coefficients, and
+    `jpeg_device_entropy` counts such records.  Before a batch is handed out its status words are read with one small
+    copy, and a scan the device could not decode raises DspnError naming the record: the host pass falls back to Pillow
+    for a corrupt scan, this pass cannot, because by then the batch is on the device.
     device_png=True: 8-bit greyscale / palette label maps are inflated on the host and unfiltered on the device in front of
     the augmentation (same bytes as Pillow's); any other label map takes the Pillow path, counted in `png_fallbacks`.
     color_jitter: a colour_jitter.ColorJitter (or a dict with its keys); with enable_aug and some probability in it not
@@ -155,10 +161,12 @@ class MultiTaskRecordIter(object):
     def __init__(self, path_imgrec, batch_size, data_shape, path_imglist="", label_width=-1, label_pad_width=-1,
                  label_pad_value=-1, resize_mode="force", mean_pixels=(123.68, 116.779, 103.939), enable_aug=True,
                  device=None, decode_threads=8, prefetch=True, cache_decoded=False, device_jpeg=False, device_png=False,
-                 color_jitter=None, jitter_seed=0, **kwargs):
+                 color_jitter=None, jitter_seed=0, device_entropy=False, **kwargs):
         if device_jpeg and cache_decoded:
             raise ValueError("device_jpeg=True with cache_decoded=True: the cache exists to avoid the host decode that "
                              "device_jpeg removes; choose one")
+        if device_entropy and not device_jpeg:
+            raise ValueError("device_entropy=True needs device_jpeg=True: it moves the rest of that decode to the device")
         if device_png and cache_decoded:
             raise ValueError("device_png=True with cache_decoded=True: the cache exists to avoid the host decode that "
                              "device_png removes; choose one")
@@ -205,12 +213,13 @@ class MultiTaskRecordIter(object):
         self._cache = {} if cache_decoded else None
         self._pools = [HostPools(torch.device(self.device).type == "cuda") for _ in range(2)]
         self.device_jpeg, self.jpeg_fallbacks = bool(device_jpeg), 0
+        self.device_entropy, self.jpeg_device_entropy = bool(device_entropy), 0
         self.device_png, self.png_fallbacks = bool(device_png), 0
         self._get_batch()
         if not self.provide_label:
             raise RuntimeError("Invalid ImageDetRecordIter: " + path_imgrec)
         self.reset()
-        self.jpeg_fallbacks = self.png_fallbacks = 0           # the batch above was not delivered
+        self.jpeg_fallbacks = self.png_fallbacks = self.jpeg_device_entropy = 0    # the batch above was not delivered
 
     # ---- epoch control (:401-434) -------------------------------------------------------------------------------
     def reset(self):
@@ -273,13 +282,13 @@ class MultiTaskRecordIter(object):
     def _decode(self, job):
         """one record into its slices of the pools (worker thread; the decoders and numpy's copy loops release the GIL)
         -> (the device reconstructs the image, the device unfilters the label map; None: there is no label map)"""
-        im, seg_im, img_dst, seg_dst, coef_dst, raw_dst, rec_id = job
+        im, seg_im, img_dst, seg_dst, coef_dst, raw_dst, rec_id, index = job
         if isinstance(im, Decoded):                            # cached pixels: one memcpy each
             img_dst[...] = im.a
             if seg_im is not None:
                 seg_dst[...] = seg_im.a
             return False, (None if seg_im is None else False)
-        answer = (jpeg.decode_image(im, img_dst, coef_dst),
+        answer = (jpeg.decode_image(im, img_dst, coef_dst, index),
                   None if seg_im is None else png.decode_label(seg_im, seg_dst, raw_dst))
         if self._cache is not None:
             self._cache[rec_id] = (img_dst.copy(), None if seg_im is None else seg_dst.copy())
@@ -293,20 +302,20 @@ class MultiTaskRecordIter(object):
         seg_sizes = [(sm.size[0] * sm.size[1] if sm is not None else 0) for _, _, sm, _, _ in peeked]
         img_offsets, seg_offsets = np.cumsum([0] + img_sizes).tolist(), np.cumsum([0] + seg_sizes).tolist()
         jbatch = jpeg.CodedBatch([im.info if isinstance(im, jpeg.Coded) else None for _, im, _, _, _ in peeked],
-                                 img_offsets)
+                                 img_offsets, self.device_entropy)
         pbatch = png.CodedBatch([sm.info if isinstance(sm, png.CodedLabel) else None for _, _, sm, _, _ in peeked],
                                 seg_offsets)
         pools = self._pools[serial % 2]                        # two sets of pinned staging buffers, used alternately
         pixels = pools.take("pixels", img_offsets[-1], torch.uint8)
         labels = pools.take("labels", seg_offsets[-1], torch.uint8)
-        coefs = pools.take("coefs", jbatch.count, torch.int16, floor=jbatch.FLOOR)
+        coefs = pools.take("coefs", jbatch.host_count, torch.int16, floor=jbatch.FLOOR)
         raw = pools.take("raw", pbatch.count, torch.uint8)
         ip, sp = pixels.numpy(), labels.numpy()
         label = np.ones((B, 1206)) * -1
         label[:, :3] = np.array(list(self.data_shape))
         samples = np.zeros(B, _SAMPLE)
         jobs, fnames = [], []
-        coef_dsts, raw_dsts = jbatch.slices(coefs.numpy()), pbatch.slices(raw.numpy())
+        coef_dsts, raw_dsts, indexers = jbatch.slices(coefs.numpy()), pbatch.slices(raw.numpy()), jbatch.indexers()
         for b, (hdr, im, seg_im, seg_path, rec_id) in enumerate(peeked):
             ww, hh = im.size
             slot = start + b
@@ -329,7 +338,7 @@ class MultiTaskRecordIter(object):
             s["minv"] = invert_affine(M)
             jobs.append((im, seg_im, ip[io_:io_ + img_sizes[b]].reshape(hh, ww, 3),
                          sp[so:so + seg_sizes[b]].reshape(hh, ww) if seg_im is not None else None,
-                         coef_dsts[b], raw_dsts[b], rec_id))
+                         coef_dsts[b], raw_dsts[b], rec_id, indexers[b]))
             label[b, 3:3 + hdr.shape[0]] = hdr
             fnames.append(seg_path)
         answers = list(self._pool.map(self._decode, jobs))
@@ -337,7 +346,7 @@ class MultiTaskRecordIter(object):
         pbatch.answered([a for _, a in answers])
         return {"pools": pools, "pixels": pixels[:max(img_offsets[-1], 1)], "labels": labels[:max(seg_offsets[-1], 1)],
                 "coefs": coefs, "raw": raw, "jpeg": jbatch, "png": pbatch, "samples": samples, "label": label,
-                "fnames": fnames, "start": start,
+                "fnames": fnames, "start": start, "records": ["record %s" % p[4] for p in peeked],
                 "jitter": None if self.jitter_params is None else self.jitter_params[start:start + B]}
 
     def _finish(self, prep):
@@ -350,8 +359,10 @@ class MultiTaskRecordIter(object):
         prep["pools"].uploaded(torch.cuda.current_stream(dev))
         desc_dev = torch.from_numpy(prep["samples"].view(np.uint8).reshape(-1)).to(dev)
         coded_keep = jbatch.launch(img_dev) + pbatch.launch(seg_dev)    # the coded records' bytes, in front of the warp
+        jbatch.check(prep["records"])                          # the device entropy pass's status words, if it ran
         if self.device_jpeg:
             self.jpeg_fallbacks += jbatch.fallbacks
+            self.jpeg_device_entropy += jbatch.device_entropy
         if self.device_png:
             self.png_fallbacks += pbatch.fallbacks
         if prep["jitter"] is not None:                         # on the decoded pixels, in front of the warp

@@ -66,9 +66,10 @@ def encode_blocks(images, samples, coefs, channel_order="rgb", stream=None):
     return ws
 
 
-def entropy_encode(coefs, sample, capacity=None):
-    """dspn_jpeg_entropy_encode: the file of one image as bytes.  coefs: the int16 host array sample["coef_offset"]
-    indexes; capacity: a first guess of the file's size (the call is repeated with the size it names if that was short)"""
+def entropy_encode(coefs, sample, capacity=None, restart_interval=0):
+    """dspn_jpeg_entropy_encode_restart: the file of one image as bytes.  coefs: the int16 host array
+    sample["coef_offset"] indexes; capacity: a first guess of the file's size (the call is repeated with the size it names
+    if that was short); restart_interval: MCUs between restart markers (Pillow's restart_marker_blocks), 0: none"""
     assert coefs.dtype == np.int16 and coefs.flags.c_contiguous
     nc = int(sample["ncomp"])
     last = max(int(sample["coef_offset"][c]) + 64 * int(sample["blocks_w"][c]) * int(sample["blocks_h"][c]) for c in range(nc))
@@ -76,10 +77,11 @@ def entropy_encode(coefs, sample, capacity=None):
     rec = np.array([sample], SAMPLE)
     lib = _lib.lib()
     n = _c.c_size_t(0)
+    ri = int(restart_interval)
     cap = int(capacity) if capacity else 1024 + last // 2
     for _ in range(2):
         out = np.empty(cap, np.uint8)
-        rc = lib.dspn_jpeg_entropy_encode(coefs.ctypes.data, rec.ctypes.data, out.ctypes.data, cap, _c.byref(n))
+        rc = lib.dspn_jpeg_entropy_encode_restart(coefs.ctypes.data, rec.ctypes.data, ri, out.ctypes.data, cap, _c.byref(n))
         if rc != _TOO_SMALL:
             break
         cap = n.value
@@ -87,12 +89,25 @@ def entropy_encode(coefs, sample, capacity=None):
     return out[:n.value].tobytes()
 
 
-def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", threads=8):
+def mcus_per_row(sample):
+    """MCUs in one row of the image a filled descriptor describes"""
+    hs = int(sample["hsamp"]) if int(sample["ncomp"]) == 3 else 1
+    return (int(sample["width"]) + 8 * hs - 1) // (8 * hs)
+
+
+def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", threads=8, restart_interval=0, restart_rows=0):
     """list of uint8 device tensors, (h, w, 3) or (h, w), of any mix of sizes -> list of JPEG files as bytes, each equal
     to Pillow's `Image.fromarray(x).save(f, format="JPEG", quality=quality, subsampling=subsampling)` (x in RGB order;
     channel_order="bgr" reads OpenCV's order instead; a (h, w) image is greyscale, for which subsampling says nothing).
     One upload of descriptors, two launches, one copy of the coefficients into pinned memory, and the entropy pass of
-    the images on `threads` threads."""
+    the images on `threads` threads.
+    restart_interval=n writes a restart marker every n MCUs (Pillow's restart_marker_blocks=n), restart_rows=r every r
+    MCU rows of each image (restart_marker_rows=r); at most one of the two.  Such files decode entirely on the device
+    (dataset/jpeg.py, device_entropy=True) when the interval is at most jpeg.DEVICE_MAX_INTERVAL MCUs."""
+    if restart_interval and restart_rows:
+        raise ValueError("restart_interval and restart_rows: at most one of the two")
+    if not 0 <= int(restart_interval) <= 65535 or int(restart_rows) < 0:
+        raise ValueError("restart_interval is 0..65535 MCUs and restart_rows >= 0, got %r and %r" % (restart_interval, restart_rows))
     if subsampling not in SUBSAMPLING:
         raise ValueError("subsampling is one of %s, got %r" % (sorted(SUBSAMPLING), subsampling))
     if channel_order not in CHANNEL_ORDER:
@@ -101,7 +116,7 @@ def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", t
     if not images:
         return []
     if len(images) > 1024:
-        return sum((encode_batch(images[k:k + 1024], quality, subsampling, channel_order, threads)
+        return sum((encode_batch(images[k:k + 1024], quality, subsampling, channel_order, threads, restart_interval, restart_rows)
                     for k in range(0, len(images), 1024)), [])
     tables = quant_tables(quality)
     dev = images[0].device
@@ -126,7 +141,11 @@ def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", t
         torch.cuda.current_stream(dev).synchronize()           # pool, descriptors and workspace go out of scope after this
     del ws
     cnp = host.numpy()
+    def one(s):                                                # libjpeg caps an interval given in rows at 65535 MCUs
+        ri = min(int(restart_rows) * mcus_per_row(s), 65535) if restart_rows else int(restart_interval)
+        return entropy_encode(cnp, s, restart_interval=ri)
+
     if threads <= 1 or len(images) == 1:
-        return [entropy_encode(cnp, s) for s in samples]
+        return [one(s) for s in samples]
     with ThreadPoolExecutor(min(int(threads), len(images))) as tp:
-        return list(tp.map(lambda s: entropy_encode(cnp, s), samples))
+        return list(tp.map(one, samples))

@@ -55,20 +55,28 @@ class CodedBatch(object):
     wrong only on a worker thread, so the decision what the device does falls in `answered`.
     A subclass names SAMPLE, FLOOR (the least element count its entry accepts) and gives `_describe` and `_launch`."""
 
-    def __init__(self, infos, out_offsets):
+    def __init__(self, infos, out_offsets, device_side=None):
         """infos: per sample the probed record of a stream for the device, or None; out_offsets: where each sample's
-        decoded bytes start in the output pool"""
+        decoded bytes start in the output pool; device_side: per sample, true where the device itself produces the
+        sample's coded slice (dataset/jpeg.py: the entropy pass on the device).  Such slices lie behind everyone
+        else's, so the host's part of the coded pool is its first `host_count` elements and only that is uploaded."""
         self.samples = np.zeros(len(infos), self.SAMPLE)
-        self.spans, self.count = [], 0
-        for s, info, out in zip(self.samples, infos, out_offsets):
-            n = self._describe(s, info, self.count, out) if info is not None else 0
-            self.spans.append((self.count, n))
-            self.count += n
+        self.spans, self.count = [None] * len(infos), 0
+        side = [False] * len(infos) if device_side is None else [bool(d) for d in device_side]
+        for want in (False, True):
+            for k, (s, info, out) in enumerate(zip(self.samples, infos, out_offsets)):
+                if side[k] != want:
+                    continue
+                n = self._describe(s, info, self.count, out) if info is not None else 0
+                self.spans[k] = (self.count, n)
+                self.count += n
+            if not want:
+                self.host_count = self.count
         self.on_device = self.fallbacks = 0
 
     def slices(self, pool):
-        """each sample's slice of the host array `pool` (empty where the sample is not coded)"""
-        return [pool[at:at + n] for at, n in self.spans]
+        """each sample's slice of the host array `pool` (empty where the sample is not coded, or coded on the device)"""
+        return [pool[at:at + n] if at + n <= self.host_count else pool[:0] for at, n in self.spans]
 
     def answered(self, answers):
         """what the workers said per sample: True -- its coded slice is filled, the device finishes it; False -- the host
@@ -81,8 +89,12 @@ class CodedBatch(object):
         the batch.  -> the device output pool (None without `decoded`: the caller brings its own).
         The coded route is taken exactly when some sample is left to the device; then the host's bytes go up only if
         there are any.  Otherwise the host's pool goes up as it is and nothing of this format is uploaded or launched."""
-        if self.on_device:
+        if self.on_device and self.host_count == self.count:
             self._coded_dev = coded[:max(self.count, self.FLOOR)].to(device, non_blocking=True)
+        elif self.on_device:                                   # the device fills the rest of the pool itself
+            self._coded_dev = torch.empty(max(self.count, self.FLOOR), dtype=coded.dtype, device=device)
+            if self.host_count:
+                self._coded_dev[:self.host_count].copy_(coded[:self.host_count], non_blocking=True)
         if decoded is None:
             return None
         return upload_decoded(decoded, device, self.on_device, self.fallbacks)

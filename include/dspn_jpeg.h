@@ -1,7 +1,9 @@
 /*
  * dspn_jpeg.h -- C ABI of the record iterator's JPEG decode, split where the work stops being serial:
  *   host   : marker parsing and Huffman decoding into quantised DCT coefficients (dspn_jpeg_probe,
- *            dspn_jpeg_entropy_decode; plain C++, no HIP call, thread-safe, no global state);
+ *            dspn_jpeg_entropy_decode; plain C++, no HIP call, thread-safe, no global state); for a stream with restart
+ *            intervals only the search for the markers (dspn_jpeg_scan_index), the Huffman decoding then runs on the
+ *            device, one interval per lane (dspn_jpeg_entropy_decode_batch; below);
  *   device : dequantisation, 8 x 8 inverse DCT, chroma upsampling and YCbCr -> RGB for the whole batch
  *            (dspn_jpeg_reconstruct_batch_u8), written straight into the byte pool dspn_augment_batch_u8 reads.
  * The upload of a 4:2:0 image is its int16 coefficients, 1.5 samples per pixel = 3 B per pixel, as many as RGB8.
@@ -102,6 +104,80 @@ size_t dspn_jpeg_reconstruct_workspace_bytes(long long coef_count);
 int dspn_jpeg_reconstruct_batch_u8(const short *coefs, long long coef_count, const dspn_jpeg_sample *samples, int B,
                                    unsigned char *images_out, long long images_bytes, void *workspace,
                                    size_t workspace_bytes, void *stream);
+
+/* ---- entropy pass on the device: streams with restart intervals ------------------------------------------------------
+ * Baseline Huffman decoding is serial only between restart markers: at each RSTn the bit stream is byte-aligned and the DC
+ * predictors reset, so every restart interval is a unit of work of its own.  The host only finds the markers
+ * (dspn_jpeg_scan_index: no Huffman work), the device decodes one interval per lane (dspn_jpeg_entropy_decode_batch) into
+ * the coefficient pool dspn_jpeg_reconstruct_batch_u8 reads.  The upload is the compressed scan instead of 3 B per pixel. */
+
+/* Most MCUs of one restart interval the device pass takes: the serial work of one lane.  A stream with a longer interval
+ * (or none) stays on the host pass.  Measured (profiles/jpeg_device_entropy.txt): the launch's time grows in proportion to
+ * the interval, and above about 40 MCUs it is slower than the host pass on the 16 threads a job has; 32 is the largest power
+ * of two below that.  (The first value, 512, was 40 times slower than the host.) */
+#define DSPN_JPEG_DEVICE_MAX_INTERVAL 32
+
+/* dspn_jpeg_entropy_decode_batch's status word of a sample: 0, or ((DSPN_JPEG_STATUS_SEGMENTS - first bad segment) << 3) | code
+ * (an atomic maximum over the lanes, so the FIRST bad segment of the sample wins) */
+#define DSPN_JPEG_STATUS_SEGMENTS ((1 << 27) - 1)
+enum {
+  DSPN_JPEG_BAD_CODE = 1,           /* a Huffman code that is not in its table */
+  DSPN_JPEG_BAD_INDEX = 2,          /* a coefficient index (or a zero run) past 63 */
+  DSPN_JPEG_BAD_SIZE = 3,           /* a DC difference of more than 11 bits, an AC value of more than 10 */
+  DSPN_JPEG_BAD_END = 4,            /* the segment's data ends inside a block */
+  DSPN_JPEG_BAD_REST = 5,           /* a whole byte or more of unread data before the segment's end */
+  DSPN_JPEG_BAD_DC = 6,             /* a DC value outside int16 */
+  DSPN_JPEG_BAD_SEGMENT = 7         /* the segment table or a Huffman table of the descriptor contradicts itself */
+};
+
+/* one stream of a batch for the device entropy pass, beside its dspn_jpeg_sample (which keeps its layout) */
+typedef struct dspn_jpeg_scan {
+  long long data_offset;            /* first byte of the entropy-coded data in the batch's byte pool (dspn_jpeg_scan_index
+                                       leaves the offset inside the stream here; the caller adds where it put the bytes) */
+  long long data_bytes;             /* bytes of entropy-coded data, up to the marker that ends the scan */
+  long long first_segment;          /* index of the stream's first entry in the batch's segment table */
+  int segments;                     /* restart intervals of the scan; 0: the coefficients of this sample come from elsewhere */
+  int restart_interval;             /* MCUs per interval, 1..DSPN_JPEG_DEVICE_MAX_INTERVAL */
+  int mcus_w, mcus_h;               /* the MCU grid */
+  unsigned char dc_table[4], ac_table[4];     /* Huffman table selector of each component */
+  unsigned char dc_counts[4][16], ac_counts[4][16];   /* the tables as the DHT segments carry them: codes per length 1..16 */
+  unsigned char dc_values[4][256], ac_values[4][256]; /* and the symbols in code order (a table that is not defined: all zero) */
+} dspn_jpeg_scan;
+
+/* restart intervals of the scan `info` describes: ceil(MCUs / restart_interval); 0 without a restart interval or for an
+ * unsupported stream.  Pure. */
+long long dspn_jpeg_scan_segments(const dspn_jpeg_info *info);
+
+/* Finds the restart intervals of the scan: walks from SOS to the marker that ends the scan looking only at 0xFF bytes
+ * (FF 00 is stuffing, FF FF fill, FF D0..D7 a restart marker) and writes dspn_jpeg_scan_segments(info) + 1 offsets into
+ * seg_offsets, relative to the first byte of entropy-coded data: where the data of every interval starts, and where the
+ * marker that ends the scan stands.  `scan` is filled for a pool that holds the stream's bytes from 0 and a segment table
+ * that holds only these offsets.  `info` must be what dspn_jpeg_probe said of these bytes.  Plain C++, no HIP call,
+ * thread-safe, no global state.  < 0 with a message: a stream without a restart interval or with one above
+ * DSPN_JPEG_DEVICE_MAX_INTERVAL (it stays on the host pass), restart markers that are missing, misnumbered (0..7 in cycle) or
+ * too many, a scan that does not end at a marker, or seg_capacity below the count. */
+int dspn_jpeg_scan_index(const unsigned char *bytes, size_t n, const dspn_jpeg_info *info, dspn_jpeg_scan *scan,
+                         unsigned int *seg_offsets, size_t seg_capacity);
+
+/* The entropy pass of a batch on the device, one launch on `stream` in front of dspn_jpeg_reconstruct_batch_u8's two:
+ * bytes: the byte pool (device, bytes_count bytes); samples, scans: B <= 1024 descriptors each (device); segments: the
+ * segment table (device, segment_count entries); coefs: the int16 pool (device, 16-byte aligned); status: B ints (device),
+ * zeroed here on `stream`.  One restart interval is one unit of work and one lane decodes it serially; the coefficients are
+ * exactly dspn_jpeg_entropy_decode's, every block of the padded grids of a decoded sample written in full.
+ * Nothing is trusted: a sample whose descriptors contradict themselves or each other, or could index outside a pool, is no
+ * work, like skip (so is segments == 0); a lane reads no byte outside its segment and writes no block outside its MCUs; a
+ * lane that meets bad data stops and leaves a status word (above) for its sample, whose pixels are then unspecified.
+ * Nothing else is affected. */
+int dspn_jpeg_entropy_decode_batch(const unsigned char *bytes, long long bytes_count, const dspn_jpeg_sample *samples,
+                                   const dspn_jpeg_scan *scans, int B, const unsigned int *segments, long long segment_count,
+                                   short *coefs, long long coef_count, int *status, void *stream);
+
+/* The same decode, the same program text (csrc/jpeg_huff.h), built for the host and run serially over the segments of ONE
+ * sample, all pointers in host memory: what the tests and tools/jpeg_huff_check.cpp compare and run under the sanitizers.
+ * *status receives the status word.  0 also when the status word is not: the call itself went well. */
+int dspn_jpeg_entropy_decode_segments(const unsigned char *bytes, long long bytes_count, const dspn_jpeg_sample *sample,
+                                      const dspn_jpeg_scan *scan, const unsigned int *segments, long long segment_count,
+                                      short *coefs, long long coef_count, int *status);
 
 #ifdef __cplusplus
 }

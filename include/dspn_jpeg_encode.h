@@ -6,8 +6,8 @@
  *            no HIP call, thread-safe, no global state) -- and the quantisation tables of a quality (dspn_jpeg_quant_tables).
  *
  * Yardstick: the file equals what libjpeg-turbo writes for the same pixels with its default ("slow integer") forward
- * DCT, standard Huffman tables, no restart markers -- Pillow's Image.save(format="JPEG", quality=q, subsampling=s) --
- * byte for byte.  The arithmetic, all of it integer (32 bits suffice), in the order it is applied:
+ * DCT and standard Huffman tables -- Pillow's Image.save(format="JPEG", quality=q, subsampling=s), and with a restart
+ * interval of n MCUs (dspn_jpeg_entropy_encode_restart) the same call with restart_marker_blocks=n -- byte for byte.  The arithmetic, all of it integer (32 bits suffice), in the order it is applied:
  *   colour, F(x) = int(x * 65536 + 0.5), arithmetic shifts:
  *     Y  = ( F(.299) R + F(.587) G + F(.114) B + 32768) >> 16
  *     Cb = (-F(.16874) R - F(.33126) G + F(.5) B + (128 << 16) + 32767) >> 16
@@ -91,6 +91,16 @@ int dspn_jpeg_encode_blocks_batch_u8(const unsigned char *images, long long imag
  * Huffman coding can carry (a DC difference of more than 11 bits, an AC value of more than 10) is an error. */
 int dspn_jpeg_entropy_encode(const short *coefs, const dspn_jpeg_enc_sample *s, unsigned char *out, size_t capacity,
                              size_t *length);
+
+/* dspn_jpeg_entropy_encode with restart markers every restart_interval MCUs (0..65535; 0 gives exactly the bytes of the
+ * entry above): a DRI segment where libjpeg writes it (in the scan header, behind the DHTs and in front of SOS), RSTn
+ * (n = 0..7 in cycle) after every restart_interval MCUs except the last, the partial byte in front of each marker padded
+ * with 1 bits, the DC predictors reset at each marker.  The dummy-block rule of the header note is unchanged: a dummy
+ * block takes the DC of the block before it in the MCU's order, whatever the predictor was reset to.  Such a file equals
+ * Pillow's with restart_marker_blocks=restart_interval (restart_marker_rows=r: r times the MCUs of a row), and every
+ * restart interval of it is a unit of work of its own for dspn_jpeg_entropy_decode_batch (dspn_jpeg.h). */
+int dspn_jpeg_entropy_encode_restart(const short *coefs, const dspn_jpeg_enc_sample *s, int restart_interval,
+                                     unsigned char *out, size_t capacity, size_t *length);
 
 #ifdef __cplusplus
 }

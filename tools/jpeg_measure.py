@@ -4,8 +4,9 @@ this script's output.  Everything is generated from seeds.
     python tools/jpeg_measure.py host                      # 1: entropy pass against Pillow's full decode, per image
     python tools/jpeg_measure.py device                    # 2: reconstruction of B = 32 at 1024 x 2048, device events
     python tools/jpeg_measure.py iterator --workdir DIR    # 3: MultiTaskRecordIter batches/s, device_jpeg off and on
+    python tools/jpeg_measure.py entropy --workdir DIR     # profiles/jpeg_device_entropy.txt: the entropy pass on the device
 
-`host` needs no GPU; `device` and `iterator` fail without one."""
+`host` needs no GPU; `device`, `iterator` and `entropy` fail without one."""
 import argparse
 import io
 import os
@@ -28,10 +29,12 @@ def picture(seed):
     return np.clip(np.stack(chans, -1) + g.normal(0, 8, (H, W, 3)), 0, 255).astype(np.uint8)
 
 
-def jpeg_bytes(arr, quality):
+def jpeg_bytes(arr, quality, restart_interval=0):
+    """restart_interval > 0: Pillow's restart_marker_blocks, the bytes jpeg_encode.encode_batch(restart_interval=) writes"""
     from PIL import Image
     buf = io.BytesIO()
-    Image.fromarray(arr).save(buf, format="JPEG", quality=quality, subsampling=2)
+    kw = {"restart_marker_blocks": restart_interval} if restart_interval else {}
+    Image.fromarray(arr).save(buf, format="JPEG", quality=quality, subsampling=2, **kw)
     return buf.getvalue()
 
 
@@ -134,7 +137,8 @@ def device(args):
     print("dspn_augment_batch_u8 of the same batch to (%d, 3, %d, %d), no label maps: %.3f ms per call" % (B, H // 2, W // 2, t_a))
 
 
-def _write_records(root, n):
+def _write_records(root, n, restart_interval=0, distinct=None):
+    """distinct: the number of different pictures the records cycle through (None: every record its own)"""
     from PIL import Image
     from dspnet_amd.dataset import recordio
     os.makedirs(os.path.join(root, "cityscapes", "SegmentationClass"), exist_ok=True)
@@ -147,7 +151,7 @@ def _write_records(root, n):
             x0, y0 = g.uniform(0, .8), g.uniform(0, .8)
             rows[k] = [g.integers(0, 8), x0, y0, x0 + g.uniform(.05, .2), y0 + g.uniform(.05, .2), g.uniform(0, 1)]
         label = np.array([2, 6] + rows.reshape(-1).tolist(), np.float32)
-        rec.write_idx(i, recordio.pack(recordio.IRHeader(0, label, i, 0), jpeg_bytes(picture(3000 + i), 92)))
+        rec.write_idx(i, recordio.pack(recordio.IRHeader(0, label, i, 0), jpeg_bytes(picture(3000 + i % (distinct or n)), 92, restart_interval)))
         seg = np.repeat(np.repeat(g.integers(0, 19, (H // 64, W // 64)).astype(np.uint8), 64, 0), 64, 1)   # large regions
         Image.fromarray(seg).save(os.path.join(root, "cityscapes", "SegmentationClass", "city_%06d_gtFine_labelTrainIds.png" % i))
         lines.append("%d\tJPEGImages/city_%06d_leftImg8bit.jpg\n" % (i, i))
@@ -188,15 +192,113 @@ def iterator(args):
                                            ["%.2f" % r for r in rates[True]], on / off, fb))
 
 
+def entropy(args):
+    """the device entropy pass against the 16-thread host entropy pass: B = 32 streams of 1024 x 2048 4:2:0 at quality 92
+    and 75, at the restart intervals of --intervals (MCUs; one MCU row of these images is 128)"""
+    import torch
+    from dspnet_amd.dataset import iterator as it
+    from dspnet_amd.dataset import jpeg as dj
+    dev = torch.device("cuda", 0)
+    B = 32
+    intervals = [int(v) for v in args.intervals.split(",")]
+    refused = [v for v in intervals if v > dj.DEVICE_MAX_INTERVAL]
+    if refused:                                                 # the rows at 128 and 512 of the profile were taken with the constant at 512
+        print("intervals %s are above DSPN_JPEG_DEVICE_MAX_INTERVAL = %d: such streams stay on the host pass, left out" %
+              (refused, dj.DEVICE_MAX_INTERVAL))
+        intervals = [v for v in intervals if v <= dj.DEVICE_MAX_INTERVAL]
+    pictures = [picture(2000 + i) for i in range(8)]
+    print("device entropy pass, B = %d streams (8 distinct) of %d x %d 4:2:0; host yardstick: dspn_jpeg_entropy_decode of the same "
+          "batch on a pool of 16 threads (%d CPUs visible)" % (B, H, W, os.cpu_count()))
+    for quality in (92, 75):
+        plain = [jpeg_bytes(p, quality) for p in pictures]
+        for interval in intervals:
+            streams = [jpeg_bytes(p, quality, interval) for p in pictures]
+            growth = sum(map(len, streams)) / sum(map(len, plain)) - 1
+            payloads = [streams[b % 8] for b in range(B)]
+            infos = [dj.probe_info(s)[1] for s in payloads]
+            sizes = [H * W * 3] * B
+            batch = dj.CodedBatch(infos, np.cumsum([0] + sizes[:-1]), True)
+            t0 = time.perf_counter()
+            assert all(index(p) for p, index in zip(payloads, batch.indexers()))
+            t_index = (time.perf_counter() - t0) / B
+            batch.answered([True] * B)
+            assert batch.device_entropy == B and batch.host_count == 0
+            pool = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+            batch.upload(torch.empty(1, dtype=torch.int16), dev)
+            keep = batch.launch(pool)
+            torch.cuda.synchronize(dev)
+            batch.check()
+            assert (pool[:sizes[0]].view(H, W, 3).cpu().numpy() == pillow_decode(payloads[0])).all(), "pixels differ from Pillow's"
+            desc_dev, scan_dev, status = keep[1], keep[2], keep[3]
+            a, b = B * dj.SAMPLE.itemsize, B * (dj.SAMPLE.itemsize + dj.SCAN.itemsize)
+            coef_dev = keep[0]
+
+            def launch():
+                dj.entropy_decode_device(scan_dev, desc_dev[:a], desc_dev[a:b], desc_dev[b:].view(torch.int32), coef_dev, status)
+
+            for _ in range(3):
+                launch()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(11)]
+            ev[0].record()
+            for k in range(10):
+                launch(); ev[k + 1].record()
+            torch.cuda.synchronize(dev)
+            t_dev = np.median([ev[k].elapsed_time(ev[k + 1]) for k in range(10)])
+            # the host pass of the same batch, 16 threads, the parent commit's code path
+            bufs = [np.empty(int(i["coef_count"]), np.int16) for i in infos]
+            with ThreadPoolExecutor(16) as tp:
+                walls = []
+                for _ in range(4):
+                    t0 = time.perf_counter()
+                    assert not any(tp.map(lambda k: dj.entropy_decode(payloads[k], infos[k], bufs[k]), range(B)))
+                    walls.append(time.perf_counter() - t0)
+            up_dev = batch.scan_bytes + desc_dev.numel()
+            up_host = 2 * sum(int(i["coef_count"]) for i in infos) + a
+            print("  quality %d, interval %3d MCUs: %5d segments/image, file +%.2f %% (mean %.0f KB); device entropy launch %.3f ms per batch "
+                  "(median of 10, device events), host pass on 16 threads %.1f ms per batch (best of 4; runs %s), scan index %.3f ms/image on "
+                  "one thread; upload %.2f MB per batch against %.2f MB of coefficients" %
+                  (quality, interval, int(batch.scans[0]["segments"]), 100 * growth, np.mean([len(s) for s in streams]) / 1e3, t_dev,
+                   min(walls) * 1e3, ["%.1f" % (w * 1e3) for w in walls], t_index * 1e3, up_dev / 1e6, up_host / 1e6))
+            del keep, pool
+    n = args.records
+    print("MultiTaskRecordIter, B = %d, data shape (3, 512, 1024), device_jpeg=True, %d records per file (16 distinct pictures, quality 92), %d timed batches, "
+          "device_entropy off and on alternated, two runs each" % (B, n, args.batches))
+    for interval in intervals:
+        path = _write_records(os.path.join(args.workdir, "ri%d" % interval), n, interval, distinct=16)
+        for threads in (8, 16):
+            rates = {False: [], True: []}
+            for run in range(2):
+                for on in (False, True):
+                    itr = it.MultiTaskRecordIter(path, B, (3, 512, 1024), device=dev, decode_threads=threads, device_jpeg=True,
+                                                 device_entropy=on)
+                    torch.cuda.synchronize(dev)
+                    done, t0 = 0, time.perf_counter()
+                    while done < args.batches:
+                        if not itr.iter_next():
+                            itr.reset()
+                        itr.next()
+                        done += 1
+                    torch.cuda.synchronize(dev)
+                    rates[on].append(done / (time.perf_counter() - t0))
+                    counted = itr.jpeg_device_entropy
+                    itr._drop_ahead()
+                    del itr
+            off, on_ = np.mean(rates[False]), np.mean(rates[True])
+            print("  interval %3d, decode_threads %2d: device_entropy off %.2f batches/s (runs %s), on %.2f batches/s (runs %s), ratio %.2f, "
+                  "%d records through the device pass in the last run" % (interval, threads, off, ["%.2f" % r for r in rates[False]], on_,
+                                                                         ["%.2f" % r for r in rates[True]], on_ / off, counted))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["host", "device", "iterator"])
+    ap.add_argument("what", choices=["host", "device", "iterator", "entropy"])
     ap.add_argument("--images", type=int, default=24)
     ap.add_argument("--records", type=int, default=128)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--intervals", default="8,16,32", help="entropy: restart intervals in MCUs")
     a = ap.parse_args()
-    if a.what == "iterator" and not a.workdir:
+    if a.what in ("iterator", "entropy") and not a.workdir:
         import tempfile
         a.workdir = tempfile.mkdtemp(prefix="jpeg_measure_")
-    {"host": host, "device": device, "iterator": iterator}[a.what](a)
+    {"host": host, "device": device, "iterator": iterator, "entropy": entropy}[a.what](a)
