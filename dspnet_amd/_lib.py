@@ -7,38 +7,25 @@ raises immediately.
 import ctypes
 import os
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DSPN_LIB: another build of the SAME library (A/B timing of two builds on one box); never a fallback
 LIB_PATH = os.environ.get("DSPN_LIB") or os.path.join(_HERE, "libdspn_hip.so")
 
-_c = ctypes
-_f32p = _c.POINTER(_c.c_float)
-_vp = _c.c_void_p
+# include/*.h is the one place the C ABI is written: name -> (restype, [argtypes]) of every entry point (a pointer or array
+# argument is c_void_p), name -> ctypes.Structure of every descriptor struct, name -> value of every integer-literal #define
+SIGNATURES, STRUCTS, DEFINES = _abi.parse()
 
-# name -> (restype, argtypes); mirrors include/dspn_multibox.h and include/dspn_nn.h
-SIGNATURES = {
-    "dspn_last_error": (_c.c_char_p, []),
-    "dspn_abi_version": (_c.c_int, []),
-    "dspn_profile_enable": (_c.c_int, [_c.c_int]),
-    "dspn_conv_set_reserved_cus": (_c.c_int, [_c.c_int]),
-    "dspn_conv_set_wide_tiles": (_c.c_int, [_c.c_int]),
-    "dspn_conv_set_tile_spanning": (_c.c_int, [_c.c_int]),
-    "dspn_affine_sampler_set_batched": (_c.c_int, [_c.c_int]),
-    "dspn_profile_collect": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_longlong)]),
-    "dspn_multibox_prior_f32": (_c.c_int, [_f32p, _c.c_int, _f32p, _c.c_int, _c.c_int, _c.c_int,
-                                           _c.c_float, _c.c_float, _c.c_float, _c.c_float,
-                                           _c.c_int, _vp, _vp]),
-    "dspn_multibox_target_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
-    "dspn_multibox_target_f32": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                            _c.c_int, _c.c_float, _c.c_float, _c.c_float,
-                                            _c.c_float, _c.c_int, _f32p, _vp, _vp, _vp, _vp,
-                                            _c.c_size_t, _vp]),
-    "dspn_multibox_target_errors": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_int), _vp]),
-    "dspn_multibox_detection_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
-    "dspn_multibox_detection_f32": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int,
-                                               _c.c_float, _c.c_int, _f32p, _c.c_float, _c.c_int,
-                                               _c.c_int, _vp, _vp, _c.c_size_t, _vp]),
-}
+
+def layout(struct_name):
+    """the numpy dtype of a descriptor struct of include/*.h"""
+    return _abi.dtype_of(STRUCTS[struct_name])
+
+
+def field_list(struct_name):
+    """the same as a numpy field list (a struct without padding)"""
+    return _abi.fields_of(STRUCTS[struct_name])
 
 
 class DspnError(RuntimeError):
@@ -46,13 +33,6 @@ class DspnError(RuntimeError):
 
 
 _lib = None
-
-
-def register(signatures):
-    """Used by sibling modules to add the signatures of further include/*.h files."""
-    SIGNATURES.update(signatures)
-    if _lib is not None:
-        _bind(_lib, signatures)
 
 
 def _bind(lib, signatures):
@@ -88,5 +68,5 @@ def check(status, what=""):
 
 
 def floats(values):
-    arr = (_c.c_float * len(values))(*[float(v) for v in values])
+    arr = (ctypes.c_float * len(values))(*[float(v) for v in values])
     return arr

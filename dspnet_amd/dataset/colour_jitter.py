@@ -13,7 +13,6 @@ them; PARITY STATUS: unpinned).
 DetIter(color_jitter=..., jitter_seed=...) and MultiTaskRecordIter(color_jitter=..., jitter_seed=...) draw from a
 private RandomState, so the streams that drive their geometry are the same with the feature on or off."""
 import collections
-import ctypes as _c
 
 import numpy as np
 import torch
@@ -26,14 +25,9 @@ ColorJitter = collections.namedtuple("ColorJitter", [
     "random_illumination_prob", "max_random_illumination", "random_contrast_prob", "max_random_contrast"])
 ColorJitter.__new__.__defaults__ = (0.0, 18, 0.0, 32, 0.0, 32, 0.0, 0.5)
 
-# dspn_jitter_sample (include/dspn_colour_jitter.h)
-SAMPLE = np.dtype([("img_offset", "<i8"), ("height", "<i4"), ("width", "<i4"), ("dh", "<i4"), ("dl", "<i4"), ("ds", "<i4"),
-                   ("gain", "<i4")])
-assert SAMPLE.itemsize == 32
+SAMPLE = _lib.layout("dspn_jitter_sample")                     # include/dspn_colour_jitter.h
 UNIT_GAIN = 1024
 IDENTITY = (0, 0, 0, UNIT_GAIN)
-
-_lib.register({"dspn_colour_jitter_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p])})
 
 
 def _checked(cfg):

@@ -40,7 +40,6 @@ import torch
 from .. import _lib
 from ..detect.render import nearest_tables
 from . import colour_jitter
-from . import iterator as _iterator  # noqa: F401  (registers dspn_det_augment_batch_u8 beside dspn_augment_batch_u8)
 from . import jpeg
 from . import png
 from .im2rec import read_list
@@ -55,11 +54,7 @@ COEF_BITS = 11                                                 # coefficients ar
 _ONE = 1 << COEF_BITS
 _FLT_EPSILON = 1.1920928955078125e-07
 
-# dspn_det_sample (include/dspn_det_augment.h)
-SAMPLE = np.dtype([("img_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("x0", "<i4"), ("y0", "<i4"),
-                   ("canvas_h", "<i4"), ("canvas_w", "<i4"), ("fill", "<i4"), ("mirror", "<i4"), ("kx", "<i4"),
-                   ("ky", "<i4"), ("xtab", "<i4"), ("ytab", "<i4")])
-assert SAMPLE.itemsize == 56
+SAMPLE = _lib.layout("dspn_det_sample")                        # include/dspn_det_augment.h
 FILL = 128                                                     # :277
 
 

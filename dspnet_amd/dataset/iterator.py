@@ -38,20 +38,9 @@ from . import png
 from . import recordio
 from .staging import Decoded, HostPools
 
-# dspn_warp_sample (include/dspn_augment.h)
-_SAMPLE = np.dtype([("img_offset", "<i8"), ("seg_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("flip", "<i4"),
-                    ("img_border", "<i4"), ("seg_border", "<i4"), ("reserved", "<i4"), ("minv", "<f8", (6,))])
-assert _SAMPLE.itemsize == 88
+_SAMPLE = _lib.layout("dspn_warp_sample")                       # include/dspn_augment.h
 _CMAP_BGR = (_c.c_int * 3)(2, 1, 0)                             # BGR source -> R, G, B planes (:568-569)
 _CMAP_RGB = (_c.c_int * 3)(0, 1, 2)                             # Pillow decodes to RGB: identity
-
-
-_lib.register({"dspn_augment_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
-                                                     _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.c_void_p,
-                                                     _c.c_void_p, _c.c_void_p, _c.c_void_p]),
-               # include/dspn_det_augment.h (dataset/det_iterator.py is its front end)
-               "dspn_det_augment_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
-                                                         _c.POINTER(_c.c_double), _c.c_void_p, _c.c_void_p])})
 
 
 def _entry():

@@ -19,23 +19,10 @@ import torch
 from .. import _lib
 from . import staging
 
-# dspn_jpeg_info / dspn_jpeg_sample (include/dspn_jpeg.h)
-INFO = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("restart_interval", "<i4"),
-                 ("hsamp", "<i4", (3,)), ("vsamp", "<i4", (3,)), ("blocks_w", "<i4", (3,)), ("blocks_h", "<i4", (3,)),
-                 ("supported", "<i4"), ("reason", "<i4"), ("coef_count", "<i8"), ("coef_offset", "<i8", (3,)),
-                 ("quant", "u1", (3, 64))])
-assert INFO.itemsize == 296
-SAMPLE = np.dtype([("coef_offset", "<i8", (3,)), ("img_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
-                   ("ncomp", "<i4"), ("skip", "<i4"), ("hsamp", "<i4"), ("vsamp", "<i4"), ("blocks_w", "<i4", (3,)),
-                   ("blocks_h", "<i4", (3,)), ("quant", "u1", (3, 64))])
-assert SAMPLE.itemsize == 272
-# dspn_jpeg_scan: the device entropy pass's descriptor of a stream with restart intervals
-SCAN = np.dtype([("data_offset", "<i8"), ("data_bytes", "<i8"), ("first_segment", "<i8"), ("segments", "<i4"),
-                 ("restart_interval", "<i4"), ("mcus_w", "<i4"), ("mcus_h", "<i4"), ("dc_table", "u1", (4,)),
-                 ("ac_table", "u1", (4,)), ("dc_counts", "u1", (4, 16)), ("ac_counts", "u1", (4, 16)),
-                 ("dc_values", "u1", (4, 256)), ("ac_values", "u1", (4, 256))])
-assert SCAN.itemsize == 2224
-DEVICE_MAX_INTERVAL = 32                                       # DSPN_JPEG_DEVICE_MAX_INTERVAL
+INFO = _lib.layout("dspn_jpeg_info")                           # include/dspn_jpeg.h
+SAMPLE = _lib.layout("dspn_jpeg_sample")
+SCAN = _lib.layout("dspn_jpeg_scan")                           # the device entropy pass's descriptor of a stream with restart intervals
+DEVICE_MAX_INTERVAL = _lib.DEFINES["DSPN_JPEG_DEVICE_MAX_INTERVAL"]
 STATUS_SEGMENTS = (1 << 27) - 1                                # DSPN_JPEG_STATUS_SEGMENTS
 STATUS_CODES = ("ok", "a Huffman code that is not in its table", "a coefficient index past 63",
                 "a DC difference of more than 11 bits or an AC value of more than 10", "data that ends inside a block",
@@ -45,28 +32,6 @@ REASONS = ("ok", "progressive", "extended sequential", "arithmetic coding", "los
            "sample precision is not 8 bits", "neither 1 nor 3 components", "unsupported sampling factors",
            "more than one scan", "colour transform is not YCbCr", "16-bit quantisation table")
 MAX_BATCH = 1024                                               # kMaxB of csrc/jpeg.hip: descriptors of one reconstruct call
-
-_lib.register({
-    "dspn_jpeg_probe": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
-    "dspn_jpeg_entropy_decode": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
-    "dspn_jpeg_reconstruct_workspace_bytes": (_c.c_size_t, [_c.c_longlong]),
-    "dspn_jpeg_reconstruct_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p,
-                                                  _c.c_longlong, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
-    "dspn_jpeg_scan_segments": (_c.c_longlong, [_c.c_void_p]),
-    "dspn_jpeg_scan_index": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t]),
-    "dspn_jpeg_entropy_decode_batch": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
-                                                  _c.c_longlong, _c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_void_p]),
-    "dspn_jpeg_entropy_decode_segments": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                                     _c.c_longlong, _c.c_void_p, _c.c_longlong, _c.c_void_p]),
-    # include/dspn_jpeg_encode.h (dataset/jpeg_encode.py is its front end)
-    "dspn_jpeg_quant_tables": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p]),
-    "dspn_jpeg_encode_geometry": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p]),
-    "dspn_jpeg_encode_workspace_bytes": (_c.c_size_t, [_c.c_longlong]),
-    "dspn_jpeg_encode_blocks_batch_u8": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
-                                                    _c.c_longlong, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
-    "dspn_jpeg_entropy_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
-    "dspn_jpeg_entropy_encode_restart": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
-})
 
 
 def probe_info(payload):

@@ -13,13 +13,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import jpeg as _dj  # noqa: F401                       registers the signatures of include/dspn_jpeg_encode.h
 
-# dspn_jpeg_enc_sample (include/dspn_jpeg_encode.h)
-SAMPLE = np.dtype([("coef_offset", "<i8", (3,)), ("img_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
-                   ("ncomp", "<i4"), ("skip", "<i4"), ("hsamp", "<i4"), ("vsamp", "<i4"), ("blocks_w", "<i4", (3,)),
-                   ("blocks_h", "<i4", (3,)), ("quant", "u1", (3, 64))])
-assert SAMPLE.itemsize == 272
+SAMPLE = _lib.layout("dspn_jpeg_enc_sample")                  # include/dspn_jpeg_encode.h
 SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}      # luma sampling, h x v
 CHANNEL_ORDER = {"rgb": (0, 1, 2), "bgr": (2, 1, 0)}                   # where R, G and B sit in a pixel
 MAX_SIDE = 65500                                                       # libjpeg's, and so Pillow's

@@ -14,7 +14,6 @@ non-interlaced format but 16-bit greyscale (which convert("RGB") clips; it stays
 grey + alpha at 8 and 16 bits, greyscale and palette at 1, 2, 4 and 8 bits, with or without tRNS (convert("RGB") ignores
 it).  The device reconstructs the rows at the format's stride and then makes the RGB bytes (dspn_png_rgb_batch).
 im2rec's `_decode` uses `decode_rgb_batch`; DetIter(device_png=True) goes through `open_rgb`, `decode_rgb` and `RgbBatch`."""
-import ctypes as _c
 import io
 import struct
 import zlib
@@ -25,18 +24,12 @@ import torch
 from .. import _lib
 from . import staging
 
-# dspn_png_sample (include/dspn_png.h)
-SAMPLE = np.dtype([("raw_offset", "<i8"), ("out_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
-                   ("bytes_per_pixel", "<i4"), ("skip", "<i4")])
-assert SAMPLE.itemsize == 32
+SAMPLE = _lib.layout("dspn_png_sample")                        # include/dspn_png.h
 REASONS = ("ok", "bit depth below 8", "colour type is RGB, RGBA or grey + alpha", "Adam7 interlace", "tRNS chunk",
            "acTL chunk (APNG)", "not a bit depth / colour type / method of the PNG specification")
 OK, LOW_DEPTH, COLOUR, INTERLACE, TRNS, APNG, NONSTANDARD = range(7)
-# dspn_png_rgb_sample
-RGB_SAMPLE = np.dtype([("raw_offset", "<i8"), ("recon_offset", "<i8"), ("out_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
-                       ("bit_depth", "<i4"), ("colour_type", "<i4"), ("palette_index", "<i4"), ("skip", "<i4")])
-assert RGB_SAMPLE.itemsize == 48
-PALETTE_BYTES = 768
+RGB_SAMPLE = _lib.layout("dspn_png_rgb_sample")
+PALETTE_BYTES = _lib.DEFINES["DSPN_PNG_PALETTE_BYTES"]
 # probe_rgb's reasons (REASONS above is probe's alone)
 RGB_REASONS = ("ok", "16-bit greyscale (convert(\"RGB\") clips it; decode_batch keeps the 16 bits)", "Adam7 interlace",
                "acTL chunk (APNG)", "not a bit depth / colour type / method of the PNG specification",
@@ -48,19 +41,6 @@ _CRITICAL = (b"IHDR", b"PLTE", b"IDAT", b"IEND")
 _DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}      # colour type -> legal bit depths
 # inflate_into's statuses
 INFLATE_OK, INFLATE_ZLIB, INFLATE_LENGTH, INFLATE_FILTER = 0, 1, 2, 3
-
-_lib.register({
-    "dspn_png_unfilter_batch": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_longlong,
-                                           _c.c_void_p]),
-    # include/dspn_png_encode.h (dataset/png_encode.py is its front end)
-    "dspn_png_filtered_bytes": (_c.c_longlong, [_c.c_int, _c.c_int, _c.c_int]),
-    "dspn_png_filter_workspace_bytes": (_c.c_size_t, [_c.c_int]),
-    "dspn_png_filter_batch": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_longlong,
-                                         _c.c_void_p, _c.c_size_t, _c.c_void_p]),
-    "dspn_png_rgb_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int]),
-    "dspn_png_rgb_batch": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
-                                      _c.c_longlong, _c.c_void_p, _c.c_longlong, _c.c_void_p]),
-})
 
 
 def _malformed(what):

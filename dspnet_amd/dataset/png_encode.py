@@ -15,12 +15,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import png as _dp                                      # registers the signatures of include/dspn_png_encode.h
+from . import png as _dp
 
-# dspn_png_enc_sample (include/dspn_png_encode.h)
-SAMPLE = np.dtype([("src_offset", "<i8"), ("out_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
-                   ("bytes_per_pixel", "<i4"), ("src_pitch", "<i4")])
-assert SAMPLE.itemsize == 32
+SAMPLE = _lib.layout("dspn_png_enc_sample")                   # include/dspn_png_encode.h
 MAX_ROW_BYTES = (1 << 24) - 1                                 # DSPN_PNG_ENC_MAX_ROW_BYTES
 FORMATS = {1: (8, 0), 2: (16, 0), 3: (8, 2)}                  # bytes per pixel -> IHDR bit depth, colour type
 _THREADS = 8                                                  # jpeg_encode.encode_batch's default

@@ -6,20 +6,10 @@ Same callables -- `nms(dets, thresh)`, `cpu_nms`, `gpu_nms` and the three `*_wra
 descending score order, like the reference.  `nms` / `gpu_nms` drop a box whose overlap with a kept one is
 > thresh (detect/nms.py:55, cython/nms_kernel.cu:68), `cpu_nms` when it is >= thresh (cython/cpu_nms.pyx:65).
 `bbox_overlaps` / `bbox_overlaps_cython`: the (N, K) float64 overlap matrix of cython/bbox.pyx:15-55."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
-
-_c = ctypes
-_lib.register({
-    "dspn_nms_pixel_workspace_bytes": (_c.c_size_t, [_c.c_int]),
-    "dspn_nms_pixel_f32": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p,
-                                      _c.c_void_p, _c.c_size_t, _c.c_void_p]),
-    "dspn_bbox_overlaps_f64": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
-})
 
 
 def bbox_overlaps(boxes, query_boxes, device=None):

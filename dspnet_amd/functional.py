@@ -14,176 +14,10 @@ from . import _lib
 from ._lib import check
 
 _c = ctypes
-_vp = _c.c_void_p
-_i = _c.c_int
-_ll = _c.c_longlong
-_f = _c.c_float
-_sz = _c.c_size_t
+_D = _lib.DEFINES                   # the integer-literal #defines of include/*.h
 
-# the dspn_conv2d_dgrad_bn* entries: operands, N .. accumulate | the BatchNorm operands, math and its blocks, the workspace
-_dgrad_head = [_vp] * 4 + [_i] * 15
-_dgrad_bn = _dgrad_head + [_vp] * 5 + [_i, _vp, _sz, _vp] + [_i, _vp, _vp] + [_vp, _sz]
-_lib.register({
-    "dspn_conv2d_split_workspace_bytes": (_sz, [_ll, _i]),
-    "dspn_conv2d_forward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                     _ll, _i, _i, _i, _vp, _sz, _vp]),
-    "dspn_conv2d_forward_bn_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                        _i, _ll, _i, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_absmax_f32": (_i, [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp]),
-    "dspn_absmax_batch_f32": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_conv2d_weight_planes_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "dspn_conv2d_weight_planes_tiles": (_ll, [_i, _i, _i, _i, _i]),
-    "dspn_conv2d_weight_planes_batch_f32": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_conv2d_stats_layout": (_i, [_ll, _i, _c.POINTER(_c.c_int)]),
-    "dspn_bn_stats_from_tiles_f32": (_i, [_vp, _i, _i, _ll, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_bn_tiles_workspace_bytes": (_sz, [_i, _i]),
-    "dspn_conv2d_wgrad_bn_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                      _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_conv2d_wgrad_splits": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "dspn_conv2d_wgrad_slabs_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                         _i, _i, _i, _vp, _vp, _vp]),
-    "dspn_conv2d_slab_reduce_batch_f32": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_conv2d_weight_transpose_batch_f32": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_conv2d_weight_transpose_tiles": (_ll, [_i, _i, _i, _i]),
-    "dspn_conv2d_weight_transpose_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "dspn_conv2d_dgrad_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
-                                   _sz, _vp]),
-    "dspn_conv2d_dgrad_bn_tiles": (_i, [_i, _i, _i, _i, _i]),
-    "dspn_conv2d_dgrad_bn_f32": (_i, _dgrad_bn + [_vp]),
-    "dspn_conv2d_dgrad_bn_sadd_f32": (_i, _dgrad_bn + [_vp, _i, _i, _vp]),      # ... the addend and its extent, stream
-    "dspn_conv2d_dgrad_bn_sadd_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
-    "dspn_conv2d_dgrad_bn_sums_f32": (_i, _dgrad_bn + [_vp]),
-    "dspn_conv2d_dgrad_bn_apply_f32": (_i, _dgrad_head + [_vp, _vp, _vp, _i, _vp] + [_i, _vp, _vp] + [_vp, _sz, _vp]),
-    "dspn_conv2d_dgrad_bn_recompute_route_f32": (_i, [_i, _i, _i, _i, _i, _i]),
-    "dspn_bn_backward_from_sums_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _i, _i, _i,
-                                            _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "dspn_bn_discard_parked": (_i, [_vp]),
-    "dspn_absmin_rows_batch_f32": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_tile_minmax_f32": (_i, [_vp, _ll, _i, _i, _vp, _vp]),
-    "dspn_conv2d_input_sum_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "dspn_conv2d_input_sum_grad_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                            _vp, _sz, _vp]),
-    "dspn_conv2d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
-    "dspn_conv2d_wgrad_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                   _vp, _sz, _vp]),
-    "dspn_bn_workspace_bytes": (_sz, [_ll, _i]),
-    "dspn_bn_stats_f32": (_i, [_vp, _ll, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_bn_apply_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
-    "dspn_bn_apply_planes_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
-    "dspn_absmax_affine_bound_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
-    "dspn_bn_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _sz,
-                                  _vp]),
-    "dspn_bn_backward_ex_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _sz,
-                                     _vp, _i]),
-    "dspn_add_f32": (_i, [_vp, _vp, _vp, _ll, _vp]),
-    "dspn_relu_backward_f32": (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
-    "dspn_fill_f32": (_i, [_vp, _f, _ll, _vp]),
-    "dspn_relu_backward_colsum_f32": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "dspn_colsum_workspace_bytes": (_sz, [_ll, _i]),
-    "dspn_colsum_f32": (_i, [_vp, _ll, _i, _i, _vp, _vp, _sz, _vp]),
-    "dspn_nchw_to_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "dspn_nhwc_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "dspn_copy_block_f32": (_i, [_vp, _vp, _i, _ll, _i, _ll, _i, _i, _ll, _i, _i, _i, _vp]),
-    "dspn_copy_block_batch_f32": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_transpose_bnc_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "dspn_avgpool2d_forward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_avgpool2d_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_bilinear_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "dspn_bilinear_backward_ws_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "dspn_seg_counts_f32": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
-    "dspn_seg_upsample_argmax_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_cityscapes_counts_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "dspn_cityscapes_counts_prob_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "dspn_tap_sum_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_tap_spread_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_maxpool_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_maxpool_forward_bn_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "dspn_maxpool_backward_argmax_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_bn_backward_maxpool_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _i, _vp, _vp, _sz, _vp]),
-    "dspn_bn_backward_maxpool_ex_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                             _vp, _i, _vp, _vp, _sz, _vp, _i]),
-    "dspn_maxpool_backward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_avgpool_forward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_avgpool_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_bilinear_forward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_bilinear_forward_acc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_bilinear_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_affine_sampler_forward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "dspn_affine_sampler_backward_data_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "dspn_affine_sampler_theta_workspace_bytes": (_sz, [_i, _i, _i]),
-    "dspn_affine_sampler_backward_theta_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i,
-                                                    _vp, _sz, _vp]),
-    "dspn_affine_sampler_backward_data_theta_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp,
-                                                         _vp, _sz, _vp]),
-    "dspn_affine_sampler_theta_rows": (_ll, [_i, _i, _i, _i]),
-    "dspn_affine_sampler_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "dspn_affine_sampler_theta_reduce_workspace_bytes": (_sz, [_ll]),
-    "dspn_affine_sampler_theta_reduce": (_i, [_vp, _ll, _vp, _i, _vp, _sz, _vp]),
-    "dspn_softmax_output_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _f, _f, _vp, _vp]),
-    "dspn_count_f32": (_i, [_vp, _ll, _i, _f, _vp, _vp]),
-    "dspn_smooth_l1_forward_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _vp]),
-    "dspn_smooth_l1_backward_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _vp, _vp]),
-    "dspn_cross_entropy_sum_f32": (_i, [_vp, _vp, _ll, _i, _i, _f, _f, _vp, _vp]),
-    "dspn_sum_f32": (_i, [_vp, _ll, _vp, _vp]),
-    "dspn_sgd_momentum_f32": (_i, [_vp, _vp, _vp, _ll, _f, _f, _f, _f, _vp]),
-    "dspn_sgd_momentum_segments_f32": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _f, _f, _f, _f, _vp]),
-})
-
-
-# the bfloat16-tensor twins (include/dspn_nn.h): same argument lists as the *_f32 entries
-for _name in ("dspn_conv2d_forward_bn", "dspn_conv2d_dgrad_bn", "dspn_conv2d_dgrad_bn_sadd", "dspn_conv2d_dgrad_bn_sums",
-              "dspn_conv2d_dgrad_bn_apply", "dspn_conv2d_wgrad_bn", "dspn_conv2d_wgrad_slabs",
-              "dspn_conv2d_input_sum_grad", "dspn_bn_stats", "dspn_bn_apply", "dspn_bn_backward", "dspn_bn_backward_ex",
-              "dspn_bn_backward_from_sums", "dspn_add", "dspn_relu_backward", "dspn_relu_backward_colsum", "dspn_colsum",
-              "dspn_nchw_to_nhwc", "dspn_copy_block", "dspn_tap_sum", "dspn_tap_spread", "dspn_maxpool_forward", "dspn_maxpool_forward_bn",
-              "dspn_maxpool_backward_argmax", "dspn_maxpool_backward", "dspn_avgpool_forward", "dspn_avgpool_backward",
-              "dspn_avgpool2d_forward", "dspn_avgpool2d_backward", "dspn_softmax_output", "dspn_affine_sampler_forward",
-              "dspn_affine_sampler_backward_data", "dspn_affine_sampler_backward_theta",
-              "dspn_affine_sampler_backward_data_theta"):
-    _lib.register({_name + "_bf16": _lib.SIGNATURES[_name + "_f32"]})
-_lib.register({
-    "dspn_conv2d_weight_prepare_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "dspn_conv2d_weight_prepare_batch_bf16": (_i, [_vp, _i, _ll, _vp]),
-    "dspn_copy_block_bf16_f32": _lib.SIGNATURES["dspn_copy_block_f32"],
-    "dspn_copy_block_f32_bf16": _lib.SIGNATURES["dspn_copy_block_f32"],
-})
-# include/dspn_distance.h
-_lib.register({
-    "dspn_box_rank_select_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "dspn_box_rank_select_u16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "dspn_distance_boxes_workspace_bytes": (_sz, [_i]),
-    "dspn_distance_boxes_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-})
-# include/dspn_monitor.h
-_lib.register({
-    "dspn_tensor_stats_chunk_elems": (_i, []),
-    "dspn_tensor_stats_workspace_bytes": (_sz, [_i, _ll]),
-    "dspn_tensor_stats": (_i, [_vp, _i, _ll, _vp, _vp, _sz, _vp]),
-})
-# include/dspn_render.h
-_lib.register({
-    "dspn_render_chunk_rows": (_i, []),
-    "dspn_render_classmap_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
-    "dspn_render_labels_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
-    "dspn_render_data_f32": (_i, [_vp, _i, _i, _i, _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _vp, _i, _i, _i, _i, _vp]),
-    "dspn_render_check_draw_rows": (_i, [_vp, _i, _vp, _i]),
-    "dspn_render_draw_list_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
-})
-
-
-class BnMoving(_c.Structure):
-    """include/dspn_nn.h dspn_bn_moving: the moving-statistics block of the `_ex` BatchNorm finalize entry points"""
-    _fields_ = [("moving_mean", _vp), ("moving_var", _vp), ("momentum", _f), ("mode", _i), ("channels", _i)]
-
-
-BN_TRACK, BN_GLOBAL = 1, 2      # DSPN_BN_TRACK / DSPN_BN_GLOBAL
-_bnmp = _c.POINTER(BnMoving)
-_lib.register({
-    "dspn_bn_stats_ex_f32": (_i, _lib.SIGNATURES["dspn_bn_stats_f32"][1][:-1] + [_bnmp, _vp]),
-    "dspn_bn_stats_ex_bf16": (_i, _lib.SIGNATURES["dspn_bn_stats_f32"][1][:-1] + [_bnmp, _vp]),
-    "dspn_bn_stats_from_tiles_ex_f32": (_i, _lib.SIGNATURES["dspn_bn_stats_from_tiles_f32"][1][:-1] + [_bnmp, _vp]),
-})
+BnMoving = _lib.STRUCTS["dspn_bn_moving"]      # the moving-statistics block of the `_ex` BatchNorm finalize entry points
+BN_TRACK, BN_GLOBAL = _D["DSPN_BN_TRACK"], _D["DSPN_BN_GLOBAL"]
 
 
 def bn_moving(moving_mean, moving_var, momentum, mode, channels=0):
@@ -295,7 +129,8 @@ def act_empty(*shape, device=None):
 
 
 # ------------------------------------------------------------------ convolution
-_MATH_CODES = {"fp32": 0, "f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3}      # include/dspn_nn.h DSPN_MATH_*
+_MATH_CODES = {"fp32": _D["DSPN_MATH_FP32"], "f32": _D["DSPN_MATH_FP32"], "bf16": _D["DSPN_MATH_BF16"],
+               "bf16x3": _D["DSPN_MATH_F32_BF16X3"], "f16x2": _D["DSPN_MATH_F32_F16X2"]}
 # this module's default for the `math` argument it passes on every convolution call (float tensors); DSPN_CONV_MATH
 # overrides it for a whole process (the test suite is run once per mode)
 DEFAULT_CONV_MATH = os.environ.get("DSPN_CONV_MATH", "f16x2")
@@ -346,7 +181,7 @@ def bn_stats_from_tiles(tile_stats, tiles, tile_rows, rows, C, eps, gamma, beta,
         check(L().dspn_bn_stats_from_tiles_ex_f32(*args, moving, stream()), "bn_stats_from_tiles_ex")
 
 
-ABSMAX_SLOTS = 64      # include/dspn_nn.h DSPN_ABSMAX_SLOTS: a magnitude is 64 partial maxima
+ABSMAX_SLOTS = _D["DSPN_ABSMAX_SLOTS"]      # a magnitude is 64 partial maxima
 
 
 def absmax(x, in_affine=None, out=None):
@@ -570,10 +405,10 @@ def conv_dgrad_bn_tiles(x_shape, stride):
     return L().dspn_conv2d_dgrad_bn_tiles(N, H, W, C, stride)
 
 
-MATH_DY_PLANES = 0x200       # include/dspn_nn.h DSPN_MATH_DY_PLANES
-MATH_X_PLANES = 0x400        # include/dspn_nn.h DSPN_MATH_X_PLANES
+MATH_DY_PLANES, MATH_X_PLANES = _D["DSPN_MATH_DY_PLANES"], _D["DSPN_MATH_X_PLANES"]
 # the flag word of dspn_bn_backward_from_sums_* (include/dspn_nn.h DSPN_BN_SUMS_*)
-BN_SUMS_PLANES, BN_SUMS_FINALIZE_ONLY, BN_SUMS_APPLY_ONLY, BN_SUMS_PARKED, BN_SUMS_FIXED_STATS = 1, 2, 4, 8, 16
+BN_SUMS_PLANES, BN_SUMS_FINALIZE_ONLY, BN_SUMS_APPLY_ONLY, BN_SUMS_PARKED, BN_SUMS_FIXED_STATS = (
+    _D["DSPN_BN_SUMS_" + _k] for _k in ("PLANES", "FINALIZE_ONLY", "APPLY_ONLY", "PARKED", "FIXED_STATS"))
 
 
 def conv2d_dgrad_addend_route(x_shape, ldy, dy_planes):
@@ -1224,7 +1059,8 @@ def seg_upsample_argmax(prob, C, Ho, Wo):
 
 
 # include/dspn_nn.h DSPN_CITYSCAPES_*: labelIds of the confusion matrix, and the dense per-image instance table
-CITYSCAPES_LABELS, CITYSCAPES_INST_LABEL0, CITYSCAPES_INST_LABELS, CITYSCAPES_INST_PER_LABEL = 34, 24, 10, 1000
+CITYSCAPES_LABELS, CITYSCAPES_INST_LABEL0, CITYSCAPES_INST_LABELS, CITYSCAPES_INST_PER_LABEL = (
+    _D["DSPN_CITYSCAPES_" + _k] for _k in ("LABELS", "INST_LABEL0", "INST_LABELS", "INST_PER_LABEL"))
 
 
 def cityscapes_tables(n_images, device):
@@ -1318,10 +1154,9 @@ def check_box_count(count, max_boxes):
 
 # ------------------------------------------------------------------ display images (include/dspn_render.h)
 # dspn_draw_row: nine int32
-DRAW_ROW_FIELDS = [("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("r", "<i4"), ("g", "<i4"),
-                   ("b", "<i4"), ("arg", "<i4")]
-DRAW_OUTLINE, DRAW_FILL, DRAW_GLYPH = 0, 1, 2      # DSPN_DRAW_*
-RENDER_FONT_BYTES = 665                            # DSPN_RENDER_FONT_BYTES
+DRAW_ROW_FIELDS = _lib.field_list("dspn_draw_row")
+DRAW_OUTLINE, DRAW_FILL, DRAW_GLYPH = _D["DSPN_DRAW_OUTLINE"], _D["DSPN_DRAW_FILL"], _D["DSPN_DRAW_GLYPH"]
+RENDER_FONT_BYTES = _D["DSPN_RENDER_FONT_BYTES"]
 
 
 def render_chunk_rows():
@@ -1413,11 +1248,9 @@ def render_draw_list(canvas, table, font, y0=0, x0=0, Hd=None, Wd=None):
 
 # ------------------------------------------------------------------ per-tensor statistics (training monitor)
 # include/dspn_monitor.h dspn_stats_row (40 bytes) and dspn_stats_out (48 bytes)
-STATS_ROW_FIELDS = [("base", "<u8"), ("rows", "<i8"), ("first_chunk", "<i8"), ("C", "<i4"), ("ld", "<i4"), ("dtype", "<i4"),
-                    ("reserved", "<i4")]
-STATS_OUT_FIELDS = [("sumsq", "<f8"), ("sum", "<f8"), ("n_nan", "<u8"), ("n_posinf", "<u8"), ("n_neginf", "<u8"),
-                    ("absmax", "<f4"), ("reserved", "<i4")]
-_STATS_DTYPES = {torch.float32: (0, 4), torch.bfloat16: (1, 2)}      # DSPN_STATS_F32 / DSPN_STATS_BF16, bytes per element
+STATS_ROW_FIELDS = _lib.field_list("dspn_stats_row")
+STATS_OUT_FIELDS = _lib.field_list("dspn_stats_out")
+_STATS_DTYPES = {torch.float32: (_D["DSPN_STATS_F32"], 4), torch.bfloat16: (_D["DSPN_STATS_BF16"], 2)}      # code, bytes per element
 
 
 def tensor_stats_chunk_elems():
@@ -1537,9 +1370,8 @@ def sgd_momentum(w, grad, mom, lr, momentum, wd, rescale):
                                     stream()), "sgd_momentum")
 
 
-# include/dspn_nn.h dspn_sgd_segment (24 bytes) and DSPN_SGD_MAX_SEGMENTS
-SGD_SEGMENT_FIELDS = [("offset", "<i8"), ("length", "<i8"), ("lr_mult", "<f4"), ("wd_mult", "<f4")]
-SGD_MAX_SEGMENTS = 8192
+SGD_SEGMENT_FIELDS = _lib.field_list("dspn_sgd_segment")
+SGD_MAX_SEGMENTS = _D["DSPN_SGD_MAX_SEGMENTS"]
 
 
 def sgd_segment_table(rows, numel, device):
@@ -1568,11 +1400,6 @@ def sgd_momentum_segments(w, grad, mom, table, lr, momentum, wd, rescale):
 
 
 # ------------------------------------------------------------------ polygon rasteriser (include/dspn_polygon.h)
-_lib.register({
-    "dspn_polygon_wave_entries": (_i, []),
-    "dspn_polygon_rasterize": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _ll, _vp, _i, _i, _i, _vp, _vp]),
-    "dspn_polygon_resolve": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-})
 
 
 def polygon_wave_entries():

@@ -105,7 +105,6 @@ def query(lib, case):
 def main():
     assert not [k for k in os.environ if k.startswith("DSPN_") and k != "DSPN_LIB"], "unset the DSPN_* knobs"
     from dspnet_amd import _lib
-    from dspnet_amd import functional  # noqa: F401  (registers the signatures)
     lib = _lib.lib()
     rows = [{"args": list(c), "results": query(lib, c)} for c in cases()]
     doc = {"args": ["N", "H", "W", "Cin", "Cout", "k", "stride", "pad", "dil"], "rows": rows}

@@ -116,7 +116,6 @@ def main():
     import torch
     assert not torch.cuda.is_available(), "the refused calls carry stand-in pointers: write the fixture where no GPU is visible"
     from dspnet_amd import _lib
-    from dspnet_amd import functional  # noqa: F401  (registers the signatures)
     lib = _lib.lib()
     refused = []
     for entry, kw in refused_cases():

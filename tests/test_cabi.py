@@ -1,15 +1,13 @@
 """The C-ABI library loads on a machine without a GPU and exports exactly what include/*.h
 declares (no compute calls here)."""
+import ctypes
 import glob
 import os
 import re
 
 import pytest
 
-from dspnet_amd import _lib
-from dspnet_amd import functional  # noqa: F401  (registers the include/dspn_nn.h signatures)
-from dspnet_amd.detect import nms as _nms_front  # noqa: F401  (registers include/dspn_nms.h)
-from dspnet_amd.dataset import iterator as _iter_front  # noqa: F401  (registers include/dspn_augment.h)
+from dspnet_amd import _abi, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,8 +34,34 @@ def test_every_declared_symbol_is_exported_and_bound():
     for name in sorted(decl):
         assert hasattr(lib, name), f"{name} declared in include/ but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature in dspnet_amd/_lib.py"
-    for name in _lib.SIGNATURES:
-        assert name in decl, f"{name} bound in _lib.py but not declared in include/*.h"
+
+
+def test_every_header_parses_and_every_declared_name_has_a_signature():
+    """every prototype and struct of every header parses (a declaration outside the vocabulary raises), and SIGNATURES --
+    what lib() binds -- has an entry for each declared name"""
+    decl, structs = declared_symbols(), {}
+    for h in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        text = open(h).read()
+        sigs, st, _ = _abi.parse_text(text, os.path.basename(h))
+        assert len(st) == len(re.findall(r"\btypedef\s+struct\b", text)), h
+        assert all(_lib.SIGNATURES[name] == sig for name, sig in sigs.items()), h
+        structs.update(st)
+    assert len(_lib.SIGNATURES) >= 187 and set(_lib.SIGNATURES) == decl
+    assert structs.keys() == _lib.STRUCTS.keys() == STRUCT_BYTES.keys()
+
+
+# sizeof of every descriptor struct of include/*.h: a changed layout is a changed ABI and says so here
+STRUCT_BYTES = {"dspn_warp_sample": 88, "dspn_det_sample": 56, "dspn_png_sample": 32, "dspn_png_rgb_sample": 48,
+                "dspn_jpeg_info": 296, "dspn_jpeg_sample": 272, "dspn_jpeg_scan": 2224, "dspn_jpeg_enc_sample": 272,
+                "dspn_png_enc_sample": 32, "dspn_jitter_sample": 32, "dspn_draw_row": 36, "dspn_stats_row": 40,
+                "dspn_stats_out": 48, "dspn_sgd_segment": 24, "dspn_bn_moving": 32}
+
+
+@pytest.mark.parametrize("name", sorted(STRUCT_BYTES))
+def test_descriptor_struct_sizes_are_pinned(name):
+    dt = _lib.layout(name)
+    assert dt.itemsize == STRUCT_BYTES[name] == ctypes.sizeof(_lib.STRUCTS[name])
+    assert [dt.fields[n][1] for n in dt.names] == [getattr(_lib.STRUCTS[name], n).offset for n in dt.names]
 
 
 def test_workspace_queries_are_pure():
