@@ -24,7 +24,7 @@ import re
 import numpy as np
 import torch
 
-from . import functional as fn, graph_plan
+from . import backward_route as R, functional as fn, graph_plan
 from .magnitudes import Magnitudes
 
 
@@ -126,7 +126,7 @@ class Tensor:
         self.am_slot = None
         self.alias_of = None
         self.grad_planes = False   # this backward pass: .grad holds fp16 piece planes, not floats (BatchNorm.dx_planes)
-        self.sc_compact = None     # this backward pass: the projection shortcut's share of .grad, compact (Conv._compact_shortcut)
+        self.sc_compact = None     # this backward pass: the projection shortcut's share of .grad, compact (Conv._data_gradient)
         self.channels = None       # logical channel count when the last axis is padded (19 -> 20, 3 -> 4)
         self.data = None if virtual else (data if data is not None else fn.zeros(*self.shape, device=device, dtype=self.dtype))
         self.grad = None
@@ -253,13 +253,14 @@ class Graph:
         # ... and the BACKWARD of some of those nodes beside the decoder's (set_side_backward): only nodes whose gradients
         # stay inside the branch; every main-stream node of the branch waits for what the side stream has been given so far
         self.side_bwd = None
+        self.on_branch_stream = False      # True while backward_node runs a node of the branch on the side stream
         self.side_fwd_events, self.side_fwd_waits = {}, {}   # graph_plan.side_sync
         self.side_plan = None      # what the builder asked for (any device) and what graph_plan.side_sync made of it
         self.slab_tables = {}      # key -> (conv nodes, device table) of deferred split-K slab reductions
         # the compact data gradient of a projection shortcut between its two calls (graph_plan.shortcut_compaction): ONE flat
         # buffer sized for the largest pair -- a pair's two calls are neighbours on the step's stream, so only one is live
         self.sc_compact_buf = None
-        self.bn1_recompute_calls = 0   # apply passes run inside a recomputed data gradient so far (Conv._recompute_route)
+        self.bn1_recompute_calls = 0   # apply passes run inside a recomputed data gradient so far (BatchNorm._apply)
         self.wt_table = None       # descriptor table of every Conv's (weight, transposed weight) pair
         self.wt_batched = False    # True while backward() runs after one batched transpose launch
         self.arena = self.grad_arena = self.mom_arena = None
@@ -634,7 +635,11 @@ class Graph:
                 side.wait_event(sb["fork_ev"])
                 sb["forked"] = True
             with torch.cuda.stream(side), fn.workspace_lane(1):
-                n.backward()
+                self.on_branch_stream = True
+                try:
+                    n.backward()
+                finally:
+                    self.on_branch_stream = False
                 sb["prog_ev"].record(side)
             sb["dirty"] = True
             return
@@ -656,6 +661,8 @@ class Graph:
         return self._bn_chain
 
     def wgrad_beside(self, conv, dy, planes, xa, dya):
+        """-> False, nothing launched, for a node of the branch stream or a tap-expanded one (backward_route.conv_route asks for
+        neither)"""
         main = torch.cuda.current_stream(self.device)
         if main == shared_stream(self.device, "branch", -1) or conv.tap_expand:
             return False
@@ -730,9 +737,8 @@ class Graph:
         streams = set()
         for n in self.nodes:
             if isinstance(n, BatchNorm):
-                if n._pending is not None:
-                    streams.add(n._pending[2])
-                n._pending, n.bwd_sums_ready, n._recompute = None, False, None
+                streams.update(n.hand.parked_streams())
+                n.hand.clear()
         for s in streams:      # (a job no apply half has run belongs to a node that is still pending)
             fn.bn_discard_parked(s)
 
@@ -920,6 +926,29 @@ FUSE_MAXPOOL_BACKWARD = os.environ.get("DSPN_FUSE_POOL_BWD", "1") != "0"      # 
 X_PLANES_MIN_READS = int(os.environ.get("DSPN_X_PLANES_MIN_READS", "6"))
 
 
+class BackwardHandoff:
+    """The per-pass state between nodes: what a BatchNorm is left by other nodes, or by its own first half, during ONE backward
+    pass.  Each field is taken (reset) by the step that uses it; clear() drops a pass that will not be finished."""
+    __slots__ = ("sums_ready", "pooled", "parked", "recompute")
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.sums_ready = False    # the data gradient of Conv.bn_bwd_node's convolution has gathered BatchNorm.bwd_sums
+        self.pooled = None         # (argmax, pooled gradient, k, stride, pad) left by a MaxPool that folds this node
+        # round 6: the finalize half is parked for / rode in the weight gradient of the convolution whose data gradient gathered
+        # the sums: (args, kwargs, stream handle) of the apply half.  The coefficients wait in BatchNorm.bwd_ws, which no
+        # other node writes
+        self.parked = None
+        # that data gradient stored no gradient for this node (backward_route.SUMS_ONLY): (conv, dy, planes, dy magnitude,
+        # weight magnitude) of the apply pass that forms it again
+        self.recompute = None
+
+    def parked_streams(self):
+        return () if self.parked is None else (self.parked[2],)
+
+
 class BatchNorm(Node):
     """mx.sym.BatchNorm with batch statistics (the solver always runs is_train=True,
     multi_solver.py:284) optionally fused with the following ReLU.
@@ -974,7 +1003,6 @@ class BatchNorm(Node):
         self.mat_consumers = []      # plain convolutions reading a MATERIALISED self.out (their last data gradient can
                                      # still gather this BatchNorm's backward reductions in its epilogue)
         self.bwd_sums = None         # (buffer, tiles) written by the LAST data gradient into self.out.grad
-        self.bwd_sums_ready = False
         self.bwd_ws = None           # with bwd_sums: this node's workspace of the backward from them (coefficients, grouped tiles)
         # round 4 (graph_plan.gradient_planes): dx leaves as fp16 piece planes; x_ext = per-channel extremes of x from the
         # forward finalize, am_dyin = slot of the magnitude of this node's own output gradient (from the data gradient's epilogue)
@@ -982,18 +1010,11 @@ class BatchNorm(Node):
         # round 4 (graph_plan.input_planes): the output as fp16 piece planes for the multi-tap convolutions behind a DEFERRED
         # apply; planes_ready: written by this step's forward (the magnitude they are cut by came out of the finalize)
         self.planes, self.planes_ready = None, False
-        self.pool_grad = None        # (argmax, pooled gradient, k, stride, pad) left by a MaxPool that folds this node (one backward)
+        self.hand = BackwardHandoff()      # what other nodes, or this node's first half, leave here during a backward pass
         self._g = g
         # True when this node's backward is the LAST writer of x's gradient (set by Graph.finalize): only then is the dx it
         # stores the complete gradient whose magnitude the producing convolution may use
         self.completes_x_grad = False
-        # round 6: the finalize half of this node's backward is parked for / rode in the weight gradient of the convolution
-        # whose data gradient gathered the sums: (args, kwargs, stream handle) of the apply half, or None.  The coefficients
-        # wait in bwd_ws, which no other node writes (Graph.abandon_backward drops a pass that never gets to the apply half)
-        self._pending = None
-        # this backward pass: the data gradient that gathered the sums stored no dy for this node (Conv._recompute_route):
-        # (conv, dy, planes, dy magnitude, weight magnitude) of the apply pass that forms it again
-        self._recompute = None
 
     def _moving(self):
         """the dspn_bn_moving block of this forward's finalize, or None (batch statistics, nothing tracked)"""
@@ -1036,36 +1057,92 @@ class BatchNorm(Node):
         mag = self._g.mag
         return mag.done(mag.input_slot(self.x, self.scale, create=False))
 
+    def _dx_magnitude_slot(self):
+        """"f16x2" math: dx is the output gradient of the convolution that produced x; where this node's backward completes it (it
+        alone reads x, or x is the residual stream and it writes last), the apply kernel leaves its magnitude: that slot, or None"""
+        prod, wanted = self.x.producer, self.x.requires_grad and self.completes_x_grad and self._g.mag.active
+        return prod.am_dy if (wanted and isinstance(prod, Conv) and self.x.dtype == torch.float32) else None
+
+    def _facts(self, beside):
+        hand = self.hand
+        return R.BnFacts(beside=beside, x_requires_grad=self.x.requires_grad, dx_planes=self.dx_planes,
+                         cuda=self._g.device.type == "cuda", finalize_beside=bool(FINALIZE_BESIDE), out_written=self.out._gw,
+                         x_written=self.x._gw, takes_magnitude=self._dx_magnitude_slot() is not None,
+                         x_ext_valid=self.dx_planes and self._x_ext_valid(),
+                         producer_guard_fb=bool(getattr(self.x.producer, "guard_fb", False)), sums_ready=hand.sums_ready,
+                         pooled=hand.pooled is not None, parked=hand.parked is not None, recompute=hand.recompute is not None)
+
     def finalize_beside(self):
         """Round 6: called by the convolution whose data gradient has just gathered this node's backward
         sums in its epilogue, BEFORE it launches its weight gradient.  The finalize half of dspn_bn_backward_from_sums (one or
         two launches on 1 - 64 workgroups, 6 - 15 us of an otherwise idle chip) is PARKED in the library and rides in front of
         that weight gradient's grid (csrc/bn_final_job.h); backward() later launches the apply half.  (On a second stream
         instead -- two events per node -- the step LOST 1.5 %: profiles/r06_finalize_beside_ab.txt.)  -> True if it did."""
+        route = R.bn_route(self._facts(beside=True))
+        self._run(route)
+        return route.finalize == R.PARKED
+
+    def backward(self):
+        self._run(R.bn_route(self._facts(beside=False)))
+
+    def _run(self, route):
+        hand, g = self.hand, self._g
+        if route.kind == R.NOTHING:
+            return
+        if route.kind == R.APPLY_PARKED:
+            (args, kw, _), hand.parked = hand.parked, None
+            return self._apply(route.apply, args, kw)
+        # what every entry point takes.  Frozen gamma / beta: not computed (NULL to the kernels); dgamma stays None without a gamma
+        # (fix_gamma).  fixed_stats (use_global_stats under training): mean / rstd are the moving statistics, dx has no term through them
+        gamma = None if self.gamma is None else self.gamma.data
+        out = dict(dgamma=None if self.gamma is None else (fn.NO_OUTPUT if self.gamma.fixed else self.gamma.grad),
+                   dbeta=fn.NO_OUTPUT if self.beta.fixed else self.beta.grad, relu=self.relu, fixed_stats=self.use_global_stats)
+        if route.writes_dx:
+            dx, acc = self.x.grad_target()
+            out.update(dx=dx, dx_absmax=g.mag.claim(self._dx_magnitude_slot()))
+        else:  # the parameters alone: reductions and finalize, no dx (the kernels take dx == NULL)
+            acc = False
+            out.update(dx=fn.NO_OUTPUT, dx_absmax=None)
+        if hand.pooled is not None:
+            (argmax, dyp, k, s, p), hand.pooled = hand.pooled, None
+            if route.kind == R.POOLED:
+                fn.bn_backward_maxpool(self.x.data, self.scale, self.shift, dyp, argmax, k, s, p, self.mean, self.rstd, gamma, **out)
+                return
+            assert route.unpool_first      # (a second writer of x's gradient: materialise the pooling backward after all)
+            fn.maxpool_backward_argmax(argmax, dyp, self.out.shape, k, s, p, dx=self.out.own_grad())
+            self.out.grad = self.out.own_grad()
+        if route.kind == R.STANDALONE:
+            fn.bn_backward(self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd, gamma, accumulate=acc, **out)
+            return
+        # the two reductions came out of the data-gradient kernel's epilogue
+        hand.sums_ready = False
+        args, kw = self._from_sums_call(route.kind == R.FROM_SUMS_PLANES, gamma, acc, out)
+        phase = {R.WITH_APPLY: {}, R.ALONE: dict(phase=1), R.PARKED: dict(phase=1, park=True)}[route.finalize]
+        fn.bn_backward_from_sums(*args, **phase, **kw)
+        if route.finalize == R.PARKED:
+            hand.parked = (args, kw, fn.stream())
+        elif route.finalize == R.ALONE:
+            self._apply(route.apply, args, kw)
+        if route.kind == R.FROM_SUMS_PLANES:
+            self.x.grad_planes = True
+
+    def _from_sums_call(self, planes, gamma, acc, out):
+        """(positional arguments, keywords) of fn.bn_backward_from_sums, whichever phase: the parked finalize and the finalize in
+        front of a recomputed data gradient hand the same pair to their apply half"""
         g = self._g
-        if (not FINALIZE_BESIDE or g.device.type != "cuda" or not self.bwd_sums_ready or self.pool_grad is not None
-                or not self.out._gw or self._pending is not None or not self.x.requires_grad):
-            # (parameters only -- x needs no gradient -- is the finalize alone: no apply half to park it for)
-            return False
-        self.backward(beside=True)
-        return self._pending is not None
+        args = (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd, gamma, self.bwd_sums[0], self.bwd_sums[1])
+        kw = dict(out, accumulate=acc, workspace=self.bwd_ws)
+        if planes:      # the gradient leaves as fp16 piece planes (same buffer): dx_absmax receives the BOUND it is cut by
+            assert not acc
+            kw.update(dy_absmax=g.mag.block(self.am_dyin), x_chan_minmax=self.x_ext, dx_planes=True,
+                      dx_absmin=g.mag.min_view(self.x.producer.am_dy) if g.guard["enabled"] else None)
+        return args, kw
 
-    def _from_sums(self, beside, args, kw):
-        kw["workspace"] = self.bwd_ws
-        if beside:
-            fn.bn_backward_from_sums(*args, phase=1, park=True, **kw)
-            self._pending = (args, kw, fn.stream())
-        elif self._recompute is None:
-            fn.bn_backward_from_sums(*args, **kw)
-        else:      # (the gradient was never stored: the finalize now, the apply pass in the data gradient that forms it again)
-            fn.bn_backward_from_sums(*args, phase=1, **kw)
-            self._apply(args, kw)
-
-    def _apply(self, args, kw):
+    def _apply(self, how, args, kw):
         """the apply half from the coefficients the finalize left in bwd_ws: the apply kernel over the stored gradient, or --
-        the data gradient stored none (Conv._recompute_route) -- that data gradient again, with the apply in its epilogue"""
-        rc, self._recompute = self._recompute, None
-        if rc is None:
+        the data gradient stored none (backward_route.SUMS_ONLY) -- that data gradient again, with the apply in its epilogue"""
+        rc, self.hand.recompute = self.hand.recompute, None
+        if how == R.KERNEL:
             fn.bn_backward_from_sums(*args, phase=2, **kw)
             return
         conv, dy, planes, dya, wa = rc
@@ -1073,65 +1150,6 @@ class BatchNorm(Node):
                                  accumulate=kw["accumulate"], dx_absmax=kw["dx_absmax"], wt_planes=conv.wtp, math=conv.math,
                                  dy_absmax=dya, w_absmax=wa, dy_planes=planes, wt_shape=conv.wt_shape)
         self._g.bn1_recompute_calls += 1
-
-    def backward(self, beside=False):
-        if self._pending is not None:
-            args, kw, _ = self._pending
-            self._pending = None
-            self._apply(args, kw)
-            return
-        if not self.out._gw:
-            return
-        am = None
-        # frozen gamma / beta: not computed (NULL to the kernels); dgamma stays None where there is no gamma (fix_gamma)
-        dgam = None if self.gamma is None else (fn.NO_OUTPUT if self.gamma.fixed else self.gamma.grad)
-        dbet = fn.NO_OUTPUT if self.beta.fixed else self.beta.grad
-        # use_global_stats under training: mean / rstd are the moving statistics the forward finalize wrote, so dx has no term
-        # through them (include/dspn_nn.h DSPN_BN_SUMS_FIXED_STATS).  Every route below takes the mode; the kw dict of
-        # _from_sums carries it into the parked finalize and the finalize in front of a recomputed data gradient
-        fixed = self.use_global_stats
-        if self.x.requires_grad:
-            dx, acc = self.x.grad_target()
-            # "f16x2" math: dx is the output gradient of the convolution that produced x; when this call completes it (a
-            # tensor read by this BatchNorm alone, or the residual stream, whose last writer in backward order is the next
-            # unit's first BatchNorm), its magnitude comes out of the apply kernel instead of a pass of its own
-            prod, g = self.x.producer, self._g
-            if isinstance(prod, Conv) and dx.dtype == torch.float32 and self.completes_x_grad:
-                am = g.mag.claim(prod.am_dy)
-        else:  # the parameters alone: reductions and finalize, no dx (the kernels take dx == NULL)
-            dx, acc = fn.NO_OUTPUT, False
-        if self.pool_grad is not None:
-            argmax, dyp, k, s, p = self.pool_grad
-            self.pool_grad = None
-            if not acc:
-                fn.bn_backward_maxpool(self.x.data, self.scale, self.shift, dyp, argmax, k, s, p, self.mean, self.rstd,
-                                       None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx,
-                                       dgamma=dgam, dbeta=dbet, dx_absmax=am, fixed_stats=fixed)
-                return
-            # (a second writer of x's gradient: materialise the pooling backward after all)
-            fn.maxpool_backward_argmax(argmax, dyp, self.out.shape, k, s, p, dx=self.out.own_grad())
-            self.out.grad = self.out.own_grad()
-        if (self.bwd_sums_ready and self.dx_planes and am is not None and not acc and self._x_ext_valid()
-                and not getattr(prod, "guard_fb", False)):      # (a convolution on the guard's fallback reads a FLOAT gradient)
-            # the gradient leaves as fp16 piece planes (same buffer): `am` receives the BOUND it is cut by
-            self.bwd_sums_ready = False
-            self._from_sums(beside, (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
-                                     None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
-                            dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=False, dx_absmax=am,
-                                 dy_absmax=g.mag.block(self.am_dyin), x_chan_minmax=self.x_ext, dx_planes=True,
-                                 dx_absmin=g.mag.min_view(prod.am_dy) if g.guard["enabled"] else None, fixed_stats=fixed))
-            self.x.grad_planes = True
-            return
-        if self.bwd_sums_ready:      # the two reductions came out of the data-gradient kernel's epilogue
-            self.bwd_sums_ready = False
-            self._from_sums(beside, (self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
-                                     None if self.gamma is None else self.gamma.data, self.bwd_sums[0], self.bwd_sums[1]),
-                            dict(relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet, accumulate=acc, dx_absmax=am, fixed_stats=fixed))
-            return
-        assert not beside, "finalize_beside() without the data gradient's sums"
-        fn.bn_backward(self.x.data, self.scale, self.shift, self.out.grad, self.mean, self.rstd,
-                       None if self.gamma is None else self.gamma.data, relu=self.relu, dx=dx, dgamma=dgam, dbeta=dbet,
-                       accumulate=acc, dx_absmax=am, fixed_stats=fixed)
 
 
 # round 6: the weight gradients of the step's stream on a stream of their own (Graph.wgrad_beside): nothing on the critical
@@ -1407,36 +1425,50 @@ class Conv(Node):
         xa, dya, wa = self._magnitudes("x"), self._magnitudes("dy"), self._magnitudes("w")
         if dya is not None and not self._g.mag.done(self.am_dy):       # (else: the BatchNorm backward that completed dy took it)
             fn.absmax(dy, out=self._g.mag.claim(self.am_dy))    # (a projection shortcut that shares this slot reads the same gradient)
-        # round 6: when this data gradient gathers the backward sums of the BatchNorm in front (bn_bwd_node), it goes FIRST and
-        # that node's finalize rides in front of the weight gradient's grid (BatchNorm.finalize_beside)
-        bn = self.bn_bwd_node if self.x.requires_grad else None
-        isg = self.input_sum_grad if (self.input_sum_grad is not None and not self.input_sum_grad.fixed) else None
-        if self.w.fixed:
-            # frozen weight: no weight gradient, so nothing for a BatchNorm finalize to ride in (it runs on its own) and no
-            # second stream; the data gradient (and the bn_data beta's sum) still run
-            if isg is not None:
-                fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=isg.grad)
-            if self.x.requires_grad:
-                self._data_gradient(dy, planes, dya, wa)
-            return
-        early = (bn is not None and FINALIZE_BESIDE and not self.guard_fb and self._g.device.type == "cuda"
-                 and bn.pool_grad is None)
-        if (WGRAD_SIDE and self._g.wgrad_side_allowed and self._g.device.type == "cuda" and (bn is not None or self._g.batchnorm_chain()) and self._wgrad_worth_a_stream()
-                and self._g.wgrad_beside(self, dy, planes, xa, dya)):
-            early = False          # (the weight gradient went to its own stream: nothing to ride in, and the finalize's gap is filled)
-            if isg is not None:
-                fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=isg.grad)
-            if self.x.requires_grad:
-                self._data_gradient(dy, planes, dya, wa)
-            return
-        if early:
-            self._data_gradient(dy, planes, dya, wa)
-            bn.finalize_beside()
-        self._weight_gradient(dy, planes, xa, dya)
-        if isg is not None:
-            fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=isg.grad)
-        if self.x.requires_grad and not early:
-            self._data_gradient(dy, planes, dya, wa)
+        route = R.conv_route(self._facts(planes))
+        step = {R.WGRAD: self._weight_gradient_step, R.ISG: self._input_sum_gradient, R.DGRAD: self._data_gradient,
+                R.PARK: self._park_finalize}
+        for s in route.steps:
+            step[s](route, dy, planes, xa, dya, wa)
+
+    def _facts(self, planes):
+        """what backward_route.conv_route reads: the node and graph_plan's marks, the knobs as they stand now, this pass"""
+        g, x, bn, pair = self._g, self.x, self.bn_bwd_node, self.sc_pair
+        hand = None if bn is None else bn.hand
+        cuda = g.device.type == "cuda"
+        stride2_member = pair is not None and self.stride == 2
+        (N, H, W, C), K = x.shape, self.wt_shape[3]
+        return R.ConvFacts(
+            stride=self.stride, bn_bwd_node=bn is not None, sc_pair=pair is not None, bn1_recompute=self.bn1_recompute,
+            bn_dx_planes=bn is not None and bn.dx_planes, bn_x_requires_grad=bn is not None and bn.x.requires_grad,
+            w_fixed=self.w.fixed, x_requires_grad=x.requires_grad,
+            input_sum_grad=self.input_sum_grad is not None and not self.input_sum_grad.fixed, tap_expand=self.tap_expand,
+            cuda=cuda, compact_buf=g.sc_compact_buf is not None,
+            wgrad_side=bool(WGRAD_SIDE), wgrad_side_allowed=g.wgrad_side_allowed, finalize_beside=bool(FINALIZE_BESIDE),
+            sc_compact=bool(SC_COMPACT), bn1_recompute_knob=BN1_RECOMPUTE, bn_chain=g.batchnorm_chain(),
+            wgrad_worth=self._wgrad_worth_a_stream(), on_branch_stream=g.on_branch_stream,
+            guard_fb=self.guard_fb, pair_guard_fb=pair is not None and pair.guard_fb, dy_planes=bool(planes), x_written=x._gw,
+            pair_out_written=stride2_member and pair.out._gw, have_addend=x.sc_compact is not None,
+            bn_pooled=hand is not None and hand.pooled is not None, bn_parked=hand is not None and hand.parked is not None,
+            recompute_pays=self.bn1_recompute and bn1_recompute_pays(N * H * W, C, K),
+            # (host-only queries of the library, asked for marked nodes only)
+            addend_kernel=stride2_member and fn.conv2d_dgrad_addend_route(x.shape, pair.out.shape[3], pair.out.grad_planes),
+            recompute_kernel=self.bn1_recompute and fn.conv2d_dgrad_recompute_route(x.shape, K, planes))
+
+    def _weight_gradient_step(self, route, dy, planes, xa, dya, wa):
+        if route.wgrad == R.ON_SIDE:
+            went = self._g.wgrad_beside(self, dy, planes, xa, dya)
+            assert went, "the route sent a weight gradient beside the chain that Graph.wgrad_beside refuses"
+        else:
+            self._weight_gradient(dy, planes, xa, dya)
+
+    def _input_sum_gradient(self, route, dy, planes, xa, dya, wa):
+        fn.conv2d_input_sum_grad(dy, self.w.data, self.x.shape, self.stride, self.pad, self.dil, out=self.input_sum_grad.grad)
+
+    def _park_finalize(self, route, dy, planes, xa, dya, wa):
+        """round 6: the data gradient that gathered the sums of the BatchNorm in front has gone FIRST; that node's finalize
+        rides in front of the weight gradient's grid, which comes next (BatchNorm.finalize_beside)"""
+        self.bn_bwd_node.finalize_beside()
 
     def _wgrad_worth_a_stream(self):
         """The weight gradient goes beside the chain only where that pays: behind a data gradient that feeds a BatchNorm
@@ -1479,78 +1511,49 @@ class Conv(Node):
             fn.conv2d_wgrad(x, dy, wshape, *geom, out=self.w.grad.view(wshape), **how)
         self.slabs_fresh = self.slabs is not None
 
-    def _data_gradient(self, dy, planes, dya, wa):
-        g = self._g
+    def _data_gradient(self, route, dy, planes, xa, dya, wa):
+        g, kind = self._g, route.dgrad
         if self.wtp is not None and (g.wp_frozen if self.w.fixed else g.wp_table) is None:
             fn.weight_planes(self.w.data, transposed=True, cols=self.wtp.shape[2] * 32, out=self.wtp, math=self.math,
                              w_absmax=wa)
         elif self.wtp is None and not (g.wt_frozen is not None if self.w.fixed else g.wt_batched):
             fn.weight_transpose(self.w.data, out=self.wt, copy=self.wh)
-        if self.sc_pair is not None and self.stride == 2 and self._compact_shortcut(dy, planes, dya, wa):
-            return
-        dx, acc = self.x.grad_target()
-        sa = self.x.sc_compact   # left by the pair's shortcut in this pass: this call is then the first and only writer of dx
-        assert sa is None or (not acc and not self.guard_fb and self.bn_bwd_node is not None)
-        bn = self.bn_bwd_node   # set by Graph.finalize on the LAST writer of a deferred BN's gradient
-        bn_bwd, bn_dya = None, None
-        if bn is not None:
-            bn_bwd = (bn.x.data, bn.scale, bn.shift, bn.mean, bn.rstd, bn.relu, bn.bwd_sums[0])
-            bn.bwd_sums_ready = True
-            if bn.dx_planes:         # that BatchNorm's backward bounds its dx from the largest gradient stored here
-                bn_dya = g.mag.claim(bn.am_dyin)
-            if self._recompute_route(bn, planes, acc):
-                # the sums alone: dx stays unwritten; bn's backward runs this product again (BatchNorm._apply)
-                fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, bn_bwd=bn_bwd, wt_planes=self.wtp,
-                                math=self.math, dy_absmax=dya, w_absmax=wa, dy_planes=planes, wt_shape=self.wt_shape,
-                                sums_only=True)
-                bn._recompute = (self, dy, planes, dya, wa)
-                return
-        if self.guard_fb:
-            w3 = self._w3(True)
-            fn.conv2d_dgrad(dy, self.wt if w3 is None else None, self.x.shape, self.stride, self.pad, self.dil, out=dx,
-                            accumulate=acc, bn_bwd=bn_bwd, wt_planes=w3, math="bf16x3", wt_shape=self.wt_shape)
+        # each kind chooses its operands once -- the weight, dx's shape, (stride, pad, dil) and what else the call names
+        wt, shape, geom = self.wt, self.x.shape, (self.stride, self.pad, self.dil)
+        how = dict(wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa, dy_planes=planes)
+        bn, bn_dya = (self.bn_bwd_node if route.hands_sums else None), None
+        if kind == R.COMPACT:
+            # a projection shortcut (1 x 1, stride 2, pad 0) as the stride-1 1 x 1 data gradient on the subsampled grid, into the
+            # graph's compact buffer, left on the input tensor for the pair's conv1 (which runs next among the writers of that
+            # gradient and adds it in its epilogue).  A weight gradient of this node beside the chain reads dy, never the
+            # compact buffer, which is written and read on the step's stream only
+            (N, H, W, C), (Ho, Wo) = self.x.shape, dy.shape[1:3]
+            dx = g.sc_compact_buf[:N * Ho * Wo * C].view(N, Ho, Wo, C)
+            shape, geom = dx.shape, (1, 0, 1)
+            how.update(out=dx)
+        else:
+            dx, acc = self.x.grad_target()
+            if bn is not None:       # set by Graph.finalize on the LAST writer of a deferred BN's gradient
+                how.update(bn_bwd=(bn.x.data, bn.scale, bn.shift, bn.mean, bn.rstd, bn.relu, bn.bwd_sums[0]))
+                bn.hand.sums_ready = True
+                if route.claims_dyin:    # that BatchNorm's backward bounds its dx from the largest gradient stored here
+                    bn_dya = g.mag.claim(bn.am_dyin)
+            if kind == R.SUMS_ONLY:      # dx stays unwritten; bn's backward runs this product again (BatchNorm._apply)
+                how.update(sums_only=True)
+                bn.hand.recompute = (self, dy, planes, dya, wa)
+            elif kind == R.FALLBACK:
+                w3 = self._w3(True)
+                wt = self.wt if w3 is None else None
+                how = dict(out=dx, accumulate=acc, bn_bwd=how.get("bn_bwd"), wt_planes=w3, math="bf16x3")
+            else:      # (the addend: this call is then the first and only writer of dx)
+                how.update(out=dx, accumulate=acc, bn_dy_absmax=bn_dya, strided_addend=self.x.sc_compact if kind == R.ADDEND else None)
+        fn.conv2d_dgrad(dy, wt, shape, *geom, wt_shape=self.wt_shape, **how)
+        if kind == R.COMPACT:
+            self.x.sc_compact = dx
+        elif kind == R.FALLBACK:
             if bn_dya is not None:       # (the two-piece data gradient leaves this by-product in its epilogue)
                 fn.absmax(dx, out=bn_dya)
-            self._g.guard_count_call()
-            return
-        fn.conv2d_dgrad(dy, self.wt, self.x.shape, self.stride, self.pad, self.dil, out=dx, accumulate=acc,
-                        bn_bwd=bn_bwd, wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa,
-                        bn_dy_absmax=bn_dya, dy_planes=planes, wt_shape=self.wt_shape, strided_addend=sa)
-
-    def _recompute_route(self, bn, planes, acc):
-        """This pass, for a pair graph_plan.bn1_recompute marked: does the data gradient run for the sums alone, and again in
-        bn's backward?  No -- the pair of today -- with the knob off, on a layer the predicate leaves out, where either node
-        is on the range guard's fallback, where bn has no dx to write (its input needs no gradient) or folds a pooling
-        backward, where another writer got to the gradient first, or where the library has no kernel for the call."""
-        if (not self.bn1_recompute or not BN1_RECOMPUTE or acc or self.guard_fb or not planes or self._g.device.type != "cuda"
-                or not bn.x.requires_grad or bn.pool_grad is not None or bn.dx_planes or bn._pending is not None):
-            return False
-        N, H, W, C = self.x.shape
-        K = self.wt_shape[3]
-        if BN1_RECOMPUTE < 2 and not bn1_recompute_pays(N * H * W, C, K):
-            return False
-        return fn.conv2d_dgrad_recompute_route(self.x.shape, K, planes)
-
-    def _compact_shortcut(self, dy, planes, dya, wa):
-        """The data gradient of a projection shortcut (1 x 1, stride 2, pad 0) as the stride-1 1 x 1 data gradient on the
-        subsampled grid, into the graph's compact buffer, left on the input tensor for the pair's conv1 (which runs next among
-        the writers of that gradient and adds it in its epilogue).  Decided per pass: False -- the full-resolution call as
-        first writer, conv1 accumulates -- when the knob is off, either node is on the range guard's fallback, conv1 has no
-        gradient to propagate, or no kernel takes the addend for conv1's call (its dy not piece planes, launch settings).
-        A frozen shortcut weight changes nothing here: the operand planes are prepared the same way for either call.
-        The weight gradient of this node beside the chain (_wg_before_write / WgradSide.reads) is unaffected: it reads dy,
-        never the compact buffer, which is written and read on the step's stream only."""
-        conv1, x, g = self.sc_pair, self.x, self._g
-        if (not SC_COMPACT or self.guard_fb or conv1.guard_fb or planes or x._gw or not conv1.out._gw or g.sc_compact_buf is None
-                or not fn.conv2d_dgrad_addend_route(x.shape, conv1.out.shape[3], conv1.out.grad_planes)):
-            return False
-        N, H, W, C = x.shape
-        Ho, Wo = dy.shape[1], dy.shape[2]
-        dxc = g.sc_compact_buf[:N * Ho * Wo * C].view(N, Ho, Wo, C)
-        fn.conv2d_dgrad(dy, self.wt, dxc.shape, 1, 0, 1, out=dxc, wt_planes=self.wtp, math=self.math, dy_absmax=dya, w_absmax=wa,
-                        wt_shape=self.wt_shape)
-        x.sc_compact = dxc
-        return True
+            g.guard_count_call()
 
 
 class BilinearConcatConv(Node):
@@ -1790,7 +1793,7 @@ class MaxPool(Node):
                 and self.out.grad.dtype == torch.float32 and self.out.grad.device.type == "cuda"):
             # round 4: the BatchNorm(+ReLU) folded into this pooling forms its output gradient from (pooled gradient, argmax)
             # itself (dspn_bn_backward_maxpool_f32): the dense gradient of the pooling input is never written
-            bn.pool_grad = (self.argmax, self.out.grad, self.k, self.s, self.p)
+            bn.hand.pooled = (self.argmax, self.out.grad, self.k, self.s, self.p)
             self.x._gw = True
             return
         dx, _ = self.x.grad_target()

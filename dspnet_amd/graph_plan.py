@@ -141,7 +141,7 @@ def shortcut_compaction(g, index):
     """The projection units of the ResNets: act1 feeds conv1 (1 x 1, stride 1) and the shortcut (1 x 1, stride 2, pad 0), and
     conv1 -- built first -- is the last writer of act1's gradient and gathers bn1's backward sums.  The shortcut's data
     gradient is the stride-1 1 x 1 data gradient on the subsampled grid; written at full resolution it is three quarters
-    zeros that conv1's accumulate reads back.  Marked pairs keep it compact (Conv._compact_shortcut) and conv1's data gradient
+    zeros that conv1's accumulate reads back.  Marked pairs keep it compact (backward_route.COMPACT) and conv1's data gradient
     adds it at the even positions (include/dspn_nn.h dspn_conv2d_dgrad_bn_sadd_f32).  A pair: the BatchNorm output's gradient
     has exactly these two writers, "f16x2" math, float tensors; whether a given pass takes the path is the nodes' decision."""
     if g.math != "f16x2" or g.device.type != "cuda":
@@ -172,7 +172,7 @@ def bn1_recompute(g, index):
     reader, bn1's backward.  Marked pairs may leave it unwritten: the data gradient runs for the sums alone and again with the
     apply pass in its epilogue (include/dspn_nn.h dspn_conv2d_dgrad_bn_sums_f32 / _apply_f32).  A pair: "f16x2" math, float
     tensors, bn1's dx a float tensor (not piece planes) that is wanted, no projection shortcut beside conv1 (that is an
-    sc_pair); whether a given pass takes the route is the nodes' decision (Conv._recompute_route)."""
+    sc_pair); whether a given pass takes the route is decided per pass (backward_route.conv_route)."""
     if g.math != "f16x2" or g.device.type != "cuda":
         return
     for idx, c in enumerate(g.nodes):

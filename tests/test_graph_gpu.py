@@ -590,7 +590,7 @@ def test_two_batchnorms_parked_at_once_keep_their_own_coefficients(gpu_device):
 
             def watch(self):
                 r = orig(self)
-                pending.append(sum(n._pending is not None for n in (bn1, bn2)))
+                pending.append(sum(n.hand.parked is not None for n in (bn1, bn2)))
                 return r
             E.BatchNorm.finalize_beside = watch
             try:
