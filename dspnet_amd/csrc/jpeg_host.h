@@ -1,7 +1,9 @@
-// Host half of the JPEG decode (include/dspn_jpeg.h): marker parsing and Huffman decoding of a baseline stream into
-// quantised DCT coefficients.  Plain C++ with no HIP call and no global state, so that it also builds into a stand-alone
-// program under the host sanitizers (tools/jpeg_host_check.cpp).  Every read is checked against the end of the input and
-// every block is written through the geometry this file derived itself and compared with the caller's `info`.
+// Host half of the JPEG decode (include/dspn_jpeg.h): marker parsing, the scan index, and the host entropy pass -- the walk
+// over the MCUs, the restart markers between intervals, the end of the scan and the error texts around the Huffman decode of
+// jpeg_huff.h (tables, bit reader, decode_block), which this pass shares with the device.  Plain C++ with no HIP call and no
+// global state, so that it also builds into a stand-alone program under the host sanitizers (tools/jpeg_host_check.cpp).
+// Every read is checked against the end of the input and every block is written through the geometry this file derived
+// itself and compared with the caller's `info`.
 #pragma once
 #include <cstdarg>
 #include <cstdint>
@@ -9,28 +11,34 @@
 #include <cstring>
 
 #include "../../include/dspn_jpeg.h"
+#include "jpeg_huff.h"
 
 namespace dspn_jpeg {
 
+namespace hf = dspn_jpeg_huff;
+using hf::kLookBits;
+
 constexpr int kErr = -1;
-constexpr int kLookBits = 9;
 
-static const unsigned char kNatural[64] = {   // zigzag position -> natural (row-major) index
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+struct Natural {
+  unsigned char at[64];
+  constexpr Natural() : at{} { hf::fill_natural(at); }
+};
+static constexpr Natural kNaturalOrder;
+static constexpr const unsigned char (&kNatural)[64] = kNaturalOrder.at;   // zigzag position -> natural (row-major) index
 
-struct Huff {
+// a table of the stream: the shared decode table and what only the host needs
+struct Huff : hf::Table {
   bool present = false;
-  int nvals = 0;
   unsigned char counts[16] = {};    // codes per length 1..16, as the DHT segment carries them
-  unsigned char vals[256];
-  int maxcode[18];                  // largest code of each length, -1: none
-  int valoffset[17];                // index of the first value of a length minus its first code
-  uint16_t look[1 << kLookBits];    // (length << 8) | symbol for codes of up to kLookBits bits, 0: longer
   // AC tables: (value << 8) | (run << 4) | bits for a window that holds a whole code AND its magnitude bits
   // (code length + size <= kLookBits, value in -128..127), 0: take the two steps
   int16_t fast_ac[1 << kLookBits];
+  // What decode_block does with this type as its AC table.  The host pass takes every AC size a symbol can name, up to 15,
+  // where the device pass (hf::Table) refuses more than 10.  The difference is kept on purpose, it is not a bug:
+  // tests/test_jpeg_entropy_limits.py.
+  static constexpr int kMaxAcSize = 15;
+  static constexpr bool kFastAc = true;
 };
 
 struct Parsed {
@@ -54,31 +62,14 @@ inline int fail(char *err, size_t errn, const char *fmt, ...) {
 
 inline int build_huff(Huff &h, const unsigned char *bits /* [1..16] at bits[0..15] */, const unsigned char *vals, int nvals,
                       char *err, size_t errn) {
+  unsigned char padded[256] = {};   // build_codes copies 256 values, the segment holds nvals
+  memcpy(padded, vals, (size_t)nvals);
   h.present = true;
-  h.nvals = nvals;
   memcpy(h.counts, bits, 16);
-  memcpy(h.vals, vals, (size_t)nvals);
-  memset(h.look, 0, sizeof(h.look));
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; ++l) {
-    const int cnt = bits[l - 1];
-    h.valoffset[l] = k - code;
-    if (cnt) {
-      if (code + cnt > (1 << l)) return fail(err, errn, "jpeg: Huffman table has more codes of length %d than fit", l);
-      if (l <= kLookBits)
-        for (int i = 0; i < cnt; ++i) {
-          const int first = (code + i) << (kLookBits - l);
-          for (int j = 0; j < (1 << (kLookBits - l)); ++j) h.look[first + j] = (uint16_t)((l << 8) | vals[k + i]);
-        }
-      code += cnt;
-      k += cnt;
-      h.maxcode[l] = code - 1;
-    } else {
-      h.maxcode[l] = -1;
-    }
-    code <<= 1;
-  }
-  h.maxcode[17] = 0x7fffffff;
+  hf::build_codes(h, bits, padded);
+  for (int l = 1; l <= 16; ++l)
+    if (h.maxcode[l] >= (1 << l)) return fail(err, errn, "jpeg: Huffman table has more codes of length %d than fit", l);
+  hf::build_look(h, 0, 1);
   for (int i = 0; i < (1 << kLookBits); ++i) {
     h.fast_ac[i] = 0;
     const int len = h.look[i] >> 8, run = (h.look[i] >> 4) & 15, mag = h.look[i] & 15;
@@ -227,14 +218,8 @@ inline int probe(const unsigned char *b, size_t n, dspn_jpeg_info *info, char *e
   return rc;
 }
 
-// MSB-first bit reader over the entropy-coded segment: the top `bits` bits of `buf` are valid.  At a marker or at the end of
-// the input it feeds zero bits and counts them in `pad`; a decoder that has consumed padding (bits < pad) has run off the data.
-struct BitReader {
-  const unsigned char *p, *end;
-  uint64_t buf = 0;
-  int bits = 0, pad = 0;
-  bool stopped = false;             // at a marker or at the end
-
+// The shared bit reader behind a wide load: eight bytes at once where none of them is 0xFF.  Host only.
+struct FastBitReader : hf::BitReader {
   inline void fill() {              // -> bits >= 57
     if (!stopped && end - p >= 8) {
       uint64_t w;
@@ -251,82 +236,9 @@ struct BitReader {
         return;
       }
     }
-    while (bits <= 56) {
-      unsigned v = 0;
-      if (!stopped) {
-        if (p >= end) stopped = true;
-        else if (*p != 0xFF) v = *p++;
-        else if (p + 1 < end && p[1] == 0x00) { v = 0xFF; p += 2; }
-        else stopped = true;        // a marker (or a lone 0xFF at the end): stay in front of it
-      }
-      if (stopped) pad += 8;
-      buf |= (uint64_t)v << (56 - bits);
-      bits += 8;
-    }
+    hf::BitReader::fill();
   }
-  inline unsigned peek(int k) const { return (unsigned)(buf >> (64 - k)); }   // 1 <= k <= 32
-  inline void drop(int k) { buf <<= k; bits -= k; }
 };
-
-inline int decode_symbol(BitReader &br, const Huff &h) {     // needs bits >= 16; -1: no such code
-  const unsigned e = h.look[br.peek(kLookBits)];
-  if (e) { br.drop((int)(e >> 8)); return (int)(e & 255); }
-  for (int l = kLookBits + 1; l <= 16; ++l) {
-    const int code = (int)br.peek(l);
-    if (code <= h.maxcode[l]) {
-      const int idx = h.valoffset[l] + code;
-      if (idx < 0 || idx >= h.nvals) return -1;
-      br.drop(l);
-      return h.vals[idx];
-    }
-  }
-  return -1;
-}
-
-inline int receive_extend(BitReader &br, int s) {            // 1 <= s <= 15, needs bits >= s
-  const int v = (int)br.peek(s);
-  br.drop(s);
-  return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-}
-
-inline int decode_block(BitReader &br, const Huff &dc, const Huff &ac, int &pred, int16_t *blk, char *err, size_t errn) {
-  memset(blk, 0, 64 * sizeof(int16_t));
-  if (br.bits < 32) br.fill();
-  int s = decode_symbol(br, dc);
-  if (s < 0) return fail(err, errn, "jpeg: DC code not in its table");
-  if (s > 11) return fail(err, errn, "jpeg: DC difference of %d bits", s);
-  if (s) pred += receive_extend(br, s);
-  if (pred < -32768 || pred > 32767) return fail(err, errn, "jpeg: DC value out of range");
-  blk[0] = (int16_t)pred;
-  for (int k = 1; k < 64;) {
-    if (br.bits < 32) br.fill();
-    const int f = ac.fast_ac[br.peek(kLookBits)];
-    if (f) {                        // run, size and value in one step
-      k += (f >> 4) & 15;
-      if (k > 63) return fail(err, errn, "jpeg: coefficient index past 63");
-      blk[kNatural[k++]] = (int16_t)(f >> 8);
-      br.drop(f & 15);
-      continue;
-    }
-    const int rs = decode_symbol(br, ac);
-    if (rs < 0) return fail(err, errn, "jpeg: AC code not in its table");
-    const int r = rs >> 4;
-    s = rs & 15;
-    if (s) {
-      k += r;
-      if (k > 63) return fail(err, errn, "jpeg: coefficient index past 63");
-      blk[kNatural[k]] = (int16_t)receive_extend(br, s);
-      ++k;
-    } else if (r == 15) {
-      k += 16;
-      if (k > 64) return fail(err, errn, "jpeg: zero run past coefficient 63");
-    } else {
-      break;                        // EOB (r < 15 with s == 0 is read as one, as libjpeg does)
-    }
-  }
-  if (br.bits < br.pad) return fail(err, errn, "jpeg: scan data ends inside a block");
-  return 0;
-}
 
 // the caller's `info` against what these bytes parse to
 inline bool same_info(const dspn_jpeg_info &info, const dspn_jpeg_info &I) {
@@ -337,6 +249,19 @@ inline bool same_info(const dspn_jpeg_info &info, const dspn_jpeg_info &I) {
   return same;
 }
 
+// decode_block straight into the output plane (the caller clears the block)
+struct PlaneSink {
+  int16_t *blk;
+  inline void set(int at, int v) { blk[at] = (int16_t)v; }
+};
+
+// the DSPN_JPEG_BAD_ codes decode_block returns, in the host pass's words
+static const char *const kBlockError[] = {
+    "ok", "a Huffman code that is not in its table", "a coefficient index or a zero run past 63",
+    "a DC difference of more than 11 bits", "scan data ends inside a block", "", "a DC value out of range"};
+static_assert(sizeof(kBlockError) / sizeof(kBlockError[0]) == DSPN_JPEG_BAD_DC + 1, "one text per code decode_block returns");
+static_assert(Huff::kMaxAcSize == 15, "the text of DSPN_JPEG_BAD_SIZE names DC alone: no AC symbol names more than 15 bits");
+
 inline int entropy_decode(const unsigned char *b, size_t n, const dspn_jpeg_info *info, int16_t *out, char *err, size_t errn) {
   if (!info || !out) return fail(err, errn, "jpeg_entropy_decode: null argument");
   Parsed P;
@@ -344,14 +269,15 @@ inline int entropy_decode(const unsigned char *b, size_t n, const dspn_jpeg_info
   const dspn_jpeg_info &I = P.info;
   if (!I.supported) return fail(err, errn, "jpeg_entropy_decode: unsupported stream (reason %d)", I.reason);
   if (!same_info(*info, I)) return fail(err, errn, "jpeg_entropy_decode: info does not describe these bytes");
-  BitReader br;
-  br.p = b + P.scan_pos;
-  br.end = b + n;
+  FastBitReader br;
+  br.start(b + P.scan_pos, b + n);
   int pred[3] = {0, 0, 0};
   const int nc = I.ncomp;
   const int mcux = I.blocks_w[0] / I.hsamp[0], mcuy = I.blocks_h[0] / I.vsamp[0];
   const int ri = I.restart_interval;
   int until_restart = ri, next_rst = 0;
+  // the walk over the MCUs: run_segment (jpeg_huff.h) has the same one for a single interval, kept apart because the
+  // kernel's code changes when the loop becomes a function shared with this one (profiles/jpeg_entropy_one_core.txt)
   for (int my = 0; my < mcuy; ++my)
     for (int mx = 0; mx < mcux; ++mx) {
       if (ri && until_restart == 0) {
@@ -360,8 +286,7 @@ inline int entropy_decode(const unsigned char *b, size_t n, const dspn_jpeg_info
         if (q >= br.end || *q != 0xFF) return fail(err, errn, "jpeg: missing restart marker %d", next_rst);
         while (q < br.end && *q == 0xFF) ++q;
         if (q >= br.end || *q != 0xD0 + next_rst) return fail(err, errn, "jpeg: missing restart marker %d", next_rst);
-        br.p = q + 1;
-        br.buf = 0; br.bits = 0; br.pad = 0; br.stopped = false;
+        br.start(q + 1, br.end);
         pred[0] = pred[1] = pred[2] = 0;
         next_rst = (next_rst + 1) & 7;
         until_restart = ri;
@@ -372,7 +297,10 @@ inline int entropy_decode(const unsigned char *b, size_t n, const dspn_jpeg_info
         for (int v = 0; v < I.vsamp[c]; ++v)
           for (int h = 0; h < I.hsamp[c]; ++h) {
             const long long blk = (long long)(my * I.vsamp[c] + v) * I.blocks_w[c] + (mx * I.hsamp[c] + h);
-            if (decode_block(br, dc, ac, pred[c], plane + 64 * blk, err, errn)) return kErr;
+            PlaneSink sink = {plane + 64 * blk};
+            memset(sink.blk, 0, 64 * sizeof(int16_t));
+            const int code = hf::decode_block(br, dc, ac, pred[c], kNatural, sink);
+            if (code) return fail(err, errn, "jpeg: %s", kBlockError[code]);
           }
       }
       --until_restart;

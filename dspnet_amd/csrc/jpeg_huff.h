@@ -1,5 +1,8 @@
-// Huffman decoding of ONE restart interval of a baseline JPEG scan (include/dspn_jpeg.h, "entropy pass on the device"), as
-// __host__ __device__ functions: the kernel in jpeg.hip runs this text one interval per lane, the host build
+// Huffman decoding of a baseline JPEG scan (include/dspn_jpeg.h), the only text of it: code derivation and lookahead table,
+// bit reader, decode_symbol, receive_extend, decode_block and the zigzag order, as __host__ __device__ functions.  The host
+// entropy pass (jpeg_host.h) calls decode_block with its own reader and AC-table type from its own walk over the MCUs; the
+// rest of this file is ONE restart interval as the device pass sees it ("entropy pass on the device"), its walk over the
+// interval's MCUs included: the kernel in jpeg.hip runs run_segment one interval per lane, the host build
 // (dspn_jpeg_entropy_decode_segments, tools/jpeg_huff_check.cpp) runs it serially and under the host sanitizers.
 // Nothing here trusts its input: `prepare` checks the descriptors of a sample against the pools, `run_segment` checks the
 // two entries of the segment table it reads, the bit reader never passes the end of its segment, every table index is
@@ -28,7 +31,14 @@ struct Table {
   int valoffset[17];                 // index of the first value of a length minus its first code
   int nvals;                         // < 0: the counts are not those of a prefix code
   unsigned char vals[256];
+  // What decode_block does with this type as its AC table.  The device pass refuses an AC value of more than 10 bits
+  // (DSPN_JPEG_BAD_SIZE): the DCT of 8-bit samples cannot give one.  The host pass (dspn_jpeg::Huff in jpeg_host.h) takes
+  // every size a symbol can name, up to 15.  The difference is kept on purpose, it is not a bug
+  // (tests/test_jpeg_entropy_limits.py pins both sides).
+  static constexpr int kMaxAcSize = 10;
+  static constexpr bool kFastAc = false;
 };
+static_assert(sizeof(Table) == 1424, "Table must not grow: kSlots of them sit in LDS");
 
 // what a lane needs of its sample, checked
 struct Layout {
@@ -150,15 +160,35 @@ DSPN_HD void build_look(Table &t, int first, int step) {
   }
 }
 
+// zigzag position -> natural (row-major) index, by walking the diagonals.  The one definition: dspn_jpeg::kNatural
+// (jpeg_host.h) is this at compile time, the kernel runs it into LDS.
+constexpr DSPN_HD void fill_natural(unsigned char *out /* [64] */) {
+  int r = 0, c = 0;
+  for (int k = 0; k < 64; ++k) {
+    out[k] = (unsigned char)(r * 8 + c);
+    if ((r + c) & 1) {               // down and to the left
+      if (r == 7) ++c; else if (c == 0) ++r; else { ++r; --c; }
+    } else {                         // up and to the right
+      if (c == 7) ++r; else if (r == 0) ++c; else { --r; ++c; }
+    }
+  }
+}
+
 // MSB-first bit reader over [p, end): the top `bits` bits of `buf` are valid.  At a marker or at the end it feeds zero bits
 // and counts them in `pad`; a decoder that has consumed padding (bits < pad) has run off the data.  Byte by byte: lanes of a
-// wave sit at unrelated places of unrelated segments, so there is nothing to gain from wider loads.
+// wave sit at unrelated places of unrelated segments, so there is nothing to gain from wider loads.  (The host pass reads
+// through dspn_jpeg::FastBitReader, which puts a wide load in front of this loop.)
 struct BitReader {
   const unsigned char *p, *end;
   uint64_t buf;
   int bits, pad;
-  bool stopped;
+  bool stopped;                      // at a marker or at the end
 
+  DSPN_HD void start(const unsigned char *from, const unsigned char *to) {
+    p = from;
+    end = to;
+    buf = 0; bits = 0; pad = 0; stopped = false;
+  }
   DSPN_HD void fill() {              // -> bits >= 57
     while (bits <= 56) {
       unsigned v = 0;
@@ -181,7 +211,8 @@ struct BitReader {
   DSPN_HD void drop(int k) { buf <<= k; bits -= k; }
 };
 
-DSPN_HD int decode_symbol(BitReader &br, const Table &h) {   // needs bits >= 16; -1: no such code
+template <class Reader>
+DSPN_HD int decode_symbol(Reader &br, const Table &h) {      // needs bits >= 16; -1: no such code
   const unsigned e = h.look[br.peek(kLookBits)];
   if (e) { br.drop((int)(e >> 8)); return (int)(e & 255u); }
   for (int l = kLookBits + 1; l <= 16; ++l) {
@@ -196,16 +227,21 @@ DSPN_HD int decode_symbol(BitReader &br, const Table &h) {   // needs bits >= 16
   return -1;
 }
 
-DSPN_HD int receive_extend(BitReader &br, int s) {           // 1 <= s <= 15, needs bits >= s
+template <class Reader>
+DSPN_HD int receive_extend(Reader &br, int s) {              // 1 <= s <= 15, needs bits >= s
   const int v = (int)br.peek(s);
   br.drop(s);
   return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
-// One block into `sink` (cleared by the caller).  The 64 values of a block are addressed by a zigzag position that only the
-// data knows, so they must not be a per-lane array (it would live in scratch): Sink is LDS on the device, 64 words on the host.
-template <class Sink>
-DSPN_HD int decode_block(BitReader &br, const Table &dc, const Table &ac, int &pred, const unsigned char *natural, Sink &sink) {
+// One block into `sink` (cleared by the caller; decode_block only calls sink.set(natural index, value)).  The 64 values of a
+// block are addressed by a zigzag position that only the data knows, so they must not be a per-lane array (it would live in
+// scratch): Sink is LDS on the device, memory on the host.
+// What differs between the passes is a compile-time property of the AC table's type: AcTable::kMaxAcSize, and
+// AcTable::kFastAc, whether the table has fast_ac[], (value << 8) | (run << 4) | bits for a window that holds a whole code
+// AND its magnitude bits -- run, size and value in one step.
+template <class Reader, class AcTable, class Sink>
+DSPN_HD int decode_block(Reader &br, const Table &dc, const AcTable &ac, int &pred, const unsigned char *natural, Sink &sink) {
   if (br.bits < 32) br.fill();
   int s = decode_symbol(br, dc);
   if (s < 0) return DSPN_JPEG_BAD_CODE;
@@ -215,6 +251,16 @@ DSPN_HD int decode_block(BitReader &br, const Table &dc, const Table &ac, int &p
   sink.set(0, pred);
   for (int k = 1; k < 64;) {
     if (br.bits < 32) br.fill();
+    if constexpr (AcTable::kFastAc) {
+      const int f = ac.fast_ac[br.peek(kLookBits)];
+      if (f) {
+        k += (f >> 4) & 15;
+        if (k > 63) return DSPN_JPEG_BAD_INDEX;
+        sink.set(natural[k++], f >> 8);
+        br.drop(f & 15);
+        continue;
+      }
+    }
     const int rs = decode_symbol(br, ac);
     if (rs < 0) return DSPN_JPEG_BAD_CODE;
     const int r = rs >> 4;
@@ -222,7 +268,7 @@ DSPN_HD int decode_block(BitReader &br, const Table &dc, const Table &ac, int &p
     if (s) {
       k += r;
       if (k > 63) return DSPN_JPEG_BAD_INDEX;
-      if (s > 10) return DSPN_JPEG_BAD_SIZE;
+      if (s > AcTable::kMaxAcSize) return DSPN_JPEG_BAD_SIZE;
       sink.set(natural[k], receive_extend(br, s));
       ++k;
     } else if (r == 15) {
@@ -247,9 +293,7 @@ DSPN_HD int run_segment(const Layout &L, int i, const unsigned char *bytes, cons
   for (int c = 0; c < 3; ++c)
     if (c < L.ncomp && (tables[L.dc_slot[c]].nvals < 0 || tables[L.ac_slot[c]].nvals < 0)) return DSPN_JPEG_BAD_SEGMENT;
   BitReader br;
-  br.p = bytes + L.data_offset + a;
-  br.end = bytes + L.data_offset + b;
-  br.buf = 0; br.bits = 0; br.pad = 0; br.stopped = false;
+  br.start(bytes + L.data_offset + a, bytes + L.data_offset + b);
   const int first = i * L.interval;
   const int n = L.mcus - first < L.interval ? L.mcus - first : L.interval;
   int my = first / L.mcus_w, mx = first - my * L.mcus_w;
@@ -281,19 +325,6 @@ DSPN_HD int run_segment(const Layout &L, int i, const unsigned char *bytes, cons
   const bool at_marker = t + 1 == br.end && t > br.p && (*t & 0xF8) == 0xD0;
   if (!(i + 1 == L.segments ? at_end : at_marker)) return DSPN_JPEG_BAD_REST;
   return 0;
-}
-
-// zigzag position -> natural (row-major) index, by walking the diagonals: dspn_jpeg::kNatural, made where a table cannot be shared
-DSPN_HD void fill_natural(unsigned char *out /* [64] */) {
-  int r = 0, c = 0;
-  for (int k = 0; k < 64; ++k) {
-    out[k] = (unsigned char)(r * 8 + c);
-    if ((r + c) & 1) {               // down and to the left
-      if (r == 7) ++c; else if (c == 0) ++r; else { ++r; --c; }
-    } else {                         // up and to the right
-      if (c == 7) ++r; else if (r == 0) ++c; else { --r; ++c; }
-    }
-  }
 }
 
 DSPN_HD int status_word(int code, int segment) {

@@ -64,9 +64,6 @@ static int run(const unsigned char *src, size_t n, std::vector<int16_t> *keep, T
 
 int main(int argc, char **argv) {
   if (argc < 2) { fprintf(stderr, "usage: %s stream.jpg ...\n", argv[0]); return 2; }
-  unsigned char natural[64];
-  dspn_jpeg_huff::fill_natural(natural);
-  if (memcmp(natural, dspn_jpeg::kNatural, 64)) { fprintf(stderr, "fill_natural is not the zigzag order\n"); return 1; }
   Tally tally;
   for (int a = 1; a < argc; ++a) {
     FILE *f = fopen(argv[a], "rb");
