@@ -418,14 +418,16 @@ __global__ __launch_bounds__(256) void absmax_affine_bound_kernel(const float *_
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
   float b = 0.f;
-  for (int c = threadIdx.x; c < C; c += 256) b = fmaxf(b, fabsf(scale[c]) * m + fabsf(shift[c]));
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float t = fabsf(scale[c]) * m + fabsf(shift[c]);
+    b = fmaxf(b, t == t ? t : INFINITY);                // a NaN coefficient: no finite bound exists (fmaxf alone would skip it)
+  }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) b = fmaxf(b, __shfl_xor(b, o, 64));
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = b;
   __syncthreads();
   if (threadIdx.x == 0) {
     b = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-    if (!(b == b)) b = INFINITY;                        // a NaN coefficient: no finite bound exists
     if (b > 0.f) atomicMax(out, __float_as_uint(b));
   }
 }

@@ -188,7 +188,8 @@ def absmax(x, in_affine=None, out=None):
     """largest magnitude of the float32 tensor x (last dimension = channels, a multiple of 4) -- of (relu)(x * scale + shift)
     when in_affine = (scale, shift, relu) is given -- as 64 partial maxima in device memory: the `*_absmax` operand of the
     "f16x2" math (`.max()` of the result is the magnitude).  out: an existing 64-element float32 tensor to take the maxima
-    INTO (it is not zeroed here)"""
+    INTO (it is not zeroed here).  NaNs never enter the block: a NaN element or coefficient contributes nothing (fmaxf skips
+    it; behind the ReLU it is 0); an infinity makes its workgroup's slot inf, the other slots keep their finite maxima"""
     assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] % 4 == 0
     if out is None:
         out = zeros(ABSMAX_SLOTS, device=x.device)
@@ -229,7 +230,8 @@ def absmin_rows_batch(table, n, total):
 
 
 def tile_minmax(x, tile_rows, out):
-    """out (tiles, 2, C): smallest / largest value of each channel over each tile of `tile_rows` rows of x (..., C)"""
+    """out (tiles, 2, C): smallest / largest value of each channel over each tile of `tile_rows` rows of x (..., C); NaNs are
+    skipped, a channel that is all NaN in a tile gives +inf / -inf"""
     C = x.shape[-1]
     check(L().dspn_tile_minmax_f32(ptr(x), _rows(x), C, int(tile_rows), ptr(out), stream()), "tile_minmax")
     return out
@@ -648,7 +650,8 @@ def bn_apply_planes(x, scale, shift, y_absmax, relu=False, out=None):
 
 def absmax_affine_bound(scale, shift, x_absmax, out):
     """out (64-float magnitude block, not zeroed here) max= max_c |scale[c]| * M + |shift[c]|, M = the magnitude in x_absmax:
-    a bound of |(relu)(x * scale + shift)| without a pass over x"""
+    a bound of |(relu)(x * scale + shift)| without a pass over x.  A NaN coefficient, or an inf slot in x_absmax, gives +inf
+    (one slot of out is written: a convolution whose block holds no other finite slot then runs unscaled)"""
     assert scale.numel() == shift.numel() and x_absmax.numel() == out.numel() == ABSMAX_SLOTS
     check(L().dspn_absmax_affine_bound_f32(ptr(scale), ptr(shift), scale.numel(), ptr(x_absmax), ptr(out), stream()),
           "absmax_affine_bound")
