@@ -18,6 +18,7 @@
 
 #include "dspn_common.h"
 #include "jpeg_encode_host.h"
+#include "jpeg_encode_sample.h"
 
 namespace {
 
@@ -32,23 +33,9 @@ struct ChannelMap { int r, g, b; };
 
 // true when every index the kernels derive from `s` stays inside images and coefs / workspace (coef_count)
 __device__ bool sample_ok(const dspn_jpeg_enc_sample &s, const Pools &pl) {
-  if (s.skip) return false;
-  if (s.width < 1 || s.height < 1 || s.width > 65535 || s.height > 65535) return false;
-  if (s.ncomp != 1 && s.ncomp != 3) return false;
-  int hs = 1, vs = 1;
-  if (s.ncomp == 3) {
-    hs = s.hsamp; vs = s.vsamp;
-    if (!((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))) return false;
-  }
-  if (s.img_offset < 0 || s.img_offset > pl.images_bytes - (long long)s.ncomp * s.width * s.height) return false;
-  for (int c = 0; c < s.ncomp; ++c) {
-    const int cw = c ? (s.width + hs - 1) / hs : s.width, ch = c ? (s.height + vs - 1) / vs : s.height;
-    const int bw = s.blocks_w[c], bh = s.blocks_h[c];
-    if (bw != (cw + 7) / 8 || bh != (ch + 7) / 8) return false;      // 1 .. 8192 each
-    const long long off = s.coef_offset[c];
-    if (off < 0 || (off & 63) || off > pl.coef_count - 64LL * bw * bh) return false;
-  }
-  return true;
+  int hs, vs;
+  if (!dspn_jpeg_enc::coefs_ok(s, pl.coef_count, hs, vs)) return false;
+  return s.img_offset >= 0 && s.img_offset <= pl.images_bytes - (long long)s.ncomp * s.width * s.height;
 }
 
 // first[b] = units of samples 0 .. b - 1 (first[B] = all); units(s) is called for valid samples only

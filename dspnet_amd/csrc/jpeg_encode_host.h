@@ -115,8 +115,8 @@ struct Codes {
   unsigned char size[256];          // 0: the symbol has no code
 };
 
-inline void build_codes(Codes &t, const unsigned char *bits, const unsigned char *vals) {
-  memset(&t, 0, sizeof(t));
+constexpr void build_codes(Codes &t, const unsigned char *bits, const unsigned char *vals) {   // constexpr: the device pass builds its tables at compile time
+  t = Codes{};
   int code = 0, k = 0;
   for (int l = 1; l <= 16; ++l) {
     for (int i = 0; i < bits[l - 1]; ++i, ++k) {
@@ -202,37 +202,27 @@ inline void put_dht(Out &o, int tc_th, const unsigned char *bits, const unsigned
   for (int i = 0; i < n; ++i) o.put(vals[i]);
 }
 
-// -> 0, kErr, or kTooSmall (the file needs *length > capacity bytes; out[0 .. capacity - 1] hold its beginning)
-// restart_interval: MCUs between restart markers, 0: none (and no DRI segment)
-inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, int restart_interval, unsigned char *out,
-                          size_t capacity, size_t *length, char *err, size_t errn) {
-  if (!coefs || !s || !length || (!out && capacity)) return fail(err, errn, "jpeg_entropy_encode: null argument");
-  *length = 0;
+// what both the file writer and the header writer ask of a descriptor; g receives its geometry
+inline int check_descriptor(const char *who, const dspn_jpeg_enc_sample *s, int restart_interval, Geometry &g, char *err, size_t errn) {
   if (restart_interval < 0 || restart_interval > 65535)
-    return fail(err, errn, "jpeg_entropy_encode: a restart interval of %d MCUs (0..65535)", restart_interval);
-  Geometry g;
+    return fail(err, errn, "%s: a restart interval of %d MCUs (0..65535)", who, restart_interval);
   if (geometry(s->width, s->height, s->ncomp, s->hsamp, s->vsamp, g, err, errn)) return kErr;
   for (int c = 0; c < g.ncomp; ++c) {
     if (s->blocks_w[c] != g.bw[c] || s->blocks_h[c] != g.bh[c])
-      return fail(err, errn, "jpeg_entropy_encode: component %d has a grid of %d x %d blocks, its real grid is %d x %d", c,
+      return fail(err, errn, "%s: component %d has a grid of %d x %d blocks, its real grid is %d x %d", who, c,
                   s->blocks_w[c], s->blocks_h[c], g.bw[c], g.bh[c]);
     if (s->coef_offset[c] < 0 || (s->coef_offset[c] & 63))
-      return fail(err, errn, "jpeg_entropy_encode: coef_offset[%d] must be a multiple of 64, >= 0", c);
+      return fail(err, errn, "%s: coef_offset[%d] must be a multiple of 64, >= 0", who, c);
     for (int i = 0; i < 64; ++i)
-      if (s->quant[c][i] == 0) return fail(err, errn, "jpeg_entropy_encode: a zero in the quantisation table of component %d", c);
+      if (s->quant[c][i] == 0) return fail(err, errn, "%s: a zero in the quantisation table of component %d", who, c);
   }
   if (g.ncomp == 3 && memcmp(s->quant[1], s->quant[2], 64))
-    return fail(err, errn, "jpeg_entropy_encode: the two chroma components must share one quantisation table");
+    return fail(err, errn, "%s: the two chroma components must share one quantisation table", who);
+  return 0;
+}
 
-  Codes dc[2], ac[2];
-  build_codes(dc[0], kDcLumBits, kDcVals);
-  build_codes(ac[0], kAcLumBits, kAcLumVals);
-  build_codes(dc[1], kDcChrBits, kDcVals);
-  build_codes(ac[1], kAcChrBits, kAcChrVals);
-
-  Out o;
-  o.p = out;
-  o.cap = capacity;
+// SOI through the SOS header: everything in front of the first byte of the scan
+inline void put_headers(Out &o, const dspn_jpeg_enc_sample *s, const Geometry &g, int restart_interval) {
   o.put2(0xFFD8);
   o.put2(0xFFE0); o.put2(16);
   for (const char *j = "JFIF"; *j; ++j) o.put((unsigned char)*j);
@@ -256,6 +246,46 @@ inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, i
   o.put2(0xFFDA); o.put2((unsigned)(6 + 2 * g.ncomp)); o.put((unsigned)g.ncomp);
   for (int c = 0; c < g.ncomp; ++c) { o.put((unsigned)(c + 1)); o.put(c ? 0x11u : 0x00u); }
   o.put(0); o.put(63); o.put(0);
+}
+
+// the headers alone (dspn_jpeg_encode_headers) -> 0, kErr, or kTooSmall as below
+inline int encode_headers(const dspn_jpeg_enc_sample *s, int restart_interval, unsigned char *out, size_t capacity, size_t *length,
+                          char *err, size_t errn) {
+  if (!s || !length || (!out && capacity)) return fail(err, errn, "jpeg_encode_headers: null argument");
+  *length = 0;
+  Geometry g;
+  if (check_descriptor("jpeg_encode_headers", s, restart_interval, g, err, errn)) return kErr;
+  Out o;
+  o.p = out;
+  o.cap = capacity;
+  put_headers(o, s, g, restart_interval);
+  *length = o.n;
+  if (o.n > capacity) {
+    fail(err, errn, "jpeg_encode_headers: the headers need %zu bytes, the buffer holds %zu", o.n, capacity);
+    return kTooSmall;
+  }
+  return 0;
+}
+
+// -> 0, kErr, or kTooSmall (the file needs *length > capacity bytes; out[0 .. capacity - 1] hold its beginning)
+// restart_interval: MCUs between restart markers, 0: none (and no DRI segment)
+inline int entropy_encode(const int16_t *coefs, const dspn_jpeg_enc_sample *s, int restart_interval, unsigned char *out,
+                          size_t capacity, size_t *length, char *err, size_t errn) {
+  if (!coefs || !s || !length || (!out && capacity)) return fail(err, errn, "jpeg_entropy_encode: null argument");
+  *length = 0;
+  Geometry g;
+  if (check_descriptor("jpeg_entropy_encode", s, restart_interval, g, err, errn)) return kErr;
+
+  Codes dc[2], ac[2];
+  build_codes(dc[0], kDcLumBits, kDcVals);
+  build_codes(ac[0], kAcLumBits, kAcLumVals);
+  build_codes(dc[1], kDcChrBits, kDcVals);
+  build_codes(ac[1], kAcChrBits, kAcChrVals);
+
+  Out o;
+  o.p = out;
+  o.cap = capacity;
+  put_headers(o, s, g, restart_interval);
 
   int pred[3] = {0, 0, 0};
   int until_restart = restart_interval, next_rst = 0;

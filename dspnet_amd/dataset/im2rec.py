@@ -76,15 +76,16 @@ def _decode(payloads, device):
     return out
 
 
-def write_records(prefix, root, quality=95, pack_label=True, pass_through=False, batch=16, device=None, restart_interval=0):
+def write_records(prefix, root, quality=95, pack_label=True, pass_through=False, batch=16, device=None, restart_interval=0,
+                  device_entropy=False):
     """reads `prefix`.lst and writes `prefix`.rec / `prefix`.idx through MXIndexedRecordIO, one record per line, keyed by
     the line's index, in list order.  pass_through: the file's bytes are packed as they are.  Otherwise each image is decoded
     to three channels (on the device where it is a JPEG or PNG a device decode supports, with Pillow otherwise) and re-encoded on
     the device, `batch` images per call, as `recordio.pack_img(header, image, quality)` would encode it.  An unreadable
     file is an error (the reference prints and skips it).  No resizing and no cropping (see the module text).
     restart_interval=n: the re-encoded files carry a restart marker every n MCUs (jpeg_encode.encode_batch), which lets the
-    iterators decode them entirely on the device (device_entropy=True); the pixels they decode to are the same.  -> the
-    number of records written."""
+    iterators decode them entirely on the device (device_entropy=True); the pixels they decode to are the same.
+    device_entropy: encode_batch's switch for the Huffman pass on the device (the same bytes).  -> the number of records written."""
     items = read_list(prefix + ".lst")
     if not pass_through:
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -101,7 +102,7 @@ def write_records(prefix, root, quality=95, pack_label=True, pass_through=False,
                 packed = [recordio.pack(h, p) for h, p in zip(headers, payloads)]
             else:
                 files = jpeg_encode.encode_batch(_decode(payloads, device), quality=quality, subsampling="4:2:0",
-                                                 restart_interval=restart_interval)
+                                                 restart_interval=restart_interval, device_entropy=device_entropy)
                 packed = [recordio.pack(h, f) for h, f in zip(headers, files)]
             for (index, _, _), s in zip(chunk, packed):
                 rec.write_idx(index, s)
@@ -120,8 +121,10 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--restart-interval", type=int, default=0,
                     help="MCUs between restart markers in the re-encoded files (0: none); see DESIGN.md for the choice")
+    ap.add_argument("--device-entropy", action="store_true", help="Huffman-code the re-encoded files on the device too (the same bytes)")
     a = ap.parse_args(argv)
-    n = write_records(a.prefix, a.root, a.quality, a.pack_label, a.pass_through, a.batch, restart_interval=a.restart_interval)
+    n = write_records(a.prefix, a.root, a.quality, a.pack_label, a.pass_through, a.batch, restart_interval=a.restart_interval,
+                      device_entropy=a.device_entropy)
     print("%d records -> %s.rec" % (n, a.prefix))
 
 

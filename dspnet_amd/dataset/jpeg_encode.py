@@ -1,11 +1,12 @@
 """JPEG encode split between device and host (include/dspn_jpeg_encode.h), the mirror image of dataset/jpeg.py: the device
 converts the colours, downsamples the chroma, runs the forward DCT and quantises for a whole batch of images of mixed sizes
 in one call of two launches; the host does the serial rest -- markers and Huffman coding -- per image on a thread pool
-(ctypes releases the GIL around it).  The files equal what Pillow writes for the same pixels and settings
+(ctypes releases the GIL around it), or, with device_entropy=True, the device codes the scans as well and the host is left
+with the marker segments and a join.  The files equal what Pillow writes for the same pixels and settings
 (`Image.fromarray(x).save(f, format="JPEG", quality=q, subsampling=s)`: libjpeg-turbo, standard Huffman tables) byte for byte.
 
 `encode_batch` and `quant_tables` are the public use; `fill_sample`, `encode_blocks` and `entropy_encode` are the three C
-entry points one by one."""
+entry points one by one, `entropy_scan_batch`, `entropy_write_batch` and `headers` those of the device entropy pass."""
 import ctypes as _c
 from concurrent.futures import ThreadPoolExecutor
 
@@ -84,13 +85,83 @@ def entropy_encode(coefs, sample, capacity=None, restart_interval=0):
     return out[:n.value].tobytes()
 
 
+def headers(sample, restart_interval=0):
+    """dspn_jpeg_encode_headers: SOI through the SOS header of entropy_encode's file, as bytes"""
+    rec = np.array([sample], SAMPLE)
+    lib = _lib.lib()
+    n = _c.c_size_t(0)
+    out = np.empty(1024, np.uint8)                             # 623 bytes for colour with a DRI segment
+    _lib.check(lib.dspn_jpeg_encode_headers(rec.ctypes.data, int(restart_interval), out.ctypes.data, out.size, _c.byref(n)),
+               "jpeg_encode_headers")
+    return out[:n.value].tobytes()
+
+
+def entropy_scan_batch(coefs, samples, intervals, stream=None):
+    """dspn_jpeg_entropy_encode_scan_batch: coefs the int16 device pool, samples a uint8 device tensor of B descriptors,
+    intervals an int32 device tensor of B restart intervals in MCUs.  -> (scan_bytes int64 (B,), status int32 (B,), workspace),
+    all on the device; the workspace goes to entropy_write_batch as it is"""
+    dev = coefs.device
+    B = samples.numel() // SAMPLE.itemsize
+    ws_bytes = _lib.lib().dspn_jpeg_entropy_encode_workspace_bytes(coefs.numel(), B)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    sizes = torch.empty(B, dtype=torch.int64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().dspn_jpeg_entropy_encode_scan_batch(coefs.data_ptr(), coefs.numel(), samples.data_ptr(), intervals.data_ptr(), B,
+                                                              sizes.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes, st),
+               "jpeg_entropy_encode_scan")
+    return sizes, status, ws
+
+
+def entropy_write_batch(coef_count, offsets, out, ws, stream=None):
+    """dspn_jpeg_entropy_encode_write_batch: offsets an int64 device tensor of B byte offsets into the uint8 device tensor
+    out, ws the workspace of entropy_scan_batch over coef_count coefficients"""
+    st = torch.cuda.current_stream(out.device).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().dspn_jpeg_entropy_encode_write_batch(int(coef_count), offsets.numel(), offsets.data_ptr(), out.data_ptr(),
+                                                               out.numel(), ws.data_ptr(), ws.numel(), st),
+               "jpeg_entropy_encode_write")
+
+
 def mcus_per_row(sample):
     """MCUs in one row of the image a filled descriptor describes"""
     hs = int(sample["hsamp"]) if int(sample["ncomp"]) == 3 else 1
     return (int(sample["width"]) + 8 * hs - 1) // (8 * hs)
 
 
-def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", threads=8, restart_interval=0, restart_rows=0):
+def _interval_of(sample, restart_interval, restart_rows):
+    """the restart interval of one image in MCUs; libjpeg caps an interval given in rows at 65535 MCUs"""
+    return min(int(restart_rows) * mcus_per_row(sample), 65535) if restart_rows else int(restart_interval)
+
+
+def _device_scans(samples, desc, coefs, restart_interval, restart_rows):
+    """encode_batch's device_entropy=True: the coefficients stay on the device, the coded scans come down"""
+    dev = coefs.device
+    ris = [_interval_of(s, restart_interval, restart_rows) for s in samples]
+    intervals = torch.tensor(ris, dtype=torch.int32).to(dev)
+    sizes, status, ws = entropy_scan_batch(coefs, desc, intervals)
+    sizes, status = sizes.cpu().numpy(), status.cpu().numpy()  # the one small copy: 12 bytes per image
+    for k in np.flatnonzero(status == 2):                      # the host pass words the refusal
+        s = samples[k]
+        lo = min(int(s["coef_offset"][c]) for c in range(int(s["ncomp"])))
+        hi = max(int(s["coef_offset"][c]) + 64 * int(s["blocks_w"][c]) * int(s["blocks_h"][c]) for c in range(int(s["ncomp"])))
+        local = s.copy()
+        local["coef_offset"][:int(s["ncomp"])] -= lo
+        entropy_encode(coefs[lo:hi].cpu().numpy(), local, restart_interval=ris[k])
+    if status.any():
+        raise _lib.DspnError("jpeg_encode: the device entropy pass refused images %s (status %s)"
+                             % (np.flatnonzero(status).tolist(), status[status != 0].tolist()))
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    scans = torch.empty(max(int(offsets[-1]), 1), dtype=torch.uint8, device=dev)
+    entropy_write_batch(coefs.numel(), torch.from_numpy(offsets[:-1].copy()).to(dev), scans, ws)
+    host = torch.empty(scans.numel(), dtype=torch.uint8).pin_memory()
+    host.copy_(scans, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    data = host.numpy()
+    return [headers(s, ri) + data[a:b].tobytes() + b"\xff\xd9" for s, ri, a, b in zip(samples, ris, offsets[:-1], offsets[1:])]
+
+
+def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", threads=8, restart_interval=0, restart_rows=0,
+                 device_entropy=False):
     """list of uint8 device tensors, (h, w, 3) or (h, w), of any mix of sizes -> list of JPEG files as bytes, each equal
     to Pillow's `Image.fromarray(x).save(f, format="JPEG", quality=quality, subsampling=subsampling)` (x in RGB order;
     channel_order="bgr" reads OpenCV's order instead; a (h, w) image is greyscale, for which subsampling says nothing).
@@ -98,7 +169,10 @@ def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", t
     the images on `threads` threads.
     restart_interval=n writes a restart marker every n MCUs (Pillow's restart_marker_blocks=n), restart_rows=r every r
     MCU rows of each image (restart_marker_rows=r); at most one of the two.  Such files decode entirely on the device
-    (dataset/jpeg.py, device_entropy=True) when the interval is at most jpeg.DEVICE_MAX_INTERVAL MCUs."""
+    (dataset/jpeg.py, device_entropy=True) when the interval is at most jpeg.DEVICE_MAX_INTERVAL MCUs.
+    device_entropy=True: the scans are Huffman-coded on the device too (dspn_jpeg_entropy_encode_scan_batch / _write_batch):
+    the sizes come down (12 bytes per image), then the coded scans in one copy instead of the coefficients; the host
+    writes the marker segments around them.  The files are the same bytes."""
     if restart_interval and restart_rows:
         raise ValueError("restart_interval and restart_rows: at most one of the two")
     if not 0 <= int(restart_interval) <= 65535 or int(restart_rows) < 0:
@@ -111,7 +185,8 @@ def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", t
     if not images:
         return []
     if len(images) > 1024:
-        return sum((encode_batch(images[k:k + 1024], quality, subsampling, channel_order, threads, restart_interval, restart_rows)
+        return sum((encode_batch(images[k:k + 1024], quality, subsampling, channel_order, threads, restart_interval, restart_rows,
+                                 device_entropy)
                     for k in range(0, len(images), 1024)), [])
     tables = quant_tables(quality)
     dev = images[0].device
@@ -131,14 +206,15 @@ def encode_batch(images, quality=95, subsampling="4:2:0", channel_order="rgb", t
         desc = torch.from_numpy(samples.view(np.uint8).reshape(-1)).to(dev)
         coefs = torch.empty(co, dtype=torch.int16, device=dev)
         ws = encode_blocks(pool, desc, coefs, channel_order)
+        if device_entropy:
+            return _device_scans(samples, desc, coefs, restart_interval, restart_rows)
         host = torch.empty(co, dtype=torch.int16).pin_memory()
         host.copy_(coefs, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()           # pool, descriptors and workspace go out of scope after this
     del ws
     cnp = host.numpy()
-    def one(s):                                                # libjpeg caps an interval given in rows at 65535 MCUs
-        ri = min(int(restart_rows) * mcus_per_row(s), 65535) if restart_rows else int(restart_interval)
-        return entropy_encode(cnp, s, restart_interval=ri)
+    def one(s):
+        return entropy_encode(cnp, s, restart_interval=_interval_of(s, restart_interval, restart_rows))
 
     if threads <= 1 or len(images) == 1:
         return [one(s) for s in samples]

@@ -180,10 +180,11 @@ def pack_img(header, img_bgr, quality=95, img_fmt=".jpg"):
     return pack(header, buf.getvalue())
 
 
-def pack_img_batch(headers, images_bgr, quality=95, restart_interval=0):
+def pack_img_batch(headers, images_bgr, quality=95, restart_interval=0, device_entropy=False):
     """pack_img for a batch of (h, w, 3) BGR uint8 DEVICE tensors of any mix of sizes, the JPEG encode on the device
     (dataset/jpeg_encode.py): element k equals pack_img(headers[k], images_bgr[k].cpu().numpy(), quality).
-    restart_interval=n: a restart marker every n MCUs, as jpeg_encode.encode_batch writes them (the same pixels decode)"""
+    restart_interval=n: a restart marker every n MCUs, as jpeg_encode.encode_batch writes them (the same pixels decode);
+    device_entropy: its switch for the Huffman pass on the device (the same bytes)"""
     from . import jpeg_encode
     headers, images_bgr = list(headers), list(images_bgr)
     if len(headers) != len(images_bgr):
@@ -192,5 +193,5 @@ def pack_img_batch(headers, images_bgr, quality=95, restart_interval=0):
         if im.dim() != 3:
             raise ValueError("pack_img_batch: image %d is not (h, w, 3) BGR, got %s" % (k, tuple(im.shape)))
     files = jpeg_encode.encode_batch(images_bgr, quality=quality, subsampling="4:2:0", channel_order="bgr",
-                                     restart_interval=restart_interval)
+                                     restart_interval=restart_interval, device_entropy=device_entropy)
     return [pack(h, f) for h, f in zip(headers, files)]

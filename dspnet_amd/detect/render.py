@@ -299,16 +299,17 @@ def save_pngs(paths, tensors, compress_level=6):
             f.write(data)
 
 
-def save_jpeg(path, image, quality=95):
+def save_jpeg(path, image, quality=95, device_entropy=False):
     """(H, W, 3) RGB or (H, W) grey uint8 tensor -> baseline JPEG file (4:2:0 for colour), the file Pillow would write for
     the same pixels and quality.  The encode runs on the device (dataset/jpeg_encode.py: colour conversion, downsampling,
-    DCT and quantisation there, Huffman coding on the host); a host tensor or array is uploaded to the current device first."""
+    DCT and quantisation there, Huffman coding on the host, or on the device as well with device_entropy=True: the same bytes);
+    a host tensor or array is uploaded to the current device first."""
     from ..dataset import jpeg_encode
     t = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
     if t.dtype != torch.uint8 or not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)):
         raise _lib.DspnError("save_jpeg: (H, W) or (H, W, 3) uint8, got %s %s" % (t.dtype, tuple(t.shape)))
     if not t.is_cuda:
         t = t.to(torch.device("cuda", torch.cuda.current_device()))
-    (data,) = jpeg_encode.encode_batch([t.detach()], quality=quality)
+    (data,) = jpeg_encode.encode_batch([t.detach()], quality=quality, device_entropy=device_entropy)
     with open(path, "wb") as f:
         f.write(data)

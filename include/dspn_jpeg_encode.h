@@ -102,6 +102,54 @@ int dspn_jpeg_entropy_encode(const short *coefs, const dspn_jpeg_enc_sample *s, 
 int dspn_jpeg_entropy_encode_restart(const short *coefs, const dspn_jpeg_enc_sample *s, int restart_interval,
                                      unsigned char *out, size_t capacity, size_t *length);
 
+/* SOI through the SOS header of the file above: exactly the bytes dspn_jpeg_entropy_encode_restart writes in front of the
+ * first byte of the scan (the DRI segment included when restart_interval is not 0), from the same code.  Host only; the
+ * descriptor is checked as there, capacity and *length behave as there (-2, *length names the need, nothing is written
+ * past out[capacity - 1]).  headers + scan + FF D9 is the file. */
+int dspn_jpeg_encode_headers(const dspn_jpeg_enc_sample *s, int restart_interval, unsigned char *out, size_t capacity,
+                             size_t *length);
+
+/* --- the entropy pass on the device ---------------------------------------------------------------------------------------
+ * The scan of every image of a batch -- the bytes between the SOS header and EOI of dspn_jpeg_entropy_encode_restart's
+ * file, byte for byte -- Huffman-coded on the device from the coefficient pool dspn_jpeg_encode_blocks_batch_u8 left.
+ * In encoding only the bit position is serial, so the pass works per block slot of the scan (dummy blocks included) for
+ * every file, with or without restart markers: count the bits of every slot, prefix-sum them within each restart interval
+ * (the whole image when there is none), write every slot's bits at its offset into a zeroed, unstuffed stream whose
+ * intervals each end on a byte padded with 1 bits, count the FF bytes, and write the stuffed bytes and the RSTn markers at
+ * their final places.  Two calls, because the caller sizes and lays out the output between them:
+ *
+ *   dspn_jpeg_entropy_encode_scan_batch : everything up to the FF count.  When `stream` has run it, scan_bytes[i] is the
+ *     exact size of image i's scan and status[i] is 0: ok; 1: the sample is skipped or not trusted (the coefficient-side
+ *     rules of dspn_jpeg_encode_blocks_batch_u8: geometry, real grids, offsets inside coef_count; or a restart interval
+ *     outside 0..65535; or descriptors that overlap so much that the batch names more blocks than coef_count holds);
+ *     2: a coefficient baseline coding cannot carry (a DC difference of more than 11 bits, an AC value of more than 10).
+ *     scan_bytes[i] is 0 unless status[i] is 0.
+ *   dspn_jpeg_entropy_encode_write_batch : image i's scan goes to out[out_offsets[i] .. out_offsets[i] + scan_bytes[i]).
+ *     `workspace` is the one the scan call filled, untouched since; coef_count and B are that call's (a workspace that
+ *     does not say so writes nothing).  An image whose status was not 0
+ *     or whose range does not lie inside [0, out_bytes) writes nothing; no byte outside those ranges is written.
+ *
+ * coefs, samples, restart_intervals (one per image, in MCUs, 0: none), scan_bytes, status, out_offsets, out and workspace
+ * are device memory; coefs and workspace 16-byte aligned, the long long arrays and samples 8-byte aligned.  B <= 1024.
+ * Argument errors are reported before any HIP call.
+ *
+ * Workspace: with n = coef_count / 64 blocks in the pool, a batch has at most n real slots and at most 4 n slots in all (an
+ * MCU of a 2 x 2 image holds four luma slots of which one at least is real; chroma has no dummies).  A real block emits at
+ * most 11 + 11 bits of DC (the longest DC code, the longest difference) and 63 x (16 + 10) bits of AC (a 16-bit code and 10
+ * value bits per coefficient; a ZRL code only where 16 coefficients emit nothing), 1660 bits, and at most 7 bits of
+ * padding: 209 bytes.  A dummy emits a DC code, its difference and EOB, at most 11 + 11 + 4 + 7 bits: 5 bytes.  The
+ * unstuffed stream is therefore at most 209 n + 5 * 3 n bytes; beside it the workspace holds one bit per byte of it
+ * (where a marker goes), 12 bytes per slot (bit count, bit offset), one count per 1024 bytes and per 1024 slots, and a
+ * header of per-image records. */
+size_t dspn_jpeg_entropy_encode_workspace_bytes(long long coef_count, int B);
+
+int dspn_jpeg_entropy_encode_scan_batch(const short *coefs, long long coef_count, const dspn_jpeg_enc_sample *samples,
+                                        const int *restart_intervals, int B, long long *scan_bytes, int *status,
+                                        void *workspace, size_t workspace_bytes, void *stream);
+
+int dspn_jpeg_entropy_encode_write_batch(long long coef_count, int B, const long long *out_offsets, unsigned char *out,
+                                         long long out_bytes, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

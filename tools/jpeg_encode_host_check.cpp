@@ -5,7 +5,8 @@
 // Its coefficients are read back with the decoder's host half, the blocks of the real grids are copied into an exactly-sized
 // heap buffer, and the entropy encoder must reproduce the file byte for byte in an exactly-sized output buffer; then again
 // with every capacity from 0 to one byte short (a write past the capacity is a heap overflow the sanitizer sees), each of
-// which must be refused with the needed size.  The quantisation tables of every quality are formed as well.
+// which must be refused with the needed size.  The header writer alone (encode_headers, with and without a DRI segment) goes
+// through the same capacities and must give the file's prefix.  The quantisation tables of every quality are formed as well.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -68,6 +69,26 @@ int main(int argc, char **argv) {
       free(out);
     }
     free(real);
+    // the headers alone (dspn_jpeg_encode_headers): the file's prefix up to the scan, with and without a DRI segment, at every capacity
+    for (int interval = 0; interval <= 5; interval += 5) {
+      size_t need = 0;
+      if (dspn_jpeg_enc::encode_headers(&s, interval, nullptr, 0, &need, err, sizeof(err)) != dspn_jpeg_enc::kTooSmall || !need) {
+        fprintf(stderr, "%s: the headers' size was not named\n", argv[a]);
+        return 1;
+      }
+      unsigned char *whole = static_cast<unsigned char *>(malloc(need));
+      size_t n = 0;
+      if (dspn_jpeg_enc::encode_headers(&s, interval, whole, need, &n, err, sizeof(err)) || n != need) { fprintf(stderr, "%s: %s\n", argv[a], err); return 1; }
+      if (interval == 0 && (need + 2 > data.size() || memcmp(whole, data.data(), need))) { fprintf(stderr, "%s: the headers are not the file's prefix\n", argv[a]); return 1; }
+      for (size_t cap = 0; cap < need; ++cap) {
+        unsigned char *out = static_cast<unsigned char *>(malloc(cap ? cap : 1));
+        const int rc = dspn_jpeg_enc::encode_headers(&s, interval, out, cap, &n, err, sizeof(err));
+        if (rc != dspn_jpeg_enc::kTooSmall || n != need || memcmp(out, whole, cap)) { fprintf(stderr, "%s: headers at capacity %zu gave status %d\n", argv[a], cap, rc); return 1; }
+        ++refused;
+        free(out);
+      }
+      free(whole);
+    }
     printf("%s: %zu bytes reproduced\n", argv[a], data.size());
   }
   printf("jpeg_encode_host_check: ok (%ld short capacities refused)\n", refused);

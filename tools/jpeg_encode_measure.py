@@ -5,7 +5,9 @@ output.  Everything is generated from seeds; it fails without a GPU.
 
 Per run: the two device launches alone (device events), encode_batch end to end (host clock around a call that ends with
 the files in hand), and Pillow encoding the same images on the same host with the same number of threads, the two
-alternated; the first file is compared with Pillow's before anything is timed."""
+alternated; the first file is compared with Pillow's before anything is timed.  Then the entropy pass on the device
+(device_entropy=True): its files asserted equal, its two calls alone by device events, and encode_batch end to end with the
+switch off and on, alternated."""
 import argparse
 import io
 import os
@@ -116,6 +118,52 @@ def main():
         t0 = time.perf_counter(); list(tp.map(lambda s: je.entropy_encode(hostc, s), samples)); t_ent = time.perf_counter() - t0
     t0 = time.perf_counter(); je.entropy_encode(hostc, samples[0]); t_one = time.perf_counter() - t0
     print("entropy pass alone: %.1f ms per batch on %d threads, %.2f ms for one image on one thread" % (t_ent * 1e3, a.threads, t_one * 1e3))
+
+    # 4: the entropy pass on the device (device_entropy=True): the same files, the launches alone, end to end off / on alternated
+    assert je.encode_batch(images, quality=a.quality, threads=a.threads, device_entropy=True) == files, "device entropy: files differ"
+    intervals = torch.zeros(a.images, dtype=torch.int32, device=dev)
+    sizes, status, ews = je.entropy_scan_batch(coefs, desc, intervals)
+    total = int(sizes.sum().item())
+    assert not status.any().item() and total == sum(len(f) - len(je.headers(s)) - 2 for f, s in zip(files, samples))
+    offsets = (torch.cumsum(sizes, 0) - sizes).contiguous()
+    scans = torch.empty(total, dtype=torch.uint8, device=dev)
+    ews_bytes = lib.dspn_jpeg_entropy_encode_workspace_bytes(co, a.images)
+
+    def scan_call():
+        _lib.check(lib.dspn_jpeg_entropy_encode_scan_batch(coefs.data_ptr(), co, desc.data_ptr(), intervals.data_ptr(), a.images,
+                                                           sizes.data_ptr(), status.data_ptr(), ews.data_ptr(), ews_bytes, st))
+
+    def write_call():
+        _lib.check(lib.dspn_jpeg_entropy_encode_write_batch(co, a.images, offsets.data_ptr(), scans.data_ptr(), total, ews.data_ptr(),
+                                                            ews_bytes, st))
+
+    t_calls = {}
+    for name, fn in (("scan", scan_call), ("write", write_call)):
+        for _ in range(3):
+            fn()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+        ev[0].record()
+        for k in range(reps):
+            fn(); ev[k + 1].record()
+        torch.cuda.synchronize(dev)
+        t_calls[name] = float(np.median([ev[k].elapsed_time(ev[k + 1]) for k in range(reps)]))
+    print("device entropy pass alone: scan call (10 launches) %.3f ms, write call (1 launch) %.3f ms per batch (medians of %d, device "
+          "events); %.1f MB of coefficients read twice, %.2f MB of scans out; workspace %.0f MB"
+          % (t_calls["scan"], t_calls["write"], reps, co * 2 / 1e6, total / 1e6, ews_bytes / 1e6))
+
+    def device():
+        return je.encode_batch(images, quality=a.quality, threads=a.threads, device_entropy=True)
+
+    ours(); device()
+    t = {"host": [], "device": []}
+    for _ in range(a.reps):
+        for name, fn in (("host", ours), ("device", device)):
+            t0 = time.perf_counter(); fn(); t[name].append(time.perf_counter() - t0)
+    hh, dd = np.median(t["host"]) * 1e3, np.median(t["device"]) * 1e3
+    print("encode_batch end to end, host entropy pass on %d threads: %.1f ms per batch (median of %d; runs %s)"
+          % (a.threads, hh, a.reps, ["%.1f" % (x * 1e3) for x in t["host"]]))
+    print("encode_batch end to end, device_entropy=True: %.1f ms per batch (runs %s); ratio host / device %.2f"
+          % (dd, ["%.1f" % (x * 1e3) for x in t["device"]], hh / dd))
 
 
 if __name__ == "__main__":
