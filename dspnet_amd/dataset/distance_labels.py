@@ -64,12 +64,13 @@ def box_distances(disparity, boxes_px, device=None):
     return [distance_from_median(v) for v in q.cpu().tolist()]
 
 
-def save_maps(paths, maps, compress_level=6):
+def save_maps(paths, maps, compress_level=6, device_deflate=False):
     """writes a batch of (hh, ww) uint16 disparity or distance maps (device or host; a (B, hh, ww) tensor or a list) as
-    16-bit greyscale PNG files, the format the dataset keeps them in: one device filter call for the batch (png_encode)"""
+    16-bit greyscale PNG files, the format the dataset keeps them in: one device filter call for the batch (png_encode);
+    device_deflate=True keeps the deflate on the device as well (detect.render.save_pngs' keyword)"""
     from ..detect.render import save_pngs
     maps = list(maps)
     bad = [tuple(m.shape) for m in maps if str(m.dtype).replace("torch.", "") != "uint16" or len(m.shape) != 2]
     if bad:
         raise ValueError("save_maps: (hh, ww) uint16 maps, got %s among them" % (bad[0],))
-    save_pngs(paths, maps, compress_level)
+    save_pngs(paths, maps, compress_level, device_deflate=device_deflate)

@@ -6,7 +6,13 @@ the compression).  The filtered stream inside a file equals the one inside the f
 (level 6, Z_FILTERED), whose output may differ from Pillow's own zlib build by a few bytes, so the files are not compared.
 
 Formats: 8-bit grey from (H, W) uint8, 8-bit RGB from (H, W, 3) uint8, 16-bit grey from (H, W) uint16; not interlaced, no
-ancillary chunks.  `encode_batch` and `filter_batch` are the public use; `filter_into` is the C entry point."""
+ancillary chunks.  `encode_batch` and `filter_batch` are the public use; `filter_into` is the C entry point.
+
+`encode_batch(..., device_deflate=True)` keeps the deflate on the device as well (dspn_png_deflate_batch: matches of distance 1
+only, dynamic Huffman codes per block of 32768 bytes, the rule in include/dspn_png_encode.h): only the compressed bytes cross
+to the host, which adds the chunks and their CRC-32.  `deflate_batch` is that deflate alone over any byte streams,
+`deflate_host` the same encoder on the host (the same bytes, no GPU)."""
+import ctypes
 import struct
 import zlib
 from concurrent.futures import ThreadPoolExecutor
@@ -122,21 +128,144 @@ def assemble(filtered, width, height, bytes_per_pixel, compress_level=6):
                      _chunk(b"IDAT", idat), _chunk(b"IEND")))
 
 
-def encode_batch(images, compress_level=6, threads=None):
+def deflate_bound(nbytes):
+    """dspn_png_deflate_bound: the most a zlib stream of the device deflate takes for nbytes input bytes (0 below 1)"""
+    return _lib.lib().dspn_png_deflate_bound(int(nbytes))
+
+
+def deflate_host(data):
+    """dspn_png_deflate_host: a bytes-like of at least one byte -> the zlib stream the device deflate writes for it, as bytes,
+    formed on the host by the same encoder"""
+    src = np.frombuffer(data, np.uint8)
+    if src.size < 1:
+        raise _lib.DspnError("png_deflate: a stream of 0 bytes")
+    lib = _lib.lib()
+    out = np.empty(lib.dspn_png_deflate_bound(src.size), np.uint8)
+    length = ctypes.c_longlong(0)
+    _lib.check(lib.dspn_png_deflate_host(src.ctypes.data, src.size, out.ctypes.data, out.size, ctypes.addressof(length)), "png_deflate_host")
+    return out[:length.value].tobytes()
+
+
+def deflate_into(spans, pool, out, result, stream=None):
+    """dspn_png_deflate_batch: spans a list of (offset, bytes) into the uint8 device pool, out the uint8 device pool of at
+    least the sum of the bounds, result a device int64 tensor of 2 * len(spans) -> the workspace tensor (keep it alive until
+    the stream has run the call)"""
+    lib = _lib.lib()
+    offsets = np.ascontiguousarray([o for o, _ in spans], np.int64)
+    sizes = np.ascontiguousarray([n for _, n in spans], np.int64)
+    ws_bytes = lib.dspn_png_deflate_workspace_bytes(len(spans), int(sizes.sum()))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=out.device)
+    st = torch.cuda.current_stream(out.device).cuda_stream if stream is None else stream
+    _lib.check(lib.dspn_png_deflate_batch(offsets.ctypes.data, sizes.ctypes.data, len(spans), pool.data_ptr(), pool.numel(),
+                                          out.data_ptr(), out.numel(), result.data_ptr(), ws.data_ptr(), ws_bytes, st), "png_deflate")
+    return ws
+
+
+def _deflate_to_host(spans, pool):
+    """the zlib streams of the spans of a device pool -> (uint8 host array in pinned memory, list of (offset, bytes)): the
+    launches, one small copy of `result`, one copy of the used prefix of the output"""
+    dev = pool.device
+    with torch.cuda.device(dev):
+        out = torch.empty(sum(deflate_bound(n) for _, n in spans), dtype=torch.uint8, device=dev)
+        result = torch.empty(2 * len(spans), dtype=torch.int64, device=dev)
+        ws = deflate_into(spans, pool, out, result)
+        placed = result.cpu().numpy().reshape(-1, 2)            # waits for the launches
+        used = int(placed[-1, 0] + placed[-1, 1])
+        host = torch.empty(used, dtype=torch.uint8).pin_memory()
+        host.copy_(out[:used], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+    del ws
+    return host.numpy(), [(int(o), int(n)) for o, n in placed]
+
+
+def deflate_batch(streams):
+    """list of byte streams of at least one byte each -- 1-d uint8 device tensors, or host tensors / arrays / bytes-likes,
+    which are uploaded first -- -> list of zlib streams as bytes, each equal to deflate_host's for the same input.  One call
+    of dspn_png_deflate_batch for the batch, one small copy of its result table and one copy of the used prefix of its output
+    into pinned memory."""
+    streams = list(streams)
+    if not streams:
+        return []
+    dev = next((s.device for s in streams if torch.is_tensor(s) and s.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    flat = []
+    for k, s in enumerate(streams):
+        t = s.detach() if torch.is_tensor(s) else torch.from_numpy(np.frombuffer(s, np.uint8).copy())
+        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < 1:
+            raise _lib.DspnError("png_deflate: stream %d: a 1-d uint8 stream of at least one byte, got %s %s" % (k, t.dtype, tuple(t.shape)))
+        if t.is_cuda and t.device != dev:
+            raise _lib.DspnError("png_deflate: stream %d is on %s, the batch on %s" % (k, t.device, dev))
+        flat.append(t.to(dev).contiguous())
+    spans, at = [], 0
+    for t in flat:
+        spans.append((at, t.numel()))
+        at += t.numel()
+    with torch.cuda.device(dev):
+        pool = flat[0] if len(flat) == 1 else torch.cat(flat)
+    host, placed = _deflate_to_host(spans, pool)
+    return [host[o:o + n].tobytes() for o, n in placed]
+
+
+def _filter_and_deflate(images):
+    """-> (uint8 host array of the zlib streams, list of (offset, bytes, height, width, bytes per pixel)): the filter call and
+    the deflate call on one stream; the filtered streams stay on the device"""
+    geometry = [_geometry(k, im) for k, im in enumerate(images)]
+    dev, tensors = _on_device(images)
+    samples = np.zeros(len(images), SAMPLE)
+    spans = []
+    so = oo = 0
+    for s, (h, w, bpp) in zip(samples, geometry):
+        s["src_offset"], s["out_offset"], s["width"], s["height"], s["bytes_per_pixel"], s["src_pitch"] = so, oo, w, h, bpp, w * bpp
+        n = h * (1 + w * bpp)
+        spans.append((oo, n))
+        so += h * w * bpp
+        oo += n
+    with torch.cuda.device(dev):
+        flat = [t.reshape(-1).view(torch.uint8) for t in tensors]
+        src = flat[0] if len(flat) == 1 else torch.cat(flat)
+        filtered = torch.empty(oo, dtype=torch.uint8, device=dev)
+        ws = filter_into(samples, src, filtered)
+        host, placed = _deflate_to_host(spans, filtered)
+    del ws
+    return host, [(o, n, h, w, bpp) for (o, n), (h, w, bpp) in zip(placed, geometry)]
+
+
+def wrap(idat, width, height, bytes_per_pixel):
+    """the file around one finished zlib stream: signature, IHDR, one IDAT, IEND"""
+    depth, colour = FORMATS[bytes_per_pixel]
+    return b"".join((_dp.SIGNATURE, _chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, depth, colour, 0, 0, 0)),
+                     _chunk(b"IDAT", idat), _chunk(b"IEND")))
+
+
+def encode_batch(images, compress_level=6, threads=None, device_deflate=False):
     """list of images of any mix of sizes -- (H, W) uint8, (H, W) uint16 or (H, W, 3) uint8 RGB; device tensors, or host
     tensors / arrays, which are uploaded first -- -> list of PNG files as bytes (modes L, I;16 and RGB).  One filter call,
     one copy of the filtered streams into pinned memory, then deflate (compress_level, Z_FILTERED: Pillow's settings) and the
     chunks of each image on `threads` threads (default 8, never more than images).  DspnError names a dtype or shape outside
-    the three formats."""
+    the three formats.
+
+    device_deflate=True: the filter call's output feeds dspn_png_deflate_batch on the same stream, the filtered streams are
+    not copied to the host, and the threads only form the CRC-32 and the chunks.  compress_level is not used on this path.
+    The files hold the same pixels and the same filtered stream; they are larger than the default path's (about
+    1.6 times for label maps, under 1 % for photo-like images), which is why it is opt-in.  It is for large photo-like
+    images, where the host deflate is nearly all of the call."""
     images = list(images)
     if not images:
         return []
-    host, spans = _filter_to_host(images)
     threads = _THREADS if threads is None else int(threads)
+    if device_deflate:
+        host, spans = _filter_and_deflate(images)
 
-    def one(span):
-        o, n, h, w, bpp = span
-        return assemble(memoryview(host[o:o + n]), w, h, bpp, compress_level)
+        def one(span):
+            o, n, h, w, bpp = span
+            return wrap(memoryview(host[o:o + n]), w, h, bpp)
+    else:
+        host, spans = _filter_to_host(images)
+
+        def one(span):
+            o, n, h, w, bpp = span
+            return assemble(memoryview(host[o:o + n]), w, h, bpp, compress_level)
 
     if threads <= 1 or len(images) == 1:
         return [one(s) for s in spans]

@@ -286,15 +286,17 @@ def save_png(path, tensor):
     Image.fromarray(np.ascontiguousarray(a)).save(path, format="PNG")
 
 
-def save_pngs(paths, tensors, compress_level=6):
+def save_pngs(paths, tensors, compress_level=6, device_deflate=False):
     """a batch of images -> PNG files: (H, W) uint8, (H, W) uint16 or (H, W, 3) uint8 RGB tensors of any mix of sizes, device
     or host (uploaded first).  The row filters of the whole batch run on the device in one call, deflate on a thread pool
-    (dataset/png_encode.py); the pixels and the filtered stream inside each file are those of `save_png`'s file."""
+    (dataset/png_encode.py); the pixels and the filtered stream inside each file are those of `save_png`'s file.
+    device_deflate=True: the deflate runs on the device too (png_encode.encode_batch's keyword: larger files, compress_level
+    not used; for large photo-like images)."""
     from ..dataset import png_encode
     paths, tensors = list(paths), list(tensors)
     if len(paths) != len(tensors):
         raise _lib.DspnError("save_pngs: %d paths for %d images" % (len(paths), len(tensors)))
-    for path, data in zip(paths, png_encode.encode_batch(tensors, compress_level=compress_level)):
+    for path, data in zip(paths, png_encode.encode_batch(tensors, compress_level=compress_level, device_deflate=device_deflate)):
         with open(path, "wb") as f:
             f.write(data)
 

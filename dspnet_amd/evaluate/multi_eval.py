@@ -61,7 +61,7 @@ def filter_detections(det, score_thresh=0.1):
 
 def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use_difficult=False,
                  voc07_metric=False, full_res=None, score_thresh=0.1, cityscapes=False, device_depth=False,
-                 results_dir=None, device_png=False):
+                 results_dir=None, device_png=False, device_deflate=False):
     """net: training graph (symbol.multitask_symbol_factory.get_multi_symbol_train); batches: iterable of dicts with
     'data' (B,3,H,W), 'label_det' (B,L,6), 'label_seg' (B,H/4,W/4) and optionally 'disparity' (B,hh,ww) host maps.
     -> dict name -> value, plus 'class_maps' (list of uint8 device tensors) when full_res=(H, W) is given.
@@ -80,7 +80,11 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
     it), or '%06d_gtFine_labelTrainIds.png' of the running image index.  None (the default) launches nothing, imports
     nothing and writes nothing.
     device_png=True: the files of a batch are written by one detect.render.save_pngs call (row filters on the device, deflate
-    on a thread pool) in place of two Pillow saves per image; same names, same pixels."""
+    on a thread pool) in place of two Pillow saves per image; same names, same pixels.
+    device_deflate=True (with device_png=True; a ValueError without it): that call deflates on the device as well
+    (dataset/png_encode.py); same names, same pixels, larger files."""
+    if device_deflate and not device_png:
+        raise ValueError("evaluate_net: device_deflate=True needs device_png=True (it is a switch of the device PNG writer)")
     render = image_index = None
     if results_dir is not None:
         from ..detect import render
@@ -129,7 +133,7 @@ def evaluate_net(net, batches, class_names, seg_class_names, ovp_thresh=0.5, use
                 images += [ids[i], mosaic[i]]
                 image_index += 1
             if device_png:
-                render.save_pngs(paths, images)
+                render.save_pngs(paths, images, device_deflate=device_deflate)
             else:
                 for path, image in zip(paths, images):
                     render.save_png(path, image)

@@ -5,12 +5,16 @@ script's output.  Everything is generated from seeds; it fails without a GPU.
 
 File sizes against Pillow's over the case list of tests/ref_png_encode.py and over 32 labelId maps (1024 x 2048) and 32
 evaluation mosaics (2048 x 4096 x 3); encode_batch end to end against the path it replaces (`.cpu()` and `Image.save` per
-image), the two alternated; the device call and the copy to the host by device events; one image's deflate on one thread."""
+image), the two alternated; the device call and the copy to the host by device events; one image's deflate on one thread.
+Then encode_batch(device_deflate=True) (dspn_png_deflate_batch) against encode_batch at 8 and 16 threads, alternated the same
+way; its split into filter, deflate launches, copies (device events) and host CRC-32 and chunks; its sizes against level 6
+and against zlib's Z_RLE."""
 import io
 import os
 import statistics
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -124,12 +128,15 @@ for label, arrays in (("labelId 1024x2048", ids), ("mosaic 2048x4096x3", mosaics
     say("  size ratio device path / Pillow over %d files: min %.4f max %.4f; mean file %.0f bytes, raw %.0f bytes" %
         (len(rr), min(rr), max(rr), sum(map(len, mine)) / len(mine), nbytes / len(arrays)))
     # alternate the paths
-    t_dev8, t_dev16, t_pil, t_filter = [], [], [], []
+    deflated = pe.encode_batch(tensors, device_deflate=True)
+    t_dev8, t_dev16, t_pil, t_filter, t_dd = [], [], [], [], []
     for _ in range(3):
+        _, t = timed(lambda: pe.encode_batch(tensors, device_deflate=True), 1); t_dd += t
         _, t = timed(lambda: pe.encode_batch(tensors), 1); t_dev8 += t
         _, t = timed(lambda: pillow_path(tensors), 1); t_pil += t
         _, t = timed(lambda: pe.encode_batch(tensors, threads=16), 1); t_dev16 += t
         _, t = timed(lambda: pe._filter_to_host(tensors), 1); t_filter += t
+    report("encode_batch, device_deflate=True", t_dd)
     report("encode_batch, 8 threads (default)", t_dev8)
     report("encode_batch, 16 threads", t_dev16)
     report(".cpu() + Image.save per image (parent path)", t_pil)
@@ -168,5 +175,53 @@ for label, arrays in (("labelId 1024x2048", ids), ("mosaic 2048x4096x3", mosaics
         o, n = int(s["out_offset"]), a.shape[0] * (1 + int(s["src_pitch"]))
         pe.assemble(memoryview(hn[o:o + n]), a.shape[1], a.shape[0], int(s["bytes_per_pixel"]))
     say("  deflate + chunks, one thread: %.1f ms per image" % ((time.perf_counter() - t0) / 4 * 1e3))
-    del tensors, src, out, host
+    # ---- the device deflate: sizes, then the split of the call
+    for m, a in zip(deflated[:3], arrays[:3]):
+        assert np.array_equal(np.asarray(Image.open(io.BytesIO(m))), a)
+    rle = []
+    for s, a in list(zip(samples, arrays))[:4]:
+        o, n = int(s["out_offset"]), a.shape[0] * (1 + int(s["src_pitch"]))
+        z = zlib.compressobj(6, zlib.DEFLATED, 15, 8, zlib.Z_RLE)
+        rle.append(len(z.compress(memoryview(hn[o:o + n])) + z.flush()))
+    r6 = [len(d) / len(m) for d, m in zip(deflated, mine)]
+    idat = [len(d) - 57 for d in deflated[:4]]              # signature, IHDR, IEND and the IDAT chunk's 12 bytes
+    say("  device_deflate size / level 6 over %d files: min %.4f max %.4f mean %.4f; / Z_RLE over 4 streams: %s" %
+        (len(r6), min(r6), max(r6), sum(r6) / len(r6), " ".join("%.4f" % (i / r) for i, r in zip(idat, rle))))
+    spans, at = [], 0
+    for s, a in zip(samples, arrays):
+        n = a.shape[0] * (1 + int(s["src_pitch"]))
+        spans.append((at, n))
+        at += n
+    zout = torch.empty(sum(pe.deflate_bound(n) for _, n in spans), dtype=torch.uint8, device=dev)
+    result = torch.empty(2 * len(spans), dtype=torch.int64, device=dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    tf, td, tc, th = [], [], [], []
+    for k in range(6):
+        ev[0].record()
+        ws = pe.filter_into(samples, src, out)
+        ev[1].record()
+        ws2 = pe.deflate_into(spans, out, zout, result)
+        ev[2].record()
+        placed = result.cpu().numpy().reshape(-1, 2)
+        used = int(placed[-1].sum())
+        zhost = torch.empty(used, dtype=torch.uint8).pin_memory()
+        zhost.copy_(zout[:used], non_blocking=True)
+        ev[3].record()
+        torch.cuda.synchronize()
+        zn = zhost.numpy()
+        t0 = time.perf_counter()
+        for (o, n), a in zip(placed, arrays):
+            pe.wrap(memoryview(zn[o:o + n]), a.shape[1], a.shape[0], 3 if a.ndim == 3 else a.itemsize)
+        t1 = time.perf_counter()
+        if k:
+            tf.append(ev[0].elapsed_time(ev[1]) / 1e3)
+            td.append(ev[1].elapsed_time(ev[2]) / 1e3)
+            tc.append(ev[2].elapsed_time(ev[3]) / 1e3)
+            th.append(t1 - t0)
+    report("device_deflate: filter (events)", tf)
+    report("device_deflate: table copy + 5 deflate launches", td)
+    report("device_deflate: result + %d bytes to the host" % used, tc)
+    report("device_deflate: CRC-32 + chunks, one thread", th)
+    say("  deflate: %.1f GB/s of filtered bytes" % (oo / min(td) / 1e9))
+    del tensors, src, out, host, zout
 say("done")
